@@ -11,7 +11,9 @@ A step = one pass of the hot path (detector record on device -> logical predicti
 over one batch of `--shots` DEM-sampled shots.  Inputs are generated on the device before the timed region.
 One process per GPU; shots are independent so ranks share nothing but the final (errors, shots) all-reduce.
 
-Prints ONE JSON line on rank 0 (contract in the task description), with `roofline` and `cpu_baseline` objects.
+Prints ONE JSON line on rank 0: the headline and the statistics of the timed steps.  A plain run does nothing else; `--full`
+adds the kernel-event pass (`roofline`), `through_api`, `cpu_baseline` and `other_configs`.  `--dump-outputs DIR` saves what the
+last timed step computed (inputs are seeded: the same arguments give the same inputs).
 """
 import argparse
 import json
@@ -239,6 +241,13 @@ def main():
     ap.add_argument("--dry-run-backend", default=None, help=argparse.SUPPRESS)   # tests: rank plumbing + collectives on CPU (gloo), no decoding
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip the `other_configs` array (the other BASELINE configs and window shapes, each timed for two short steps)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the line can carry: the kernel-event pass and `roofline`, `through_api`, "
+                         "`cpu_baseline` and `other_configs` (each still subject to its --no-* switch); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR: predictions.npy (float32 [shots, observables]; a fixed "
+                         "seeded sample of rows when the whole array would pass 64 MB) and mismatches.npy (float64 [1]); "
+                         "_rank<r> is appended to the names when --gpus > 1")
     args = ap.parse_args()
 
     from quits_amd import parallel
@@ -266,8 +275,8 @@ def main():
     torch.cuda.set_device(local_rank % torch.cuda.device_count() if share else local_rank)
     dist = parallel.init_distributed(os.environ.get("QD_BENCH_DIST_BACKEND", "nccl"))      # "nccl" is RCCL on ROCm; None for a single process
 
-    out = run(args, rank, world, dist, full=True)
-    if rank == 0 and world == 1 and not args.no_other_configs and args.code == "bb144" and args.window is None \
+    out = run(args, rank, world, dist, full=args.full, kernel_pass=args.full, dump_dir=args.dump_outputs)
+    if args.full and rank == 0 and world == 1 and not args.no_other_configs and args.code == "bb144" and args.window is None \
             and args.osd_method == "osd_0" and not (args.bp_method != "minimum_sum" or args.schedule != "parallel"):
         out["other_configs"] = other_configs(args)
         # the same list once more, compact and LAST in the line: the driver's record keeps the tail of stdout (VERDICT r5 weak 10:
@@ -342,7 +351,24 @@ def other_configs(args):
     return res
 
 
-def run(args, rank, world, dist, full=True):
+DUMP_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(dump_dir, pred, mismatches, suffix=""):
+    """--dump-outputs: the logical predictions (uint8 [shots, observables] on the device) and the mismatch count of one step.
+    Rows are sampled with a fixed seed when the float32 array would exceed DUMP_BYTES."""
+    os.makedirs(dump_dir, exist_ok=True)
+    p = pred.cpu().numpy()
+    rows = max(1, (DUMP_BYTES - 4096) // (4 * max(1, p.shape[1])))
+    if p.shape[0] > rows:
+        p = p[np.sort(np.random.default_rng(2026).choice(p.shape[0], rows, replace=False))]
+    np.save(os.path.join(dump_dir, "predictions%s.npy" % suffix), p.astype(np.float32))
+    np.save(os.path.join(dump_dir, "mismatches%s.npy" % suffix), np.array([int(mismatches.item())], dtype=np.float64))
+
+
+def run(args, rank, world, dist, full=True, kernel_pass=True, dump_dir=None):
+    """One configuration: set up, warm up, time args.steps steps.  kernel_pass: the same steps again with the library's kernel
+    events on, for `roofline`; full: `through_api` and `cpu_baseline` as well (rank 0, N = 1)."""
     import helpers
     from quits_amd import parallel
     from quits_amd.decoder.base import detector_error_model_to_matrix
@@ -428,7 +454,7 @@ def run(args, rank, world, dist, full=True):
     fails = torch.zeros((1,), dtype=torch.int64, device="cuda")
     stats = []
     for i in range(args.warmup, nbatch):
-        c, _ = step(i, stats)
+        c, pred = step(i, stats)
         fails += c
     torch.cuda.synchronize()
     if dist is not None:
@@ -437,13 +463,52 @@ def run(args, rank, world, dist, full=True):
     elapsed = parallel.reduce_max(dist, elapsed, "cuda")
     # the path's only collective: 16 bytes over RCCL
     n_err, n_shots = parallel.reduce_counts(dist, int(fails.item()), args.shots * args.steps, "cuda")
+    if dump_dir:
+        dump_outputs(dump_dir, pred, c, "_rank%d" % rank if world > 1 else "")
+
+    pipelined = bool(plan.pipeline and args.shots >= 2 * plan.chunk)
+    st = torch.cat([t for (_, t) in stats])
+    iters = (st & 0x3FFF).to(torch.int64)
+    total_iters = int(iters.sum().item())
+    conv_frac = float(((st >> 16) & 1).float().mean().item())
+    osd_frac = float(((st >> 17) & 1).float().mean().item())
+    off_grid = int(((st >> 14) & 3).ne(0).sum().item())
+    value = n_shots / elapsed
+    pl = n_err / n_shots
+    dinfo = decs[0].info()
+    out = {
+        "metric": "decoded shots/sec + logical-error-rate, [[144,12,12]] BB code, d rounds, p=0.003",
+        "value": value, "unit": "shots/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": data_note,
+        "sampler": "stim" if stim_mod is not None else "device DEM sampler (qd_sample_dem_kernel: e ~ Bernoulli(priors), s = He, o = Le); stim: %s" % stim_info,
+        "arithmetic": ("f32 on channel LLRs rounded to multiples of 2^-%d: exact (no operation rounds; certified per shot), i.e. the "
+                       "result ldpc's f64 BpDecoder returns for those LLRs; %d of %d shot-windows left the fine grid"
+                       % (dinfo["llr_grid_bits"], off_grid, st.numel())) if dinfo["llr_grid_bits"] >= 0 else "f32, float(log((1-p)/p)) LLRs",
+        "config": {"workload": "%s circuit %s, R=%d, Z basis; DEM %dx%d (E=%d); "
+                               "%s %s BP max_iter=%d ms_scaling=1.0 + %s(%d); W=%d F=%d (%d window%s)"
+                               % ({"bb144": "BB [[144,12,12]]", "bb72": "BB [[72,12,6]]", "hgp225": "HGP [[225,9,6]]", "qlp1020": "QLP [[1020,136]]"}[args.code],
+                                  cname, R, m, n, E, args.bp_method, args.schedule, args.max_iter, args.osd_method, args.osd_order, W, F, len(plan.windows),
+                                  "" if len(plan.windows) == 1 else "s"),
+                   "shots_per_step_per_gpu": args.shots, "parallelism": "shots sharded over %d GPU(s), no data-path collective" % world},
+        "logical_error_rate": pl, "ler_sigma": float(np.sqrt(max(pl * (1 - pl), 1e-30) / n_shots)),
+        "lfr_per_round": 1.0 - (1.0 - pl) ** (1.0 / R),
+        "bp_converged_frac": conv_frac, "osd_frac": osd_frac, "mean_bp_iters": total_iters / max(1, st.numel()),
+        "pipeline": {"osd_beside_next_chunk_bp": pipelined, "chunk_shots": plan.chunk,
+                     "note": "timed region: chunk i's post-processing on a second stream beside chunk i+1's BP (two workspaces); "
+                             "ms_per_step_with_kernel_events and the roofline's per-kernel times are from a pass with the kernels back to back"},
+        # SURVEY.md 8(d): early exit makes the work data-dependent -- shot-windows by BP iterations used (index = iterations)
+        "bp_iters_hist": torch.bincount(iters.clamp(max=args.max_iter), minlength=args.max_iter + 1).tolist(),
+    }
+    if not kernel_pass:
+        plan.release_workspaces()
+        return out
 
     # ---- the same K steps once more with the library's HIP events on (recorded on the launch stream around each kernel):
     # per-kernel device time for the roofline object
     # (kernels back to back on one stream in this pass: the per-kernel times the roofline is priced on are those of a kernel that
     # has the GPU to itself, as under rocprofv3 --kernel-trace of a QD_NO_PIPELINE=1 run; the timed region above overlaps them)
     pipeline_setting = plan.pipeline
-    pipelined = bool(plan.pipeline and args.shots >= 2 * plan.chunk)
     plan.pipeline = False
     for d in decs:
         d.set_profiling(True)
@@ -461,12 +526,6 @@ def run(args, rank, world, dist, full=True):
         d.set_profiling(False)
         for k in prof:
             prof[k] += pr[k]
-    st = torch.cat([t for (_, t) in stats])
-    iters = (st & 0x3FFF).to(torch.int64)
-    total_iters = int(iters.sum().item())
-    conv_frac = float(((st >> 16) & 1).float().mean().item())
-    osd_frac = float(((st >> 17) & 1).float().mean().item())
-    off_grid = int(((st >> 14) & 3).ne(0).sum().item())
     bp_s = prof["bp_ms"] / 1e3
     nlaunch = max(1, prof["bp_launches"])
 
@@ -657,35 +716,8 @@ def run(args, rank, world, dist, full=True):
             "chain": (osd_pm or {}).get("chain"),
         }
 
-    value = n_shots / elapsed
-    pl = n_err / n_shots
-    dinfo = decs[0].info()
-    out = {
-        "metric": "decoded shots/sec + logical-error-rate, [[144,12,12]] BB code, d rounds, p=0.003",
-        "value": value, "unit": "shots/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f32", "data": data_note,
-        "sampler": "stim" if stim_mod is not None else "device DEM sampler (qd_sample_dem_kernel: e ~ Bernoulli(priors), s = He, o = Le); stim: %s" % stim_info,
-        "arithmetic": ("f32 on channel LLRs rounded to multiples of 2^-%d: exact (no operation rounds; certified per shot), i.e. the "
-                       "result ldpc's f64 BpDecoder returns for those LLRs; %d of %d shot-windows left the fine grid"
-                       % (dinfo["llr_grid_bits"], off_grid, st.numel())) if dinfo["llr_grid_bits"] >= 0 else "f32, float(log((1-p)/p)) LLRs",
-        "config": {"workload": "%s circuit %s, R=%d, Z basis; DEM %dx%d (E=%d); "
-                               "%s %s BP max_iter=%d ms_scaling=1.0 + %s(%d); W=%d F=%d (%d window%s)"
-                               % ({"bb144": "BB [[144,12,12]]", "bb72": "BB [[72,12,6]]", "hgp225": "HGP [[225,9,6]]", "qlp1020": "QLP [[1020,136]]"}[args.code],
-                                  cname, R, m, n, E, args.bp_method, args.schedule, args.max_iter, args.osd_method, args.osd_order, W, F, len(plan.windows),
-                                  "" if len(plan.windows) == 1 else "s"),
-                   "shots_per_step_per_gpu": args.shots, "parallelism": "shots sharded over %d GPU(s), no data-path collective" % world},
-        "logical_error_rate": pl, "ler_sigma": float(np.sqrt(max(pl * (1 - pl), 1e-30) / n_shots)),
-        "lfr_per_round": 1.0 - (1.0 - pl) ** (1.0 / R),
-        "bp_converged_frac": conv_frac, "osd_frac": osd_frac, "mean_bp_iters": total_iters / max(1, st.numel()),
-        "ms_per_step_with_kernel_events": 1e3 * elapsed_ev / args.steps,
-        "pipeline": {"osd_beside_next_chunk_bp": pipelined, "chunk_shots": plan.chunk,
-                     "note": "timed region: chunk i's post-processing on a second stream beside chunk i+1's BP (two workspaces); "
-                             "ms_per_step_with_kernel_events and the roofline's per-kernel times are from a pass with the kernels back to back"},
-        # SURVEY.md 8(d): early exit makes the work data-dependent -- shot-windows by BP iterations used (index = iterations)
-        "bp_iters_hist": torch.bincount(iters.clamp(max=args.max_iter), minlength=args.max_iter + 1).tolist(),
-        "roofline": roofline,
-    }
+    out["ms_per_step_with_kernel_events"] = 1e3 * elapsed_ev / args.steps
+    out["roofline"] = roofline
 
     if full and rank == 0 and world == 1 and not args.no_api and args.osd_method.startswith("osd"):
         out["through_api"] = through_api(args, circ, hz, lz, W, F, sampler, value)

@@ -1207,3 +1207,45 @@ def test_scatter_accumulator_banks_and_walk_do_not_change_results(gpu, monkeypat
         assert np.array_equal(o[0], outs[0][0]) and np.array_equal(o[1], outs[0][1])
     assert 0 < infos[0]["scatter_walk_ideal"] <= infos[0]["scatter_walk_cycles"] <= 1.15 * infos[0]["scatter_walk_ideal"], infos[0]
     assert infos[3]["scatter_walk_cycles"] > infos[0]["scatter_walk_cycles"]          # the old layout and walk cost more LDS cycles in the same model
+
+
+def test_bench_plain_run_dumps_the_last_timed_step(gpu, tmp_path):
+    """bench.py without --full: the headline keys, --steps timed steps and none of the --full extras.  --dump-outputs writes the last
+    timed step's predictions and mismatch count: the same on a second run, and equal to the oracle's on the same seeded shots (the
+    device DEM sampler is counter-based: the last step decodes shots [(warmup + steps - 1) N, (warmup + steps) N))."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from quits_amd.decoder.base import spacetime, window_count
+    from quits_amd.dem import Circuit
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    name, shots, steps, warmup, max_iter = "bb72_custom_r6_p0.003", 1024, 3, 1, 20
+    lines, dumps = [], []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--code", "bb72", "--shots", str(shots),
+                            "--steps", str(steps), "--warmup", str(warmup), "--max-iter", str(max_iter), "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]))
+        dumps.append((np.load(d / "predictions.npy"), np.load(d / "mismatches.npy")))
+    line = lines[0]
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(line)
+    assert line["steps"] == steps and line["value"] > 0 and line["ms_per_step"] > 0
+    assert not {"roofline", "ms_per_step_with_kernel_events", "through_api", "cpu_baseline", "other_configs"} & set(line)
+    pred, mism = dumps[0]
+    assert pred.dtype == np.float32 and pred.shape == (shots, 12) and mism.dtype == np.float64
+    assert np.array_equal(pred, dumps[1][0]) and np.array_equal(mism, dumps[1][1])
+    H, L, pri = helpers.dem_matrices(name)
+    det, obs, _ = orc.sample_dem(H, L, pri, seed=1, shot0=(warmup + steps - 1) * shots, B=shots)
+    assert mism[0] == (pred != obs).any(axis=1).sum()
+    cd = helpers.code("bb72")
+    R, W, F = 6, 8, 1                                   # bench.py's single window over the whole history: W = R + 2
+    ncr, _, _ = window_count(R, W, F)
+    checks, commits, priors, updates = spacetime(Circuit(helpers.circuit_text(name)), cd["hz"], W, F, ncr)
+    wins = [{"H": checks[k], "L": commits[k], "priors": priors[k], "U": updates[k] if k < ncr else None, "row0": F * k * cd["hz"].shape[0]}
+            for k in range(len(checks))]
+    ref, _ = orc.sliding_window_decode(wins, cd["hz"].shape[0], det,
+                                       orc.make_params("minimum_sum", "parallel", max_iter, "osd_0", 0, 1.0, orc.FORM_LDPC_F64), device_grid=True)
+    assert np.array_equal(pred, ref.astype(np.float32))

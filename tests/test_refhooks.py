@@ -152,6 +152,26 @@ def test_bench_cpu_baseline_kind_follows_the_import(stub_wheels, monkeypatch):
     assert "cpu_baseline_port" not in res
 
 
+def test_bench_dump_outputs_dtypes_budget_and_names(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 predictions and a float64 mismatch count; over the byte budget, the same seeded sample of
+    rows on every call, in row order; the rank suffix of an N > 1 run."""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    pred = np.random.default_rng(1).integers(0, 2, (5000, 12), dtype=np.uint8)
+    bench.dump_outputs(str(tmp_path / "a"), torch.from_numpy(pred), torch.tensor([7]))
+    p, m = np.load(tmp_path / "a" / "predictions.npy"), np.load(tmp_path / "a" / "mismatches.npy")
+    assert p.dtype == np.float32 and np.array_equal(p, pred)
+    assert m.dtype == np.float64 and m.tolist() == [7.0]
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4096 + 4 * 12 * 1000)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), torch.from_numpy(pred), torch.tensor([7]), "_rank1")
+    b, c = np.load(tmp_path / "b" / "predictions_rank1.npy"), np.load(tmp_path / "c" / "predictions_rank1.npy")
+    assert b.shape == (1000, 12) and np.array_equal(b, c)
+    assert np.array_equal(b, pred[np.sort(np.random.default_rng(2026).choice(5000, 1000, replace=False))])
+    assert os.path.exists(tmp_path / "b" / "mismatches_rank1.npy")
+
+
 def test_pin_ldpc_end_to_end_with_the_stub(stub_wheels, tmp_path, monkeypatch, capsys):
     import pin_ldpc
     monkeypatch.setattr(pin_ldpc, "FIXTURES", [("bb72_custom_r6_p0.003", (3, 1, 0))])

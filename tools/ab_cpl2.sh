@@ -11,7 +11,7 @@ run() {   # run <switch> <bench args>
   local SW=$1; shift
   for sw in 0 1 0 1; do
     if [ $sw = 1 ]; then export $SW=1; else unset $SW; fi
-    timeout 600 python bench.py --steps 3 --warmup 1 --no-cpu "$@" 2>/dev/null | tail -1 | python -c "
+    timeout 600 python bench.py --full --steps 3 --warmup 1 --no-cpu "$@" 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']; print('$SW=$sw $*', round(d['value']), round(d['ms_per_step'],2), d.get('logical_error_rate'), r['kernel'], round(r['avg_launch_ms'],2), round(r['osd_kernel_ms_per_launch'],2), round(r['frac'],3))
 "

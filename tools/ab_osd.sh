@@ -5,7 +5,7 @@ for rep in 1 2; do
   for v in A B; do
     if [ $v = A ]; then lib=$1; extra=""; else lib=$2; extra="$3"; fi
     for p in 0.003 0.006; do
-      env QUITS_AMD_LIB=$PWD/$lib $extra timeout 200 python bench.py --p $p --steps 3 --warmup 1 --no-cpu 2>/dev/null | tail -1 | \
+      env QUITS_AMD_LIB=$PWD/$lib $extra timeout 200 python bench.py --full --p $p --steps 3 --warmup 1 --no-cpu 2>/dev/null | tail -1 | \
         python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$v', '$p', round(d['value']), round(d['roofline']['avg_launch_ms'],2), round(d['roofline']['osd_kernel_ms_per_launch'],2))"
     done
   done

@@ -8,7 +8,7 @@ O=gpurun_out/$TAG
 mkdir -p $O
 timeout 900 python -m pytest tests -m gpu -q -x -k "wide_scatter or config4_qlp or scatter_kernel_and" > $O/tests.txt 2>&1
 tail -5 $O/tests.txt
-B="python bench.py --code qlp1020 --window 3 1 --shots 8192 --steps 2 --warmup 1 --no-cpu"
+B="python bench.py --full --code qlp1020 --window 3 1 --shots 8192 --steps 2 --warmup 1 --no-cpu"
 for a in "--p-override 0.001" "--p-override 0.0005" ""; do
   for sw in 0 1 0 1; do
     if [ $sw = 1 ]; then export QD_NO_SCATTER_WIDE=1; else unset QD_NO_SCATTER_WIDE; fi

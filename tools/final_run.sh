@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 make -C oracle -s 2>&1 | tail -2
 O=gpurun_out/$TAG
 mkdir -p $O
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 tail -c 600 $O/bench.json
 bash tools/profile_bench.sh $TAG > $O/profile_bench.log 2>&1
 bash tools/pmc_bp_kernel.sh $TAG > $O/pmc_bp_kernel.log 2>&1

@@ -12,7 +12,7 @@ for set in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_VMEM_RD S
            "SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA SQ_INST_CYCLES_SALU SQ_THREAD_CYCLES_VALU SQ_INSTS_VMEM_WR SQ_INSTS_FLAT SQ_LDS_UNALIGNED_STALL SQ_LDS_ADDR_CONFLICT" \
            "GRBM_GUI_ACTIVE TCC_HIT_sum TCC_MISS_sum TCP_TCC_READ_REQ_sum"; do
   i=$((i+1))
-  rocprofv3 --pmc $set -f csv -d $OUT/p$i -o p$i -- python $REPO/bench.py $ARGS > $OUT/p$i.json 2> $OUT/p$i.err || tail -3 $OUT/p$i.err
+  rocprofv3 --pmc $set -f csv -d $OUT/p$i -o p$i -- python $REPO/bench.py --full $ARGS > $OUT/p$i.json 2> $OUT/p$i.err || tail -3 $OUT/p$i.err
 done
 python - <<PY
 import csv, glob, collections

@@ -1,7 +1,7 @@
 #!/bin/bash
 # BASELINE.json configs beyond the headline, one JSON line each (GPU box).  usage: tools/run_configs.sh > out.jsonl
 cd "$(dirname "$0")/.."
-B="python bench.py --steps 2 --warmup 1 --cpu-shots 300"
+B="python bench.py --full --steps 2 --warmup 1 --cpu-shots 300"
 $B --code hgp225 --shots 16384 --max-iter 30 2>/dev/null                 # configs[0] shape on the GPU (single window)
 $B --code hgp225 --shots 16384 --max-iter 30 --window 3 1 2>/dev/null
 $B --code bb72 --shots 65536 2>/dev/null                                   # configs[1]: [[72,12,6]], single window
