@@ -54,6 +54,7 @@ extern "C" {
 typedef struct qd_graph qd_graph;       /* one window's Tanner graph + priors, resident on one device */
 typedef struct qd_decoder qd_decoder;   /* graph + parameters + device workspace                      */
 typedef struct qd_spmat qd_spmat;       /* sparse GF(2) matrix on the device (L_k, U_k, H for sampling) */
+typedef struct qd_circuit qd_circuit;   /* compiled circuit program of the frame sampler, on the device */
 
 /* qd_params.reserved: run flooding min-sum in the one-message-per-edge kernel too (ldpc's own update order, prefix sums
  * instead of "total minus own").  On the LLR grid both kernels compute exactly and agree bit for bit.  Validation aid. */
@@ -73,7 +74,7 @@ typedef struct qd_params {
     double ms_scaling_factor;   /* not exposed by the reference wrapper -> ldpc default 1.0; 0 = 1-2^-it */
 } qd_params;
 
-int qd_version(void);                 /* 103 (103: qd_decoder_post_head_start; 101: qd_graph_info wrote 12 entries; 102: 10 again + qd_graph_info_ex) */
+int qd_version(void);                 /* 104 (104: qd_circuit_* + qd_sample_circuit; 103: qd_decoder_post_head_start; 101: qd_graph_info wrote 12 entries; 102: 10 again + qd_graph_info_ex) */
 const char *qd_last_error(void);
 /* Number of visible HIP devices (0 if none): lets a host fail loudly before building anything. */
 int qd_device_count(void);
@@ -204,6 +205,24 @@ int qd_count_mismatch(const uint8_t *d_pred, const uint8_t *d_obs, int32_t k, in
  *      d_det: B x det_stride bytes (first m columns written), d_obs: B x obs_stride bytes. */
 int qd_sample_dem(const qd_spmat *Ht, const qd_spmat *Lt, const double *priors, uint64_t seed, int64_t shot0,
                   int64_t B, uint8_t *d_det, int64_t det_stride, uint8_t *d_obs, int64_t obs_stride, void *stream);
+
+/* ---- circuit-level input: a Pauli-frame simulation of the circuit itself (what stim's compile_detector_sampler().sample(...,
+ *      separate_observables=True) returns, simulation.py:8-28), without gauge randomisation: exact when every detector and observable
+ *      is deterministic, as in every QUITS circuit.  quits_amd/frame.py compiles the circuit text into `program` (int32 words; the layout
+ *      and the frame rules are in its docstring), one threshold floor(p * 2^32) per distinct noise probability, and the measurement ring
+ *      length max_lookback (>= the largest rec[-k] look-back and >= the widest measurement instruction).  Every index in the program is
+ *      checked here; QD_ECAPACITY when 8 * (2 nq + max_lookback + nobs) bytes exceed the kernel's 64 KiB of LDS per 64 shots. */
+int qd_circuit_create(const int32_t *program, int64_t program_len, int32_t nq, int32_t nmeas, int32_t ndet, int32_t nobs,
+                      const uint32_t *thresholds, int32_t nthr, int32_t max_lookback, int32_t device, qd_circuit **out);
+void qd_circuit_destroy(qd_circuit *c);
+/* info[8] = {qubits, noise sites, LDS bytes per wavefront of 64 shots, measurements, detectors, observables, ring length, program words} */
+int qd_circuit_info(const qd_circuit *c, int64_t *info);
+/* Shots shot0 .. shot0 + B - 1.  Noise site j of shot s fires iff r < threshold, r = word (j & 3) of
+ * Philox4x32-10(key = (seed lo, seed hi), counter = (s lo, s hi, j >> 2, 1)); a depolarizing site's Pauli comes from the same r
+ * (1 + r mod 3, or 1 + r mod 15 split as (v >> 2, v & 3)).  The stream depends on (seed, shot, site) only: calls with
+ * consecutive shot0 compose.  d_det: B x det_stride bytes (first ndet columns written), d_obs: B x obs_stride bytes.  Asynchronous. */
+int qd_sample_circuit(const qd_circuit *c, uint64_t seed, int64_t shot0, int64_t B, uint8_t *d_det, int64_t det_stride,
+                      uint8_t *d_obs, int64_t obs_stride, void *stream);
 
 #ifdef __cplusplus
 }

@@ -44,6 +44,7 @@ EXPORTS = [
     "qd_decoder_create", "qd_decoder_info", "qd_decoder_postproc_kernel", "qd_decoder_destroy", "qd_decoder_reserve", "qd_decoder_set_workspace_limit", "qd_decoder_release_workspace", "qd_decode_batch", "qd_decode_stage", "qd_osd0_batch", "qd_decoder_failed_llr",
     "qd_decoder_set_profiling", "qd_decoder_profile", "qd_decoder_post_head_start", "qd_decoder_debug_counters", "qd_spmat_create", "qd_spmat_destroy", "qd_gf2_spmv_batch",
     "qd_unpack_bits", "qd_count_mismatch", "qd_sample_dem",
+    "qd_circuit_create", "qd_circuit_destroy", "qd_circuit_info", "qd_sample_circuit",
 ]
 
 
@@ -66,8 +67,8 @@ def load():
     L = C.CDLL(LIB_PATH)
     vp, i32, i64, u64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64
     L.qd_version.restype = C.c_int
-    if L.qd_version() < 103:              # 103: qd_decoder_post_head_start (the pipelined driver); 102: qd_graph_info_ex and the 10-entry qd_graph_info
-        raise RuntimeError("quits_amd: %s is version %d, this package needs >= 103 -- rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)"
+    if L.qd_version() < 104:              # 104: the circuit sampler; 103: qd_decoder_post_head_start (the pipelined driver); 102: qd_graph_info_ex
+        raise RuntimeError("quits_amd: %s is version %d, this package needs >= 104 -- rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)"
                            % (LIB_PATH, L.qd_version()))
     L.qd_last_error.restype = C.c_char_p
     L.qd_device_count.restype = C.c_int
@@ -100,6 +101,11 @@ def load():
     L.qd_unpack_bits.argtypes = [vp, i64, i32, i64, vp, i64, vp]
     L.qd_count_mismatch.argtypes = [vp, vp, i32, i64, vp, vp]
     L.qd_sample_dem.argtypes = [vp, vp, vp, u64, i64, i64, vp, i64, vp, i64, vp]
+    L.qd_circuit_create.argtypes = [vp, i64, i32, i32, i32, i32, vp, i32, i32, i32, C.POINTER(vp)]
+    L.qd_circuit_destroy.argtypes = [vp]
+    L.qd_circuit_destroy.restype = None
+    L.qd_circuit_info.argtypes = [vp, vp]
+    L.qd_sample_circuit.argtypes = [vp, u64, i64, i64, vp, i64, vp, i64, vp]
     _lib = L
     return L
 

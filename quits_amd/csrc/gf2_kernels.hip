@@ -83,21 +83,7 @@ __global__ void qd_count_mismatch_kernel(const uint8_t *__restrict__ pred, const
 
 // ---- DEM sampler (stands in for stim's detector sampler, quits/simulation.py:23-27).  Same integer recipe as
 // oq_sample_dem (oracle/qd_oracle.c): Philox4x32-10, key = seed, counter = (shot lo, shot hi, j / 4, 0); word j & 3
-// fires fault j iff it is < floor(p_j * 2^32).  One workgroup per shot, detector/observable bits accumulated in LDS.
-__device__ __forceinline__ void qd_philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
-                                                 uint32_t k1, uint32_t out[4])
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
+// fires fault j iff it is < floor(p_j * 2^32) (qd_philox4x32_10: qd_internal.h).  One workgroup per shot, detector/observable bits accumulated in LDS.
 __global__ void qd_sample_dem_kernel(SpmatDev Ht, SpmatDev Lt, const uint32_t *__restrict__ thr, uint32_t k0,
                                      uint32_t k1, int64_t shot0, int m, int nobs, uint8_t *det, int64_t det_stride,
                                      uint8_t *obs, int64_t obs_stride)

@@ -318,7 +318,7 @@ static void scatter_walk(int m, const int32_t *row_ptr, const int32_t *col_idx, 
     }
 }
 
-extern "C" int qd_version(void) { return 103; }      // 103: qd_decoder_post_head_start; 102: qd_graph_info fills 10 entries again, qd_graph_info_ex(g, info, n) the rest; 101: qd_decoder_postproc_kernel
+extern "C" int qd_version(void) { return 104; }      // 104: qd_circuit_* and qd_sample_circuit; 103: qd_decoder_post_head_start; 102: qd_graph_info fills 10 entries again, qd_graph_info_ex(g, info, n) the rest; 101: qd_decoder_postproc_kernel
 extern "C" const char *qd_last_error(void) { return g_err; }
 extern "C" int qd_device_count(void)
 {
@@ -1683,5 +1683,138 @@ extern "C" int qd_sample_dem(const qd_spmat *Ht, const qd_spmat *Lt, const doubl
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     (void)hipFree(d_thr);
     if (e != hipSuccess) return fail(QD_EHIP, "sampler: %s", hipGetErrorString(e));
+    return QD_OK;
+}
+
+// ---- circuit-level sampler (frame_sampler.hip): the program comes from quits_amd/frame.py; everything the kernel indexes with is
+// checked here once, so the kernel trusts the program.
+hipError_t qd_launch_frame_sample(const FrameDev &c, uint64_t seed, int64_t shot0, int64_t B, uint8_t *det, int64_t det_stride,
+                                  uint8_t *obs, int64_t obs_stride, hipStream_t s);
+
+struct qd_circuit {
+    int device = 0;
+    FrameDev d{};
+    int nq = 0, nmeas = 0, ndet = 0, nobs = 0;
+    int64_t nsites = 0;
+    DevAllocs mem;
+};
+
+static int frame_check_program(const int32_t *p, int64_t len, int nq, int nmeas, int ndet, int nobs, int nthr, int ring, int64_t *nsites)
+{
+    std::vector<int64_t> seen((size_t)nq, -1);     // qubit -> pc of the last gate part that used it
+    int64_t pc = 0, sites = 0, meas = 0;
+    int next_det = 0;
+    auto bad = [&](const char *what) { return fail(QD_EINVAL, "circuit program word %lld: %s", (long long)pc, what); };
+    while (pc < len) {
+        if (len - pc < 2) return bad("truncated instruction");
+        const int op = p[pc], n = p[pc + 1];
+        if (op < 0 || op >= QD_FOP_COUNT) return bad("unknown opcode");
+        if (n < 0) return bad("negative count");
+        int64_t width;
+        switch (op) {
+        case QD_FOP_R: case QD_FOP_H: width = 2 + (int64_t)n; break;
+        case QD_FOP_CX: case QD_FOP_M: case QD_FOP_MX: case QD_FOP_MR: width = 2 + 2 * (int64_t)n; break;
+        case QD_FOP_XERR: case QD_FOP_ZERR: case QD_FOP_DEP1: width = 4 + (int64_t)n; break;
+        case QD_FOP_DEP2: width = 4 + 2 * (int64_t)n; break;
+        case QD_FOP_FLUSH: width = 3; break;
+        default: width = 3 + (int64_t)n; break;                 // DET, OBS
+        }
+        if (width > len - pc) return bad("instruction runs past the end of the program");
+        const int32_t *a = p + pc + 2;
+        if (op <= QD_FOP_MR) {
+            const int per = (op == QD_FOP_R || op == QD_FOP_H) ? 1 : 2;
+            for (int i = 0; i < n; ++i)
+                for (int k = 0; k < (op == QD_FOP_CX ? 2 : 1); ++k) {
+                    const int q = a[per * i + k];
+                    if (q < 0 || q >= nq) return bad("qubit out of range");
+                    if (seen[q] == pc) return bad("a qubit repeats inside one gate part");
+                    seen[q] = pc;
+                }
+            if (op >= QD_FOP_M) {
+                for (int i = 0; i < n; ++i)
+                    if (a[2 * i + 1] < 0 || a[2 * i + 1] >= ring) return bad("ring slot out of range");
+                meas += n;
+            }
+        } else if (op <= QD_FOP_DEP2) {
+            if (a[0] < 0 || a[0] >= nthr) return bad("threshold index out of range");
+            if (a[1] < 0 || (a[1] & 3)) return bad("first site must be a non-negative multiple of 4");
+            const int nt = op == QD_FOP_DEP2 ? 2 * n : n;
+            for (int i = 0; i < nt; ++i)
+                if (a[2 + i] < 0 || a[2 + i] >= nq) return bad("qubit out of range");
+            sites += n;
+        } else if (op == QD_FOP_FLUSH) {
+            if (n < 1 || n > QD_WAVE || a[0] < 0 || (a[0] & (QD_WAVE - 1)) || a[0] + n > ndet) return bad("bad detector block");
+            if (a[0] + n != next_det) return bad("a flush must close the detector block just produced");
+        } else {
+            if (op == QD_FOP_DET) {
+                if (a[0] != next_det) return bad("detectors must come in order");
+                ++next_det;
+            } else if (a[0] < 0 || a[0] >= nobs) return bad("observable out of range");
+            for (int i = 0; i < n; ++i)
+                if (a[1 + i] < 0 || a[1 + i] >= ring) return bad("ring slot out of range");
+        }
+        pc += width;
+    }
+    if (meas != nmeas) return fail(QD_EINVAL, "program measures %lld times, nmeas = %d", (long long)meas, nmeas);
+    if (next_det != ndet) return fail(QD_EINVAL, "program defines %d detectors, ndet = %d", next_det, ndet);
+    *nsites = sites;
+    return QD_OK;
+}
+
+extern "C" int qd_circuit_create(const int32_t *program, int64_t program_len, int32_t nq, int32_t nmeas, int32_t ndet, int32_t nobs,
+                                 const uint32_t *thresholds, int32_t nthr, int32_t max_lookback, int32_t device, qd_circuit **out)
+{
+    if (!out) return fail(QD_EINVAL, "out is null");
+    *out = nullptr;
+    if (!program || program_len < 0 || program_len > INT32_MAX) return fail(QD_EINVAL, "bad program");
+    if (nq < 0 || nmeas < 0 || ndet < 0 || nobs < 0 || nthr < 0 || max_lookback < 1) return fail(QD_EINVAL, "bad sizes");
+    if (nthr > 0 && !thresholds) return fail(QD_EINVAL, "null thresholds");
+    const int64_t lds = 8 * (2 * (int64_t)nq + max_lookback + nobs);
+    if (lds > QD_FRAME_LDS_MAX)
+        return fail(QD_ECAPACITY, "circuit needs %lld B of LDS per wavefront (%d qubits, %d-measurement ring, %d observables), budget %d B",
+                    (long long)lds, nq, max_lookback, nobs, QD_FRAME_LDS_MAX);
+    int64_t nsites = 0;
+    int rc = frame_check_program(program, program_len, nq, nmeas, ndet, nobs, nthr, max_lookback, &nsites);
+    if (rc) return rc;
+    if (hipSetDevice(device) != hipSuccess) return fail(QD_EHIP, "hipSetDevice(%d) failed", device);
+    qd_circuit *c = new qd_circuit();
+    c->device = device;
+    std::vector<int32_t> prog(program, program + program_len);
+    std::vector<uint32_t> thr(thresholds, thresholds + nthr);
+    if (c->mem.upload(prog, &c->d.prog) || c->mem.upload(thr, &c->d.thr)) {
+        c->mem.release(); delete c; return fail(QD_EHIP, "device allocation/upload failed");
+    }
+    c->d.prog_len = (int)program_len; c->d.nq = nq; c->d.ring = max_lookback; c->d.nobs = nobs; c->d.lds_bytes = (int)lds;
+    c->nq = nq; c->nmeas = nmeas; c->ndet = ndet; c->nobs = nobs; c->nsites = nsites;
+    *out = c;
+    return QD_OK;
+}
+
+extern "C" void qd_circuit_destroy(qd_circuit *c)
+{
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    c->mem.release();
+    delete c;
+}
+
+extern "C" int qd_circuit_info(const qd_circuit *c, int64_t *info)
+{
+    if (!c || !info) return fail(QD_EINVAL, "null argument");
+    const int64_t v[8] = {c->nq, c->nsites, c->d.lds_bytes, c->nmeas, c->ndet, c->nobs, c->d.ring, c->d.prog_len};
+    for (int i = 0; i < 8; ++i) info[i] = v[i];
+    return QD_OK;
+}
+
+extern "C" int qd_sample_circuit(const qd_circuit *c, uint64_t seed, int64_t shot0, int64_t B, uint8_t *d_det, int64_t det_stride,
+                                 uint8_t *d_obs, int64_t obs_stride, void *stream)
+{
+    if (!c) return fail(QD_EINVAL, "null circuit");
+    if (B < 0 || shot0 < 0) return fail(QD_EINVAL, "negative shot count or shot0");
+    if (B > (int64_t)QD_WAVE * INT32_MAX) return fail(QD_EINVAL, "too many shots in one call");
+    if ((c->ndet > 0 && !d_det) || (c->nobs > 0 && !d_obs)) return fail(QD_EINVAL, "null output");
+    if (det_stride < c->ndet || obs_stride < c->nobs) return fail(QD_EINVAL, "output strides too small");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(qd_launch_frame_sample(c->d, seed, shot0, B, d_det, det_stride, d_obs, obs_stride, reinterpret_cast<hipStream_t>(stream)));
     return QD_OK;
 }

@@ -294,3 +294,29 @@ struct SpmatDev {
     const uint32_t *colmask;    // [ncols][mask_words] the rows of each column as a bit mask (null when nrows > 512)
     int mask_words;
 };
+
+// Philox4x32-10 (Salmon et al., SC'11): the counter-based generator of both samplers, qd_sample_dem (gf2_kernels.hip) and
+// qd_sample_circuit (frame_sampler.hip).  CPU restatement: philox4x32_10 in oracle/qd_oracle.c.
+__device__ __forceinline__ void qd_philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
+                                                 uint32_t k1, uint32_t out[4])
+{
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
+        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+// Circuit program of the frame sampler (frame_sampler.hip); opcodes and layout as quits_amd/frame.py writes them.
+enum QdFrameOp { QD_FOP_R = 0, QD_FOP_H, QD_FOP_CX, QD_FOP_M, QD_FOP_MX, QD_FOP_MR, QD_FOP_XERR, QD_FOP_ZERR, QD_FOP_DEP1, QD_FOP_DEP2,
+                 QD_FOP_DET, QD_FOP_FLUSH, QD_FOP_OBS, QD_FOP_COUNT };
+#define QD_FRAME_LDS_MAX (64 * 1024)   // LDS of one wavefront (64 shots): 2 x nq frame words + ring words + observable words, 8 B each
+struct FrameDev {
+    const int32_t *prog;
+    const uint32_t *thr;
+    int prog_len, nq, ring, nobs, lds_bytes;
+};

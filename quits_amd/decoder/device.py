@@ -250,5 +250,55 @@ class DemSampler:
         return det, obs
 
 
+class CircuitSampler:
+    """Device-side circuit-level sampler (qd_sample_circuit): a Pauli-frame simulation of the circuit, what the reference gets from
+    `circuit.compile_detector_sampler().sample(shots, separate_observables=True)` (simulation.py:8-28).  Same surface as DemSampler.
+    `circuit`: circuit text, quits_amd.dem.Circuit, stim.Circuit, or a quits_amd.frame.CompiledCircuit.  The semantics, the random
+    stream and its assumption (deterministic detectors) are in quits_amd/frame.py."""
+
+    def __init__(self, circuit, device: Optional[int] = None):
+        from ..frame import CompiledCircuit, compile_circuit
+        L = _lib.require_gpu()
+        torch = _torch()
+        self.device = torch.cuda.current_device() if device is None else int(device)
+        cc = circuit if isinstance(circuit, CompiledCircuit) else compile_circuit(circuit)
+        prog = np.ascontiguousarray(cc.program, dtype=np.int32)
+        thr = np.ascontiguousarray(cc.thresholds, dtype=np.uint32)
+        h = C.c_void_p()
+        rc = L.qd_circuit_create(prog.ctypes.data_as(C.c_void_p), len(prog), cc.nq, cc.nmeas, cc.ndet, cc.nobs,
+                                 thr.ctypes.data_as(C.c_void_p), len(thr), cc.ring, self.device, C.byref(h))
+        if rc == -4:
+            raise NotImplementedError(L.qd_last_error().decode())
+        _lib.check(rc)
+        self._h = h
+        self._L = L
+        self.compiled = cc
+        self.m = cc.ndet
+        self.nobs = cc.nobs
+
+    def info(self) -> dict:
+        arr = (C.c_int64 * 8)()
+        _lib.check(self._L.qd_circuit_info(self._h, arr))
+        keys = ("qubits", "sites", "lds_bytes", "measurements", "detectors", "observables", "ring", "program_words")
+        return dict(zip(keys, [int(x) for x in arr]))
+
+    def sample(self, shots: int, seed: int, shot0: int = 0):
+        """(det uint8 [shots, m], obs uint8 [shots, nobs]) on the current device, shots shot0 .. shot0 + shots - 1."""
+        torch = _torch()
+        det = torch.empty((shots, self.m), dtype=torch.uint8, device="cuda")
+        obs = torch.empty((shots, self.nobs), dtype=torch.uint8, device="cuda")
+        _lib.check(self._L.qd_sample_circuit(self._h, C.c_uint64(int(seed) & (2 ** 64 - 1)), int(shot0), int(shots), _ptr(det),
+                                             det.stride(0), _ptr(obs), obs.stride(0), _stream_ptr()))
+        return det, obs
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            try:
+                self._L.qd_circuit_destroy(self._h)
+            except Exception:
+                pass
+            self._h = None
+
+
 def _norm(x):
     return x.lower() if isinstance(x, str) else x

@@ -2,6 +2,7 @@
 
   get_codecap_pL       <- simulation.py:31-61   code-capacity logical error rate of a decoder plug-in
   get_stim_mem_result  <- simulation.py:8-28    detector / observable samples of a memory circuit
+  get_circuit_mem_result                        the same samples from the circuit itself on the device (Pauli-frame simulation)
 
 `get_codecap_pL` keeps the reference's signature and its random stream (`np.random.seed(seed)` followed by one
 `np.random.binomial(1, p, n)` per trial), so a given seed produces the same noise vectors as the reference.  With a plug-in
@@ -33,6 +34,18 @@ def get_stim_mem_result(circuit, num_trials, seed=-1):
     if seed < 0:
         seed = int(np.random.SeedSequence().entropy % (1 << 62))
     det, obs = DemSampler(H, L, priors).sample(int(num_trials), seed=int(seed))
+    return det.cpu().numpy().astype(bool), obs.cpu().numpy().astype(bool)
+
+
+def get_circuit_mem_result(circuit, num_trials, seed=-1):
+    """Detector and observable samples of a memory circuit, drawn on the device by simulating the circuit itself
+    (quits_amd.decoder.device.CircuitSampler, Pauli frames; quits_amd/frame.py states the semantics): the distribution the
+    reference's `compile_detector_sampler().sample(..., separate_observables=True)` draws from, without Stim.  `circuit` is circuit
+    text, a `quits_amd.dem.Circuit` or a `stim.Circuit`.  Returns numpy bool (det [num_trials, ndet], obs [num_trials, nobs])."""
+    from .decoder.device import CircuitSampler
+    if seed < 0:
+        seed = int(np.random.SeedSequence().entropy % (1 << 62))
+    det, obs = CircuitSampler(circuit).sample(int(num_trials), seed=int(seed))
     return det.cpu().numpy().astype(bool), obs.cpu().numpy().astype(bool)
 
 
