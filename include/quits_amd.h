@@ -63,6 +63,19 @@ typedef struct qd_circuit qd_circuit;   /* compiled circuit program of the frame
  * arithmetic: float rounding in every sum).  Validation aid; see qd_decoder_info. */
 #define QD_FLAG_RAW_LLR 2
 
+/* Validation switches: environment variables that make a graph (G: read by qd_graph_create) or a decoder (D: read by qd_decoder_create)
+ * take an alternative that the tests compare bit for bit against the default.  None changes a result and none is needed in normal
+ * use; an object keeps what it read for its whole life, and nothing on the decode path reads the environment.
+ *   QD_NO_SCATTER              D  flooding min-sum in the gather kernel (bp_kernels.hip) where a scatter kernel would take the window
+ *   QD_SCATTER_M2_LIMIT=<u>    D  lower the scatter kernels' exactness bound to u grid units: shots take the gather kernel's recheck pass
+ *   QD_SCATTER_CPL1            G  one check per lane (bp_scatter.hip) where the default is two per lane on half the lanes
+ *   QD_SCATTER_WIDE_T704       G  several-checks-per-lane kernel (bp_scatter_wide.hip) on 704 lanes x 2 checks instead of 512 x 3
+ *   QD_SCATTER_NATURAL_ROUNDS  G  ... its wavefronts take the slot-waves in natural order (no balancing of their rounds)
+ *   QD_SCATTER_BANKS_BY_SLOT   G  the scatter accumulators' banks = the degree-sorted bit slots mod 32 (no balancing)
+ *   QD_SCATTER_WALK_GREEDY     G  the scatter kernels' walk without matching: every check takes its least busy bank
+ *   QD_OSDCS_OLD=1             D  higher-order OSD by row (osd_kernels.hip) instead of the panel kernel (osd_cs.hip)
+ *   QD_GEN_STAGES="3,6" / =0   D  iteration bounds between the launches of the serial schedule (one-message-per-edge kernel) / one launch */
+
 /* Keyword arguments the reference hands to BpOsdDecoder (decoder/bposd.py:38-49,74-83). */
 typedef struct qd_params {
     int32_t bp_method;          /* QD_BP_*        ; MINIMUM_SUM + PARALLEL runs in the compressed LDS kernel,        */
@@ -123,9 +136,10 @@ int qd_decoder_postproc_kernel(const qd_decoder *d);
 /* Pre-size the device workspace for batches of up to max_batch shots (otherwise grown on demand, which
  * synchronises). */
 int qd_decoder_reserve(qd_decoder *d, int64_t max_batch);
-/* Cap the message workspace of the one-message-per-edge BP kernel (bytes; default 48 GB or QD_GENERAL_WS_GB).  Larger
- * batches are decoded in equal chunks that fit.  A sliding-window plan holds one decoder per window: the host divides
- * the budget among them.  No reference counterpart (memory management). */
+/* Cap the message workspace of the one-message-per-edge BP kernel (bytes; default 48 GB).  Larger batches are decoded in
+ * equal chunks that fit.  A sliding-window plan holds one decoder per window: the host divides its budget among them (the Python
+ * driver's QD_GENERAL_WS_GB: default 96 GB for a plan of several decoders; a plan of one keeps 48 GB unless it is set).  No reference
+ * counterpart (memory management). */
 int qd_decoder_set_workspace_limit(qd_decoder *d, int64_t bytes);
 /* Hand the device workspace back (posteriors, fail lists, message planes, elimination scratch); the decoder stays usable and
  * sizes it again at the next decode.  The host keeps sliding-window plans between calls (the reference is called once per

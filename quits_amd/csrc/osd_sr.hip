@@ -37,7 +37,6 @@
 // 66.4 ms, 128 registers 4.40 / 72 ms (profiles/r04_osd_sr_register_budget_ab.txt); tests/test_api.py holds every instantiation
 // to ScratchSize 0.
 #include "osd_shared.h"
-#include <cstdlib>
 #include <algorithm>
 
 #ifndef QD_SR_TIER_GUESS
@@ -415,7 +414,6 @@ hipError_t qd_launch_osd0_sr(const OsdGraphDev &g, const BpGraphDev &bg, const D
     r.o_tb = o[0]; r.o_rowpiv = o[1]; r.o_prow = o[2]; r.o_pcol = o[3]; r.o_ppos = o[4]; r.o_nz = o[5]; r.o_cand = o[6]; r.o_stq = o[7];
     r.o_stsp = o[8]; r.o_bcols = o[9]; r.o_red = o[10]; r.o_out = o[11]; r.o_order = o[12];
     r.tier_first = QD_OSD_TIER_FIRST;
-    if (const char *ev = std::getenv("QD_SR_TIER_FIRST")) { const int v = std::atoi(ev); if (v >= 64 && v <= QD_OSD_TIER) r.tier_first = v; }
     r.csc_ell = g.csc_ell; r.bit_orig = bg.bit_orig;
     r.det = a.det; r.upd = a.upd; r.det_stride = a.det_stride; r.det_offset = a.det_offset; r.upd_stride = a.upd_stride;
     r.llr_ws = a.llr_ws; r.fail_list = a.fail_list; r.fail_count = a.fail_count; r.q_spill = a.q_spill_sr;

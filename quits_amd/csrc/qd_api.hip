@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <numeric>
 #include <vector>
 
@@ -35,7 +36,6 @@ hipError_t qd_launch_lsd0(const GenGraphDev &gg, const BpGraphDev &bg, const Dec
                           int lsd_w, int lsd_order, const uint32_t *wfix, hipStream_t s);
 size_t qd_lsd_ws_bytes(int m, int n, int blocks, int lsd_w);
 int qd_lsd_lds_bytes(int m, int n, int out_words);
-int qd_lsd_plane_rows(int m);
 hipError_t qd_launch_stage_llr(const float *llr_in, int n, int n_pad, const uint32_t *bit_orig, int64_t B, float *llr_ws,
                                int32_t *fail_list, int32_t *fail_count, int32_t *status, hipStream_t s);
 hipError_t qd_launch_spmv(const SpmatDev &A, const uint32_t *err, int64_t err_stride, int64_t B, uint8_t *out,
@@ -83,6 +83,44 @@ struct DevAllocs {
     }
 };
 
+// The validation switches of include/quits_amd.h: each selects an alternative that the tests compare bit for bit against the default.
+// Read here alone, when a graph or a decoder is created; nothing on the decode path reads the environment.
+struct Switches {
+    bool no_scatter, scatter_cpl1, scatter_wide_t704, scatter_natural_rounds, scatter_banks_by_slot, scatter_walk_greedy, osdcs_old;
+    float scatter_m2_limit;             // +inf: not set
+    std::vector<int> gen_stages;        // iteration bounds between the launches of the serial schedule in the one-message-per-edge kernel
+};
+
+static Switches read_switches()
+{
+    auto env = [](const char *name) { return std::getenv(name); };
+    Switches w{};
+    w.no_scatter = env("QD_NO_SCATTER") != nullptr;
+    w.scatter_cpl1 = env("QD_SCATTER_CPL1") != nullptr;
+    w.scatter_wide_t704 = env("QD_SCATTER_WIDE_T704") != nullptr;
+    w.scatter_natural_rounds = env("QD_SCATTER_NATURAL_ROUNDS") != nullptr;
+    w.scatter_banks_by_slot = env("QD_SCATTER_BANKS_BY_SLOT") != nullptr;
+    w.scatter_walk_greedy = env("QD_SCATTER_WALK_GREEDY") != nullptr;
+    const char *ev = env("QD_OSDCS_OLD");
+    w.osdcs_old = ev && std::atoi(ev) == 1;
+    ev = env("QD_SCATTER_M2_LIMIT");
+    w.scatter_m2_limit = ev ? (float)std::atof(ev) : INFINITY;
+    // after iterations 3, 6, 10, 14, 20, ... (x ~1.4); QD_GEN_STAGES="3,6" sets them, QD_GEN_STAGES=0 = one launch
+    // (max_iter 10: "3,6" 50.5 ms, "3,5,7" 51.4, "4" 51.4, one launch 56.0: profiles/r06_k1g_staged_ab.txt)
+    w.gen_stages = {3, 6, 10, 14, 20, 28, 40, 56, 80, 112};
+    if ((ev = env("QD_GEN_STAGES"))) {
+        w.gen_stages.clear();
+        for (const char *q = ev; *q;) {
+            char *end = nullptr;
+            const long v = std::strtol(q, &end, 10);
+            if (end == q) break;
+            if (v > 0) w.gen_stages.push_back((int)v);
+            q = *end ? end + 1 : end;
+        }
+    }
+    return w;
+}
+
 struct qd_graph {
     int device = 0;
     int m = 0, n = 0, nnz = 0, max_rdeg = 0, max_cdeg = 0, rank = -1;
@@ -97,11 +135,24 @@ struct qd_graph {
     std::vector<uint32_t> h_bit_orig;  // bit slot -> fault
     std::vector<int32_t> h_sc_slot;    // fault -> accumulator slot of the scatter kernels (empty: they are not used)
     long long sc_walk_cycles = 0, sc_walk_ideal = 0;   // modelled LDS cycles of one pass of the scatter kernels' walk, and without any bank conflict
+    ~qd_graph() { mem.release(); }
+};
+
+// The BP kernel(s) of a decoder's stage 1, chosen once by qd_decoder_create
+enum BpPath {
+    BP_LDS_EDGE,        // flooding product-sum, one message per edge, every message in LDS (qd_launch_bp_ps_lds)
+    BP_HBM_EDGE,        // one message per edge in an HBM workspace (bp_general.hip): every other method / schedule, and QD_FLAG_EDGE_MESSAGES
+    BP_SCATTER_WIDE,    // flooding min-sum on the LLR grid, several checks per lane (bp_scatter_wide.hip); recheck + coarse grid: gather kernel
+    BP_SCATTER,         // ... one check per lane (bp_scatter.hip); recheck + coarse grid: gather kernel
+    BP_GATHER_GRID,     // ... the gather kernel (bp_kernels.hip) on the fine grid, then on the coarse grid
+    BP_GATHER_RAW,      // flooding min-sum on float LLRs off the grid (ms_scaling_factor != 1, QD_FLAG_RAW_LLR): the gather kernel
 };
 
 struct qd_decoder {
     const qd_graph *g = nullptr;
     qd_params prm{};
+    BpPath bp = BP_GATHER_RAW;
+    int post = QD_POST_NONE;    // QD_POST_*: the post-processor, chosen once by qd_decoder_create
     int64_t cap = 0;
     int osd_blocks = 0;
     float *llr_ws = nullptr;
@@ -109,7 +160,8 @@ struct qd_decoder {
     // Two sets of counters (fail / hard / redo / recheck counts), used by alternate calls.  A call's BP stage needs its set at zero; the set is zeroed by
     // the post-processing stage of the call BEFORE, on ITS stream (that set was last used two calls ago) -- not by fills at the head of the BP stage: in the
     // pipelined driver those fills sat between two BP kernels and each chunk lost ~2 ms there (a 4-byte fill launched the moment the other stream's OSD
-    // kernel starts takes 1.9-2.1 ms, profiles/r06_bp_stream_bubble.txt).  set_clean: the set has been zeroed by an operation already queued.
+    // kernel starts takes 1.9-2.1 ms, profiles/r06_bp_stream_bubble.txt).  set_clean: the set has been zeroed by an operation already queued.  After
+    // qd_decoder_reserve neither set is: the first call on each zeroes it at its head, on its own stream.
     int32_t *ctr_base = nullptr;
     int cset = 0;
     bool set_clean[2] = {false, false};
@@ -126,28 +178,23 @@ struct qd_decoder {
     uint64_t *q_spill_sr = nullptr;
     int32_t *hard_list = nullptr, *hard_list2 = nullptr;
     int osd_blocks_fast = 0;
-    int osd_blocks_sr = 0;      // > 0: OSD-0 runs in qd_osd0_sr_kernel (osd_sr.hip), the mirrored kernel only takes the shots it hands over
-    int osd_blocks_cs = 0;      // > 0: OSD-CS / OSD-E run in qd_osdcs_kernel (osd_cs.hip)
-    int cs_off[16] = {0}, cs_variant = 0, cs_lds = 0;
-    uint64_t *cs_ws = nullptr;  // [osd_blocks_cs][qd_osdcs_ws_words] Q columns for the candidate sweep
+    int post_blocks = 0;        // workgroups of the post-processor's own kernel: qd_osd0_sr_kernel (osd_sr.hip), qd_osdcs_kernel or qd_lsd0_kernel
+    int cs_off[16] = {0}, cs_variant = 0, cs_lds = 0, cs_per_cu = 0;
+    uint64_t *cs_ws = nullptr;  // [post_blocks][qd_osdcs_ws_words] Q columns for the candidate sweep
     int osd_w = 0;
-    int general = 0;            // 1: the one-message-per-edge kernel (bp_general.hip) runs BP
-    int lds_edge = 0;           // ... its LDS-resident form (flooding product-sum on a window whose messages fit LDS): no HBM message workspace
-    int lsd = 0;                // 1: BP-LSD post-processing (lsd_kernels.hip) instead of OSD
-    int lsd_blocks = 0;
     int lsd_w = 0;              // higher-order LSD: 0 = LSD-0, 1 = combination sweep, 2 = exhaustive (order = prm.osd_order)
-    uint64_t *lsd_ws = nullptr; // [lsd_blocks][mw][m_pad] Q planes, then the work counter
+    uint64_t *lsd_ws = nullptr; // [post_blocks][mw][m_pad] Q planes, then the work counter
     int64_t gen_ws_limit = 0;   // bytes; 0 = default
     GenWs gws{};
     GenStagePlan gsp{};         // serial schedule: the launches' iteration bounds, the second workspace, the survivor lists (nbounds = 0: one launch)
+    int gen_bounds[QD_GEN_MAX_STAGES] = {0}, gen_nbounds = 0;   // the bounds every reserve starts gsp from
     // ---- LLR grid (flooding min-sum, ms_scaling 1): decoder-owned prior arrays on the fine and the coarse grid
     int grid_k = -1, grid_kc = -1, grid_floor = 0;   // grid_floor: the fine grid is the 2^-10 floor, not the rule's: any number of shots may need the redo pass
     BpGraphDev bp_fine{}, bp_coarse{};         // copies of g->bp with their own bit_rec
     const float *llr0_q = nullptr;             // fault-order LLRs for the one-message-per-edge kernel (fine grid)
     int32_t *redo_list = nullptr;
     int redo_cap = 0;
-    int scatter = 0;                           // 1: the fine-grid pass runs in qd_bp_scatter_kernel
-    const int32_t *prior_g = nullptr;          // [n_pad] fine-grid channel LLRs of the bit slots in grid units
+    const int32_t *prior_g = nullptr;          // [n_pad] fine-grid channel LLRs of the bit slots in grid units (scatter kernels)
     float m2_limit = 0.f;
     int32_t *recheck_list = nullptr;           // shots the scatter kernel's bound could not certify
     int recheck_cap = 0;
@@ -182,13 +229,14 @@ static inline int pad64(int x) { return (x + 63) & ~63; }
 //                  takes its edge on the least busy bank; steps beyond a check's degree point at a trash slot on a bank nobody uses.
 // Headline window (1008 x 9504): 1932 modelled cycles per pass with the round-3 greedy walk over the degree-sorted slots, 1109 here,
 // 1052 without any conflict (WindowGraph.info(): scatter_walk_cycles / _ideal).
+// by_slot (QD_SCATTER_BANKS_BY_SLOT): the round-3 assignment, the starting point alone
 static void scatter_banks(int m, int n, const int32_t *row_ptr, const int32_t *col_idx, const std::vector<int> &chk_orig,
-                          const std::vector<int> &bit_slot_of, std::vector<int> &bank)
+                          const std::vector<int> &bit_slot_of, bool by_slot, std::vector<int> &bank)
 {
     const int nh = (m + 31) / 32;
     bank.resize(n);
     for (int j = 0; j < n; ++j) bank[j] = bit_slot_of[j] & 31;
-    if (std::getenv("QD_SCATTER_BANKS_BY_SLOT")) return;            // A/B: the round-3 assignment
+    if (by_slot) return;
     // fault -> (group, edges from that group)
     std::vector<std::vector<std::pair<int, int>>> fh(n);
     std::vector<int> load((size_t)nh * 32, 0), cnt(32, 0);
@@ -229,11 +277,11 @@ static void scatter_banks(int m, int n, const int32_t *row_ptr, const int32_t *c
 }
 
 // put(s, k, e, trash_bank): check slot s takes CSR edge e at step k (e < 0: a step beyond its degree, reading / adding 0 to the trash slot of trash_bank)
+// greedy_only (QD_SCATTER_WALK_GREEDY): no matching, every check takes its least busy bank
 template <class Put>
 static void scatter_walk(int m, const int32_t *row_ptr, const int32_t *col_idx, const std::vector<int> &chk_orig, const std::vector<int> &bank,
-                         Put put, long long *cycles, long long *ideal)
+                         bool greedy_only, Put put, long long *cycles, long long *ideal)
 {
-    const bool greedy_only = std::getenv("QD_SCATTER_WALK_GREEDY") != nullptr;      // A/B: no matching, every check takes its least busy bank
     std::vector<std::vector<int>> rem(32);
     for (int w0 = 0; w0 < m; w0 += 64) {
         int trip = 0;
@@ -327,17 +375,28 @@ extern "C" int qd_device_count(void)
     return n;
 }
 
-extern "C" int qd_graph_create(int32_t m, int32_t n, const int32_t *row_ptr, const int32_t *col_idx,
-                               const double *priors, int32_t device, qd_graph **out)
+// ---- qd_graph_create: host_graph validates the window and derives what the builders share, then one builder per device view, in this
+// order: build_bp (slot orders and BpGraphDev), build_gen (GenGraphDev), build_scatter (ScatGraphDev), build_osd (OsdGraphDev).
+struct HostGraph {
+    int m = 0, n = 0, nnz = 0, max_rdeg = 0, max_cdeg = 0, min_rdeg = 0, m_pad = 0, n_pad = 0, max_rdeg_pad = 0;
+    const int32_t *row_ptr = nullptr, *col_idx = nullptr;
+    const double *priors = nullptr;
+    std::vector<int> rdeg, cdeg;
+    std::vector<double> llr0;                                        // log((1-p)/p), fault order
+    std::vector<int32_t> cp, ri, pos;                                // CSC with the edge's position inside its row
+    std::vector<int> chk_orig, chk_slot_of, bit_orig, bit_slot_of;   // slots: degree-descending, stable (build_bp)
+    std::vector<uint8_t> chk_deg;                                    // [m_pad] degree of the check slot (build_bp)
+};
+
+static int host_graph(int32_t m, int32_t n, const int32_t *row_ptr, const int32_t *col_idx, const double *priors, HostGraph &h)
 {
-    if (!out) return fail(QD_EINVAL, "out is null");
-    *out = nullptr;
     if (m <= 0 || n <= 0 || !row_ptr || !col_idx || !priors) return fail(QD_EINVAL, "empty or null graph");
     if (m > 32767) return fail(QD_ECAPACITY, "m = %d detectors per window exceeds 32767", m);
     if (n > 65000) return fail(QD_ECAPACITY, "n = %d faults per window exceeds 65000", n);
     const int nnz = row_ptr[m];
     if (row_ptr[0] != 0 || nnz < 0) return fail(QD_EINVAL, "bad row_ptr");
-    std::vector<int> rdeg(m), cdeg(n, 0);
+    std::vector<int> &rdeg = h.rdeg, &cdeg = h.cdeg;
+    rdeg.assign(m, 0); cdeg.assign(n, 0);
     for (int i = 0; i < m; ++i) {
         rdeg[i] = row_ptr[i + 1] - row_ptr[i];
         if (rdeg[i] < 0) return fail(QD_EINVAL, "row_ptr not monotone");
@@ -349,19 +408,60 @@ extern "C" int qd_graph_create(int32_t m, int32_t n, const int32_t *row_ptr, con
     }
     for (int j = 0; j < n; ++j)
         if (!(priors[j] > 0.0 && priors[j] < 1.0)) return fail(QD_EINVAL, "prior %d = %g outside (0,1)", j, priors[j]);
+    h.llr0.resize(n);
+    for (int j = 0; j < n; ++j) h.llr0[j] = std::log((1.0 - priors[j]) / priors[j]);
     const int max_rdeg = *std::max_element(rdeg.begin(), rdeg.end());
     const int max_cdeg = *std::max_element(cdeg.begin(), cdeg.end());
     if (max_rdeg > QD_MAX_ROW_DEG || max_rdeg < 1)
         return fail(QD_ECAPACITY, "row weight %d outside 1..%d", max_rdeg, QD_MAX_ROW_DEG);
     if (max_cdeg > QD_MAX_COL_DEG || max_cdeg < 1)
         return fail(QD_ECAPACITY, "column weight %d outside 1..%d", max_cdeg, QD_MAX_COL_DEG);
+    h.m = m; h.n = n; h.nnz = nnz; h.max_rdeg = max_rdeg; h.max_cdeg = max_cdeg;
+    h.min_rdeg = *std::min_element(rdeg.begin(), rdeg.end());
+    h.m_pad = pad64(m); h.n_pad = pad64(n); h.max_rdeg_pad = (max_rdeg + 3) & ~3;
+    h.row_ptr = row_ptr; h.col_idx = col_idx; h.priors = priors;
+    if ((h.m_pad + 1) * 16 > 65535) return fail(QD_ECAPACITY, "m = %d detectors per window: check-state offsets exceed 16 bits", m);
+    if (h.n_pad + 1 > 65535) return fail(QD_ECAPACITY, "n = %d faults per window: fault slots exceed 16 bits", n);
+    // CSC with the edge's position inside its row
+    h.cp.assign(n + 1, 0); h.ri.resize(nnz); h.pos.resize(nnz);
+    for (int j = 0; j < n; ++j) h.cp[j + 1] = h.cp[j] + cdeg[j];
+    std::vector<int> fill(n, 0);
+    for (int i = 0; i < m; ++i)
+        for (int e = row_ptr[i]; e < row_ptr[i + 1]; ++e) {
+            const int j = col_idx[e], dst = h.cp[j] + fill[j]++;
+            h.ri[dst] = i; h.pos[dst] = e - row_ptr[i];
+        }
+    return QD_OK;
+}
 
-    qd_graph *g = new qd_graph();
-    g->device = device; g->m = m; g->n = n; g->nnz = nnz; g->max_rdeg = max_rdeg; g->max_cdeg = max_cdeg;
-    if (hipSetDevice(device) != hipSuccess) { delete g; return fail(QD_EHIP, "hipSetDevice(%d) failed", device); }
+static int bp_block_threads(int m, int n) { return std::max(m, (n + 9) / 10) <= 256 ? 256 : (std::max(m, (n + 9) / 10) <= 512 ? 512 : 1024); }
 
+static int scatter_wide_threads(int m) { return pad64((m + 1) / 2) <= 704 ? 704 : 1024; }
+
+// The shape conditions of the scatter kernels (build_scatter checks their LDS fit).  1: one check per lane (bp_scatter.hip): every check
+// has a lane and rows hold 2..64 faults (two sign words; a row of one fault has no second minimum) -- also the windows of <= 256 checks,
+// 3.78 -> 3.00 ms per launch on the 108-check and 8.92 -> 7.73 ms on the 216-check windows of the W = 3 plans (profiles/r05_scatter_small_ab.txt).
+// 2: several checks per lane (bp_scatter_wide.hip): more checks than a workgroup has lanes, or rows of 65..96 faults -- the QLP windows
+// of BASELINE configs[4] (1326 checks of up to 78 faults on 704 lanes).  0: neither.
+static int scatter_form(const HostGraph &h)
+{
+    const int threads = bp_block_threads(h.m, h.n);
+    if (h.min_rdeg < 2) return 0;
+    if (h.m <= threads && h.max_rdeg_pad <= 64) return 1;
+    if (threads == 1024 && h.m <= 2 * scatter_wide_threads(h.m) && h.max_rdeg_pad <= 96 && (h.m > 1024 || h.max_rdeg_pad > 64)) return 2;
+    return 0;
+}
+
+// Slot orders and the gather kernel's view (BpGraphDev): LDS carve-up, the checks' walk over their edges, the fault records
+static int build_bp(qd_graph *g, HostGraph &h, bool walk_for_atomics)
+{
+    const int m = h.m, n = h.n, nnz = h.nnz, m_pad = h.m_pad, n_pad = h.n_pad, max_rdeg_pad = h.max_rdeg_pad;
+    const int32_t *row_ptr = h.row_ptr, *col_idx = h.col_idx;
+    const std::vector<int> &rdeg = h.rdeg, &cdeg = h.cdeg;
+    const std::vector<int32_t> &cp = h.cp, &ri = h.ri;
     // slots: degree-descending, stable
-    std::vector<int> chk_slot_of(m), chk_orig(m), bit_slot_of(n), bit_orig(n);
+    std::vector<int> &chk_slot_of = h.chk_slot_of, &chk_orig = h.chk_orig, &bit_slot_of = h.bit_slot_of, &bit_orig = h.bit_orig;
+    chk_slot_of.resize(m); chk_orig.resize(m); bit_slot_of.resize(n); bit_orig.resize(n);
     std::iota(chk_orig.begin(), chk_orig.end(), 0);
     std::stable_sort(chk_orig.begin(), chk_orig.end(), [&](int a, int b) { return rdeg[a] > rdeg[b]; });
     for (int s = 0; s < m; ++s) chk_slot_of[chk_orig[s]] = s;
@@ -369,57 +469,34 @@ extern "C" int qd_graph_create(int32_t m, int32_t n, const int32_t *row_ptr, con
     std::stable_sort(bit_orig.begin(), bit_orig.end(), [&](int a, int b) { return cdeg[a] > cdeg[b]; });
     for (int s = 0; s < n; ++s) bit_slot_of[bit_orig[s]] = s;
 
-    const int m_pad = pad64(m), n_pad = pad64(n);
-    const int max_rdeg_pad = (max_rdeg + 3) & ~3;
-    const int bp_threads_ = std::max(m, (n + 9) / 10) <= 256 ? 256 : (std::max(m, (n + 9) / 10) <= 512 ? 512 : 1024);
-    // the shape conditions of the scatter kernel (its LDS fit is checked where the layouts are known)
-    // (windows small enough for 256-thread workgroups: the one-check-per-lane kernel measured 4.0 vs 4.7 ms per launch on the W = 3
-    // windows of the [[72,12,6]] code, 9.0 vs 9.8 ms on those of the [[144,12,12]] code, profiles/r03z_scatter_other_configs.txt; on
-    // 128 lanes x 2 checks it is 3.98 -> 3.75 ms on the former (108 checks: taken) and 8.95 -> 9.45 ms on the latter (216 checks:
-    // stay with the gather kernel unless QD_SCATTER_SMALL is set), profiles/r03x_scatter_shapes_ab.txt)
-    const int min_rdeg_ = *std::min_element(rdeg.begin(), rdeg.end());
-    // (round 5: with the accumulators' banks balanced per group of 32 checks -- scatter_banks / scatter_walk -- the 128-lane shape is 8.92 -> 7.73 ms per
-    // launch on those 216-check windows and 3.78 -> 3.00 ms on the 108-check ones, so every window of <= 256 checks goes there; QD_NO_SCATTER_SMALL=1:
-    // the 129..256-check windows stay with the gather kernel, profiles/r05_scatter_small_ab.txt)
-    const bool scatter_narrow = m <= bp_threads_ && (bp_threads_ >= 512 || m <= 128 || !std::getenv("QD_NO_SCATTER_SMALL")) && max_rdeg_pad <= 64 && min_rdeg_ >= 2;
-    // ... and of its two-checks-per-lane form (bp_scatter_wide.hip): more checks than a workgroup has lanes, or rows of 65..96 faults --
-    // the QLP windows of BASELINE configs[4] (1326 checks of up to 78 faults on 704 lanes)
-    const int wide_threads_ = pad64((m + 1) / 2) <= 704 ? 704 : 1024;
-    const bool scatter_wide = !scatter_narrow && bp_threads_ == 1024 && m <= 2 * wide_threads_ && max_rdeg_pad <= 96 && min_rdeg_ >= 2 &&
-                              (m > 1024 || max_rdeg_pad > 64) && !std::getenv("QD_NO_SCATTER_WIDE");
-    const bool scatter_shape = scatter_narrow || scatter_wide;
-    const int dummy_bit = n_pad, dummy_chk = m_pad;        // one extra LDS slot each
-    if ((m_pad + 1) * 16 > 65535) {
-        delete g;
-        return fail(QD_ECAPACITY, "m = %d detectors per window: check-state offsets exceed 16 bits", m);
-    }
-    if (n_pad + 1 > 65535) {
-        delete g;
-        return fail(QD_ECAPACITY, "n = %d faults per window: fault slots exceed 16 bits", n);
-    }
-    const int sign_mode = max_rdeg_pad <= 32 ? 0 : (max_rdeg_pad <= 44 ? 1 : 2);    // mode 1: 15 spare bits of the state word hold signs 32..46
-    const int neg_words_ = (max_rdeg_pad + 31) / 32;
-    const int off_chk_ = 0, off_cneg_ = (m_pad + 4) * 16;
-    const int off_llr_ = off_cneg_ + (sign_mode == 2 ? align16((neg_words_ - 1) * m_pad * 4) : 0);
+    BpGraphDev &bp = g->bp;
+    bp.m = m; bp.n = n; bp.m_pad = m_pad; bp.n_pad = n_pad; bp.max_rdeg = h.max_rdeg; bp.max_cdeg = h.max_cdeg;
+    bp.neg_words = (max_rdeg_pad + 31) / 32; bp.out_words = (n + 31) / 32;
+    bp.max_rdeg_pad = max_rdeg_pad;
+    bp.dummy_bit = n_pad; bp.dummy_chk = m_pad;        // one extra LDS slot each
+    bp.sign_mode = max_rdeg_pad <= 32 ? 0 : (max_rdeg_pad <= 44 ? 1 : 2);    // mode 1: 15 spare bits of the state word hold signs 32..46
     // 32-bit offsets always (round 6: the 16-bit packing -- half of 66 KB of L2-resident adjacency for one more unpacking instruction per
     // edge, 60.4 -> 62.0 ms when K1 was the headline kernel -- was only reachable through an environment knob and doubled K1's instantiations: removed)
-    const int adj32 = 1;
-    const int rec_words = ((1 + max_cdeg) + 3) & ~3;
-    std::vector<uint8_t> chk_deg(m_pad, 0), bit_deg(n_pad, 0);
+    bp.adj32 = 1;
+    bp.rec_words = ((1 + h.max_cdeg) + 3) & ~3;
+    // LDS carve-up
+    int off = 0;
+    bp.off_chk = off; off += (m_pad + 4) * 16;                 // + the dummy check
+    bp.off_cneg = off; off += (bp.sign_mode == 2 ? align16((bp.neg_words - 1) * m_pad * 4) : 0);
+    bp.off_llr = off; off += align16((n_pad + 4) * 4);         // + the dummy bit
+    bp.off_out = off; off += align16(bp.out_words * 4);
+    bp.off_misc = off; off += 256;
+    bp.lds_bytes = off;
+    if (bp.lds_bytes > QD_LDS_BYTES)
+        return fail(QD_ECAPACITY, "window needs %d bytes of LDS for BP state; the CU has %d", bp.lds_bytes, QD_LDS_BYTES);
+    bp.threads = bp_block_threads(m, n);
+
+    std::vector<uint8_t> &chk_deg = h.chk_deg;
+    chk_deg.assign(m_pad, 0);
+    std::vector<uint8_t> bit_deg(n_pad, 0);
     std::vector<int32_t> chk_degp_w(m_pad / 64, 0);
     std::vector<uint32_t> chk_orig_u(m_pad, 0), bit_orig_u(n_pad, 0);
-    std::vector<uint32_t> bit_rec((size_t)n_pad * rec_words, (uint32_t)(off_chk_ + dummy_chk * 16) << 16);
-    // CSC with the edge's position inside its row
-    std::vector<int32_t> cp(n + 1, 0), ri(nnz), pos(nnz);
-    for (int j = 0; j < n; ++j) cp[j + 1] = cp[j] + cdeg[j];
-    {
-        std::vector<int> fill(n, 0);
-        for (int i = 0; i < m; ++i)
-            for (int e = row_ptr[i]; e < row_ptr[i + 1]; ++e) {
-                const int j = col_idx[e], dst = cp[j] + fill[j]++;
-                ri[dst] = i; pos[dst] = e - row_ptr[i];
-            }
-    }
+    std::vector<uint32_t> bit_rec((size_t)n_pad * bp.rec_words, (uint32_t)(bp.off_chk + bp.dummy_chk * 16) << 16);
     for (int s = 0; s < m; ++s) { chk_deg[s] = (uint8_t)rdeg[chk_orig[s]]; chk_orig_u[s] = (uint32_t)chk_orig[s]; }
     // wave-uniform trip counts (slots are degree-sorted, so a wavefront's lanes nearly agree anyway)
     for (int w0 = 0; w0 < m_pad; w0 += 64) {
@@ -428,7 +505,7 @@ extern "C" int qd_graph_create(int32_t m, int32_t n, const int32_t *row_ptr, con
         chk_degp_w[w0 / 64] = ((mx + 3) & ~3) | (mx << 16);      // trip count | exact maximum (edges beyond it are padding for every lane)
     }
     // check -> fault adjacency, ELL-transposed, as LDS byte offsets of the posteriors
-    std::vector<uint32_t> chk_adj32((size_t)max_rdeg_pad * m_pad, (uint32_t)(off_llr_ + dummy_bit * 4));
+    std::vector<uint32_t> chk_adj32((size_t)max_rdeg_pad * m_pad, (uint32_t)(bp.off_llr + bp.dummy_bit * 4));
     // Order in which a check walks its edges.  Nothing the check pass computes depends on it (minimum, second minimum and the
     // sign parity are symmetric; a tie for the minimum leaves min1 = min2, so it does not matter which edge carries the argmin
     // label), so it is chosen for the LDS: step k of a wavefront is one ds_read_b32 gather, serviced in two groups of 32 lanes
@@ -438,9 +515,8 @@ extern "C" int qd_graph_create(int32_t m, int32_t n, const int32_t *row_ptr, con
     // gathers (1062 without any conflict; tools/lds_model.py).
     // The scatter kernel (bp_scatter.hip) walks the same order with ds_add_u32, and lanes of one instruction that add to the SAME
     // address serialise like any other bank conflict (profiles/r03z_lds_atomic_rates.txt: two lanes per address 2.2 -> 4.7 ns per
-    // instruction), where a gather broadcasts for free: for the windows that kernel takes, a lane on a busy bank costs one cycle
-    // whatever its address.
-    const bool walk_for_atomics = scatter_shape && !std::getenv("QD_WALK_BROADCAST");
+    // instruction), where a gather broadcasts for free: for the windows that kernel takes (walk_for_atomics), a lane on a busy bank
+    // costs one cycle whatever its address.
     std::vector<int32_t> step_of(nnz);              // CSR edge -> position in its check's walk
     {
         std::vector<std::vector<int>> rem(32);
@@ -492,7 +568,7 @@ extern "C" int qd_graph_create(int32_t m, int32_t n, const int32_t *row_ptr, con
         const int i = chk_orig[s];
         for (int e = row_ptr[i]; e < row_ptr[i + 1]; ++e) {
             const int k = step_of[e];
-            const uint32_t off = (uint32_t)off_llr_ + (uint32_t)bit_slot_of[col_idx[e]] * 4u;
+            const uint32_t off = (uint32_t)bp.off_llr + (uint32_t)bit_slot_of[col_idx[e]] * 4u;
             const size_t at = ((size_t)(k >> 2) * m_pad + s) * 4 + (k & 3);      // [group of 4 edges][slot][4]: one vector load per group
             chk_adj32[at] = off;
         }
@@ -507,7 +583,7 @@ extern "C" int qd_graph_create(int32_t m, int32_t n, const int32_t *row_ptr, con
         const int j = bit_orig[s];
         bit_deg[s] = (uint8_t)cdeg[j];
         bit_orig_u[s] = (uint32_t)j;
-        const float l0 = (float)std::log((1.0 - priors[j]) / priors[j]);
+        const float l0 = (float)h.llr0[j];
         std::memcpy(&bit_rec[rec_at(s, 0)], &l0, 4);
         for (int q = 0; q < cdeg[j]; ++q) {
             const int cs = chk_slot_of[ri[cp[j] + q]];
@@ -516,126 +592,11 @@ extern "C" int qd_graph_create(int32_t m, int32_t n, const int32_t *row_ptr, con
             const int w = k >> 5, kend = std::min(degp - 32 * w, 32);
             const int sbit = kend - 1 - (k & 31);              // the check pass shifts signs in from bit 0 (v_alignbit)
             // mode 0/1: bit index into the 64-bit value {w : z} of the state (signs 32..46 sit in w's bits 16..30)
-            const uint32_t where = sign_mode == 2 ? (((uint32_t)w << 5) | (uint32_t)sbit)
-                                                  : (uint32_t)(w == 0 ? sbit : 32 + 16 + sbit);
-            bit_rec[rec_at(s, 1 + q)] = ((uint32_t)(off_chk_ + cs * 16) << 16) | where;
+            const uint32_t where = bp.sign_mode == 2 ? (((uint32_t)w << 5) | (uint32_t)sbit)
+                                                     : (uint32_t)(w == 0 ? sbit : 32 + 16 + sbit);
+            bit_rec[rec_at(s, 1 + q)] = ((uint32_t)(bp.off_chk + cs * 16) << 16) | where;
         }
     }
-    g->h_cp = cp; g->h_ri = ri;
-    g->h_bit_rec = bit_rec; g->h_bit_orig = bit_orig_u;
-    g->h_llr0.resize(n);
-    for (int j = 0; j < n; ++j) g->h_llr0[j] = std::log((1.0 - priors[j]) / priors[j]);
-    {
-        GenGraphDev &gg = g->gen;
-        gg.m = m; gg.n = n; gg.nnz = nnz; gg.out_words = (n + 31) / 32;
-        std::vector<int32_t> rp_v(row_ptr, row_ptr + m + 1), ci_v(col_idx, col_idx + nnz), c2r(nnz);
-        for (int e = 0; e < nnz; ++e) c2r[e] = row_ptr[ri[e]] + pos[e];
-        std::vector<float> l0(n);
-        for (int j = 0; j < n; ++j) l0[j] = (float)std::log((1.0 - priors[j]) / priors[j]);
-        int rcg = 0;
-        rcg |= g->mem.upload(rp_v, &gg.rp); rcg |= g->mem.upload(ci_v, &gg.ci);
-        rcg |= g->mem.upload(cp, &gg.cp); rcg |= g->mem.upload(ri, &gg.ri);
-        rcg |= g->mem.upload(c2r, &gg.c2r); rcg |= g->mem.upload(l0, &gg.llr0);
-        gg.frec = nullptr; gg.erow = nullptr;
-        if (max_cdeg <= 8 && nnz <= 65534) {
-            std::vector<uint16_t> erow(nnz);
-            for (int i = 0; i < m; ++i)
-                for (int e = row_ptr[i]; e < row_ptr[i + 1]; ++e) erow[e] = (uint16_t)i;
-            rcg |= g->mem.upload(erow, &gg.erow);
-            std::vector<uint16_t> frec((size_t)n * 16, (uint16_t)0xFFFF);
-            for (int j = 0; j < n; ++j)
-                for (int e = cp[j]; e < cp[j + 1]; ++e) {
-                    frec[(size_t)j * 16 + (e - cp[j])] = (uint16_t)c2r[e];
-                    frec[(size_t)j * 16 + 8 + (e - cp[j])] = (uint16_t)ri[e];
-                }
-            rcg |= g->mem.upload(frec, &gg.frec);
-        }
-        {
-            gg.ell_w = (max_rdeg + 63) / 64 * 64;
-            std::vector<int32_t> ell((size_t)m * gg.ell_w * 2, 0);
-            for (int i = 0; i < m; ++i)
-                for (int x = 0; x < gg.ell_w; ++x) {
-                    const int e = row_ptr[i] + x;
-                    const bool in = e < row_ptr[i + 1];
-                    ell[((size_t)i * gg.ell_w + x) * 2] = in ? col_idx[e] : -1;
-                    ell[((size_t)i * gg.ell_w + x) * 2 + 1] = in ? bit_slot_of[col_idx[e]] : 0;
-                }
-            rcg |= g->mem.upload(ell, &gg.ell);
-        }
-        {
-            // the records below pack the fault index into 24 bits of their first word: refuse before building anything
-            if (n >= (1 << 24)) { g->mem.release(); delete g; return fail(QD_EINVAL, "more than 2^24 faults"); }
-            std::vector<int32_t> last(m, 0), lev(n, 0);
-            int nlev = 0;
-            for (int j = 0; j < n; ++j) {
-                int l = 0;
-                for (int e = cp[j]; e < cp[j + 1]; ++e) l = std::max(l, last[ri[e]]);
-                lev[j] = l;                                     // 0-based
-                for (int e = cp[j]; e < cp[j + 1]; ++e) last[ri[e]] = l + 1;
-                nlev = std::max(nlev, l + 1);
-            }
-            std::vector<int32_t> lp(nlev + 1, 0), lb(n);
-            for (int j = 0; j < n; ++j) lp[lev[j] + 1]++;
-            for (int l = 0; l < nlev; ++l) lp[l + 1] += lp[l];
-            std::vector<int32_t> fillp(lp.begin(), lp.end() - 1);
-            for (int j = 0; j < n; ++j) lb[fillp[lev[j]]++] = j;
-            // LDS slots of the rows' running prefixes (see GenGraphDev): a slot is handed on only to a row that starts strictly
-            // after its previous owner's last level (two faults of one level touch their rows in any order)
-            std::vector<int32_t> first(m, nlev), lastl(m, -1), slot(m, 0), order(m);
-            for (int i = 0; i < m; ++i)
-                for (int e = row_ptr[i]; e < row_ptr[i + 1]; ++e) {
-                    first[i] = std::min(first[i], lev[col_idx[e]]);
-                    lastl[i] = std::max(lastl[i], lev[col_idx[e]]);
-                }
-            std::iota(order.begin(), order.end(), 0);
-            std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return first[a] < first[b]; });
-            std::vector<int32_t> busy_until;                // per slot: last level of its current owner
-            for (int i : order) {
-                int sidx = -1;
-                for (size_t q = 0; q < busy_until.size(); ++q)
-                    if (busy_until[q] < first[i]) { sidx = (int)q; break; }
-                if (sidx < 0) { sidx = (int)busy_until.size(); busy_until.push_back(-1); }
-                busy_until[sidx] = lastl[i];
-                slot[i] = sidx;
-            }
-            gg.nslots = ((int)busy_until.size() * 256 <= QD_GEN_PREFIX_LDS && m < (1 << 23) && !std::getenv("QD_NO_LDS_PREFIX")) ? (int)busy_until.size() : 0;
-            // one record per (step, wavefront): see GenGraphDev
-            const int G = QD_GEN_GS, D = qd_gen_unroll(max_cdeg);
-            const int RW = (2 + 2 * D + 3) & ~3;
-            size_t nstep = 0;
-            for (int l = 0; l < nlev; ++l) nstep += (size_t)(lp[l + 1] - lp[l] + G - 1) / G;
-            std::vector<uint32_t> srec(nstep * G * RW, 0u);
-            size_t st = 0;
-            for (int l = 0; l < nlev; ++l) {
-                const int cnt = lp[l + 1] - lp[l], steps = (cnt + G - 1) / G;
-                for (int q = 0; q < steps; ++q, ++st)
-                    for (int wv = 0; wv < G; ++wv) {
-                        uint32_t *r = &srec[(st * G + wv) * RW];
-                        const uint32_t bar = (q == steps - 1) ? 0x80000000u : 0u;
-                        const int x = q * G + wv;
-                        if (x >= cnt) { r[0] = bar; continue; }
-                        const int j = lb[lp[l] + x], c0 = cp[j], deg = cp[j + 1] - c0;
-                        r[0] = (uint32_t)j | ((uint32_t)deg << 24) | bar;
-                        std::memcpy(&r[1], &l0[j], 4);
-                        for (int k = 0; k < deg; ++k) {
-                            const int i = ri[c0 + k];
-                            r[2 + k] = (uint32_t)i;
-                            if (gg.nslots > 0) r[2 + k] |= ((uint32_t)slot[i] << 24) | (col_idx[row_ptr[i]] == j ? 0x800000u : 0u);
-                            r[2 + D + k] = (uint32_t)c2r[c0 + k];
-                        }
-                    }
-            }
-            gg.nlev = nlev; gg.nstep = (int)nstep; gg.srec_w = RW;
-            rcg |= g->mem.upload(srec, &gg.srec);
-        }
-        if (rcg) { g->mem.release(); delete g; return fail(QD_EHIP, "device allocation failed while building the graph"); }
-    }
-
-    BpGraphDev &bp = g->bp;
-    bp.m = m; bp.n = n; bp.m_pad = m_pad; bp.n_pad = n_pad; bp.max_rdeg = max_rdeg; bp.max_cdeg = max_cdeg;
-    bp.neg_words = (max_rdeg_pad + 31) / 32; bp.out_words = (n + 31) / 32;
-    bp.max_rdeg_pad = max_rdeg_pad; bp.dummy_bit = dummy_bit; bp.dummy_chk = dummy_chk;
-    bp.rec_words = rec_words; bp.adj32 = adj32; bp.sign_mode = sign_mode;
     for (int q = 0; q < QD_MAX_COL_DEG; ++q) {
         int cnt = 0;
         for (int w0 = 0; w0 < n_pad; w0 += 64) {
@@ -645,192 +606,288 @@ extern "C" int qd_graph_create(int32_t m, int32_t n, const int32_t *row_ptr, con
         }
         bp.bit_thr[q] = cnt;
     }
+    g->h_bit_rec = bit_rec; g->h_bit_orig = bit_orig_u;
+    const std::vector<uint32_t> slot_of(bit_slot_of.begin(), bit_slot_of.end());
     int rc = 0;
     { const uint32_t *p32 = nullptr; rc |= g->mem.upload(chk_adj32, &p32); bp.chk_adj = p32; }
     rc |= g->mem.upload(chk_degp_w, &bp.chk_degp_w);
     rc |= g->mem.upload(chk_orig_u, &bp.chk_orig);
     rc |= g->mem.upload(bit_rec, &bp.bit_rec);
     rc |= g->mem.upload(bit_orig_u, &bp.bit_orig);
-    {
-        std::vector<uint32_t> slot_of(bit_slot_of.begin(), bit_slot_of.end()), wfix((size_t)n);
-        for (int j = 0; j < n; ++j) {
-            double w = std::log(1.0 / priors[j]) * 262144.0;
-            wfix[j] = (uint32_t)std::llround(std::min(std::max(w, 0.0), 4294967295.0));
-            g->osd.max_wfix = std::max(g->osd.max_wfix, wfix[j]);
-        }
-        rc |= g->mem.upload(slot_of, &bp.bit_slot_of);
-        rc |= g->mem.upload(wfix, &g->osd.wfix);
-    }
-    // LDS carve-up for BP
-    int off = 0;
-    bp.off_chk = off; off += (m_pad + 4) * 16;                 // + the dummy check
-    bp.off_cneg = off; off += (sign_mode == 2 ? align16((bp.neg_words - 1) * m_pad * 4) : 0);
-    bp.off_llr = off; off += align16((n_pad + 4) * 4);         // + the dummy bit
-    if (bp.off_chk != off_chk_ || bp.off_cneg != off_cneg_ || bp.off_llr != off_llr_) {
-        g->mem.release(); delete g;
-        return fail(QD_EINVAL, "internal: LDS layout mismatch");
-    }
-    bp.off_out = off; off += align16(bp.out_words * 4);
-    bp.off_misc = off; off += 256;
-    bp.lds_bytes = off;
-    const int need = std::max(m, (n + 9) / 10);
-    bp.threads = need <= 256 ? 256 : (need <= 512 ? 512 : 1024);
+    rc |= g->mem.upload(slot_of, &bp.bit_slot_of);
+    if (rc) return fail(QD_EHIP, "device allocation/upload failed");
+    return QD_OK;
+}
 
-    // Scatter form of the flooding min-sum kernel (bp_scatter.hip): one check per lane with its state in registers, two integer
-    // posterior buffers in LDS.  Admitted when every check has a lane, rows hold 2..64 faults (two sign words; a row of one fault
-    // has no second minimum) and the two buffers leave as many workgroups per CU as the gather kernel's layout does.
+// The one-message-per-edge kernels' view (GenGraphDev): CSR / CSC, the serial schedule's levels and its rows' LDS prefix slots
+static int build_gen(qd_graph *g, const HostGraph &h)
+{
+    const int m = h.m, n = h.n, nnz = h.nnz;
+    const int32_t *row_ptr = h.row_ptr, *col_idx = h.col_idx;
+    const std::vector<int32_t> &cp = h.cp, &ri = h.ri;
+    GenGraphDev &gg = g->gen;
+    gg.m = m; gg.n = n; gg.nnz = nnz; gg.out_words = (n + 31) / 32;
+    std::vector<int32_t> rp_v(row_ptr, row_ptr + m + 1), ci_v(col_idx, col_idx + nnz), c2r(nnz);
+    for (int e = 0; e < nnz; ++e) c2r[e] = row_ptr[ri[e]] + h.pos[e];
+    const std::vector<float> l0(h.llr0.begin(), h.llr0.end());
+    int rcg = 0;
+    rcg |= g->mem.upload(rp_v, &gg.rp); rcg |= g->mem.upload(ci_v, &gg.ci);
+    rcg |= g->mem.upload(cp, &gg.cp); rcg |= g->mem.upload(ri, &gg.ri);
+    rcg |= g->mem.upload(c2r, &gg.c2r); rcg |= g->mem.upload(l0, &gg.llr0);
+    gg.frec = nullptr; gg.erow = nullptr;
+    if (h.max_cdeg <= 8 && nnz <= 65534) {
+        std::vector<uint16_t> erow(nnz);
+        for (int i = 0; i < m; ++i)
+            for (int e = row_ptr[i]; e < row_ptr[i + 1]; ++e) erow[e] = (uint16_t)i;
+        rcg |= g->mem.upload(erow, &gg.erow);
+        std::vector<uint16_t> frec((size_t)n * 16, (uint16_t)0xFFFF);
+        for (int j = 0; j < n; ++j)
+            for (int e = cp[j]; e < cp[j + 1]; ++e) {
+                frec[(size_t)j * 16 + (e - cp[j])] = (uint16_t)c2r[e];
+                frec[(size_t)j * 16 + 8 + (e - cp[j])] = (uint16_t)ri[e];
+            }
+        rcg |= g->mem.upload(frec, &gg.frec);
+    }
     {
-        ScatGraphDev &sc = g->sc;
-        sc = ScatGraphDev{};
-        const int min_rdeg = *std::min_element(rdeg.begin(), rdeg.end());
-        // ---- the accumulators' own slot order: a bank for every fault (scatter_banks), then bank + 32 * (rank inside the bank)
-        std::vector<int> sc_bank, sc_slot;
-        int sc_rows = 0;
-        if (scatter_shape) {
-            scatter_banks(m, n, row_ptr, col_idx, chk_orig, bit_slot_of, sc_bank);
-            std::vector<int> fillb(32, 0);
-            sc_slot.resize(n);
-            for (int j = 0; j < n; ++j) sc_slot[j] = sc_bank[j] + 32 * fillb[sc_bank[j]]++;
-            sc_rows = *std::max_element(fillb.begin(), fillb.end());
+        gg.ell_w = (h.max_rdeg + 63) / 64 * 64;
+        std::vector<int32_t> ell((size_t)m * gg.ell_w * 2, 0);
+        for (int i = 0; i < m; ++i)
+            for (int x = 0; x < gg.ell_w; ++x) {
+                const int e = row_ptr[i] + x;
+                const bool in = e < row_ptr[i + 1];
+                ell[((size_t)i * gg.ell_w + x) * 2] = in ? col_idx[e] : -1;
+                ell[((size_t)i * gg.ell_w + x) * 2 + 1] = in ? h.bit_slot_of[col_idx[e]] : 0;
+            }
+        rcg |= g->mem.upload(ell, &gg.ell);
+    }
+    // the records below pack the fault index into 24 bits of their first word (host_graph refuses larger windows long before)
+    std::vector<int32_t> last(m, 0), lev(n, 0);
+    int nlev = 0;
+    for (int j = 0; j < n; ++j) {
+        int l = 0;
+        for (int e = cp[j]; e < cp[j + 1]; ++e) l = std::max(l, last[ri[e]]);
+        lev[j] = l;                                     // 0-based
+        for (int e = cp[j]; e < cp[j + 1]; ++e) last[ri[e]] = l + 1;
+        nlev = std::max(nlev, l + 1);
+    }
+    std::vector<int32_t> lp(nlev + 1, 0), lb(n);
+    for (int j = 0; j < n; ++j) lp[lev[j] + 1]++;
+    for (int l = 0; l < nlev; ++l) lp[l + 1] += lp[l];
+    std::vector<int32_t> fillp(lp.begin(), lp.end() - 1);
+    for (int j = 0; j < n; ++j) lb[fillp[lev[j]]++] = j;
+    // LDS slots of the rows' running prefixes (see GenGraphDev): a slot is handed on only to a row that starts strictly
+    // after its previous owner's last level (two faults of one level touch their rows in any order)
+    std::vector<int32_t> first(m, nlev), lastl(m, -1), slot(m, 0), order(m);
+    for (int i = 0; i < m; ++i)
+        for (int e = row_ptr[i]; e < row_ptr[i + 1]; ++e) {
+            first[i] = std::min(first[i], lev[col_idx[e]]);
+            lastl[i] = std::max(lastl[i], lev[col_idx[e]]);
         }
-        const int sc_trash = 32 * sc_rows;                     // 32 trash slots, one per bank, behind the accumulators
-        sc.nslots = scatter_shape ? sc_trash + 32 : n_pad + 4;
-        const int buf = align16(sc.nslots * 4);
-        sc.offA = 0; sc.offB = 0; sc.off_out = buf;            // one buffer: the scatter pass works in place
-        sc.off_bmap = sc.off_out + align16(bp.out_words * 4);
-        sc.off_misc = sc.off_bmap;
-        sc.lds_bytes = sc.off_misc + 256;
-        const int by_threads = 2048 / bp.threads;
-        const int res_old = std::min(by_threads, QD_LDS_BYTES / std::max(1, bp.lds_bytes));
-        // the shape that will really be launched (the residency test used to look at a shape that never ran): several
-        // checks per lane -- see below for the measurements behind each case
-        int shape_threads = bp.threads, shape_cpl = 1;
-        if (scatter_wide) {
-            shape_threads = wide_threads_; shape_cpl = 2;
-            if (std::getenv("QD_SCATTER_WIDE_T1024")) { shape_threads = 1024; shape_cpl = 2; }                // A/B: 16 wavefronts x 2 checks
-            else if (m <= 1536 && !std::getenv("QD_SCATTER_WIDE_T704")) { shape_threads = 512; shape_cpl = 3; }    // 19.8 -> 19.3 ms per QLP launch
-        } else if (!std::getenv("QD_SCATTER_CPL1")) {
-            if (bp.threads == 1024 && 4 * sc.lds_bytes <= QD_LDS_BYTES) { shape_threads = 512; shape_cpl = 2; }
-            else if (bp.threads == 512 && 8 * sc.lds_bytes <= QD_LDS_BYTES && !std::getenv("QD_SCATTER_NO_CPL2_256")) { shape_threads = 256; shape_cpl = 2; }
-            else if (bp.threads == 256 && 16 * sc.lds_bytes <= QD_LDS_BYTES) { shape_threads = 128; shape_cpl = 2; }    // (<= 256 checks)
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return first[a] < first[b]; });
+    std::vector<int32_t> busy_until;                // per slot: last level of its current owner
+    for (int i : order) {
+        int sidx = -1;
+        for (size_t q = 0; q < busy_until.size(); ++q)
+            if (busy_until[q] < first[i]) { sidx = (int)q; break; }
+        if (sidx < 0) { sidx = (int)busy_until.size(); busy_until.push_back(-1); }
+        busy_until[sidx] = lastl[i];
+        slot[i] = sidx;
+    }
+    gg.nslots = ((int)busy_until.size() * 256 <= QD_GEN_PREFIX_LDS && m < (1 << 23)) ? (int)busy_until.size() : 0;
+    // one record per (step, wavefront): see GenGraphDev
+    const int G = QD_GEN_GS, D = qd_gen_unroll(h.max_cdeg);
+    const int RW = (2 + 2 * D + 3) & ~3;
+    size_t nstep = 0;
+    for (int l = 0; l < nlev; ++l) nstep += (size_t)(lp[l + 1] - lp[l] + G - 1) / G;
+    std::vector<uint32_t> srec(nstep * G * RW, 0u);
+    size_t st = 0;
+    for (int l = 0; l < nlev; ++l) {
+        const int cnt = lp[l + 1] - lp[l], steps = (cnt + G - 1) / G;
+        for (int q = 0; q < steps; ++q, ++st)
+            for (int wv = 0; wv < G; ++wv) {
+                uint32_t *r = &srec[(st * G + wv) * RW];
+                const uint32_t bar = (q == steps - 1) ? 0x80000000u : 0u;
+                const int x = q * G + wv;
+                if (x >= cnt) { r[0] = bar; continue; }
+                const int j = lb[lp[l] + x], c0 = cp[j], deg = cp[j + 1] - c0;
+                r[0] = (uint32_t)j | ((uint32_t)deg << 24) | bar;
+                std::memcpy(&r[1], &l0[j], 4);
+                for (int k = 0; k < deg; ++k) {
+                    const int i = ri[c0 + k];
+                    r[2 + k] = (uint32_t)i;
+                    if (gg.nslots > 0) r[2 + k] |= ((uint32_t)slot[i] << 24) | (col_idx[row_ptr[i]] == j ? 0x800000u : 0u);
+                    r[2 + D + k] = (uint32_t)c2r[c0 + k];
+                }
+            }
+    }
+    gg.nlev = nlev; gg.nstep = (int)nstep; gg.srec_w = RW;
+    rcg |= g->mem.upload(srec, &gg.srec);
+    if (rcg) return fail(QD_EHIP, "device allocation failed while building the graph");
+    return QD_OK;
+}
+
+// Scatter form of the flooding min-sum kernel (bp_scatter.hip, bp_scatter_wide.hip; ScatGraphDev): checks in lanes with their state in
+// registers, the faults' integer posterior accumulators in LDS.  Taken (sc.ok) for the windows of scatter_form whose accumulators leave
+// as many workgroups per CU as the gather kernel's layout does.
+static int build_scatter(qd_graph *g, const HostGraph &h, int form, const Switches &env)
+{
+    ScatGraphDev &sc = g->sc;
+    const BpGraphDev &bp = g->bp;
+    sc = ScatGraphDev{};
+    if (!form) return QD_OK;
+    const int m = h.m, n = h.n, m_pad = h.m_pad;
+    const int32_t *row_ptr = h.row_ptr, *col_idx = h.col_idx;
+    // ---- the accumulators' own slot order: a bank for every fault (scatter_banks), then bank + 32 * (rank inside the bank)
+    std::vector<int> sc_bank, sc_slot(n), fillb(32, 0);
+    scatter_banks(m, n, row_ptr, col_idx, h.chk_orig, h.bit_slot_of, env.scatter_banks_by_slot, sc_bank);
+    for (int j = 0; j < n; ++j) sc_slot[j] = sc_bank[j] + 32 * fillb[sc_bank[j]]++;
+    const int sc_trash = 32 * *std::max_element(fillb.begin(), fillb.end());    // 32 trash slots, one per bank, behind the accumulators
+    sc.nslots = sc_trash + 32;
+    const int buf = align16(sc.nslots * 4);
+    sc.offA = 0; sc.offB = 0; sc.off_out = buf;            // one buffer: the scatter pass works in place
+    sc.off_bmap = sc.off_out + align16(bp.out_words * 4);
+    sc.off_misc = sc.off_bmap;
+    sc.lds_bytes = sc.off_misc + 256;
+    const int res_old = std::min(2048 / bp.threads, QD_LDS_BYTES / std::max(1, bp.lds_bytes));
+    // the shape that will really be launched (the residency test used to look at a shape that never ran): several
+    // checks per lane -- see below for the measurements behind each case
+    int shape_threads = bp.threads, shape_cpl = 1;
+    if (form == 2) {
+        shape_threads = scatter_wide_threads(m); shape_cpl = 2;
+        if (m <= 1536 && !env.scatter_wide_t704) { shape_threads = 512; shape_cpl = 3; }    // 19.8 -> 19.3 ms per QLP launch
+    } else if (!env.scatter_cpl1) {
+        if (bp.threads == 1024 && 4 * sc.lds_bytes <= QD_LDS_BYTES) { shape_threads = 512; shape_cpl = 2; }
+        else if (bp.threads == 512 && 8 * sc.lds_bytes <= QD_LDS_BYTES) { shape_threads = 256; shape_cpl = 2; }
+        else if (bp.threads == 256 && 16 * sc.lds_bytes <= QD_LDS_BYTES) { shape_threads = 128; shape_cpl = 2; }    // (<= 256 checks)
+    }
+    const int res_new = std::min(2048 / shape_threads, QD_LDS_BYTES / sc.lds_bytes);
+    if (res_new < res_old) { sc = ScatGraphDev{}; return QD_OK; }      // (res_old >= 1: build_bp checked the gather kernel's LDS)
+    const int rows = h.max_rdeg_pad / 4 + 2;          // two spare group rows: the kernel loads up to two groups ahead unconditionally
+    // every entry starts at the trash slot of bank (lane mod 32): the steps nobody reaches and the two spare rows
+    std::vector<uint32_t> adjA((size_t)rows * m_pad * 4);
+    for (int r = 0; r < rows; ++r)
+        for (int s = 0; s < m_pad; ++s)
+            for (int q = 0; q < 4; ++q) adjA[((size_t)r * m_pad + s) * 4 + q] = (uint32_t)sc.offA + (uint32_t)(sc_trash + (s & 31)) * 4u;
+    long long walk_cyc = 0, walk_ideal = 0;
+    std::vector<uint8_t> edge_step((size_t)h.nnz, 0xFF);
+    bool walk_ok = true;
+    scatter_walk(m, row_ptr, col_idx, h.chk_orig, sc_bank, env.scatter_walk_greedy, [&](int s, int k, int e, int trash_bank) {
+        const uint32_t slot = e >= 0 ? (uint32_t)sc_slot[col_idx[e]] : (uint32_t)(sc_trash + trash_bank);
+        if (k < 0 || k >= rows * 4 || s < 0 || s >= m_pad) { walk_ok = false; return; }
+        if (e >= 0) {                                      // a real edge: once, at a step below its check's degree
+            const int i = s < m ? h.chk_orig[s] : -1;
+            if (i < 0 || e < row_ptr[i] || e >= row_ptr[i + 1] || k >= h.rdeg[i] || edge_step[e] != 0xFF) { walk_ok = false; return; }
+            edge_step[e] = (uint8_t)k;
         }
-        const int res_new = std::min(2048 / shape_threads, QD_LDS_BYTES / sc.lds_bytes);
-        if (scatter_shape && min_rdeg >= 2 && bp.lds_bytes <= QD_LDS_BYTES && res_new >= 1 && res_new >= res_old) {
-            const int rows = max_rdeg_pad / 4 + 2;            // two spare group rows: the kernel loads up to two groups ahead unconditionally
-            // every entry starts at the trash slot of bank (lane mod 32): the steps nobody reaches and the two spare rows
-            std::vector<uint32_t> adjA((size_t)rows * m_pad * 4);
-            for (int r = 0; r < rows; ++r)
-                for (int s = 0; s < m_pad; ++s)
-                    for (int q = 0; q < 4; ++q) adjA[((size_t)r * m_pad + s) * 4 + q] = (uint32_t)sc.offA + (uint32_t)(sc_trash + (s & 31)) * 4u;
-            long long walk_cyc = 0, walk_ideal = 0;
-            std::vector<uint8_t> edge_step((size_t)nnz, 0xFF);
-            bool walk_ok = true;
-            scatter_walk(m, row_ptr, col_idx, chk_orig, sc_bank, [&](int s, int k, int e, int trash_bank) {
-                const uint32_t slot = e >= 0 ? (uint32_t)sc_slot[col_idx[e]] : (uint32_t)(sc_trash + trash_bank);
-                if (k < 0 || k >= rows * 4 || s < 0 || s >= m_pad) { walk_ok = false; return; }
-                if (e >= 0) {                                      // a real edge: once, at a step below its check's degree
-                    const int i = s < m ? chk_orig[s] : -1;
-                    if (i < 0 || e < row_ptr[i] || e >= row_ptr[i + 1] || k >= rdeg[i] || edge_step[e] != 0xFF) { walk_ok = false; return; }
-                    edge_step[e] = (uint8_t)k;
-                }
-                adjA[((size_t)(k >> 2) * m_pad + s) * 4 + (k & 3)] = (uint32_t)sc.offA + slot * 4u;
-            }, &walk_cyc, &walk_ideal);
-            for (int i = 0; i < m && walk_ok; ++i) {               // every step below the degree taken exactly once
-                uint64_t seen_lo = 0, seen_hi = 0;
-                for (int e = row_ptr[i]; e < row_ptr[i + 1]; ++e) {
-                    const int k = edge_step[e];
-                    if (k == 0xFF) { walk_ok = false; break; }
-                    uint64_t &w = k < 64 ? seen_lo : seen_hi;
-                    if ((w >> (k & 63)) & 1u) { walk_ok = false; break; }
-                    w |= 1ull << (k & 63);
-                }
-            }
-            if (!walk_ok) { g->mem.release(); delete g; return fail(QD_ECAPACITY, "scatter walk: an edge was not placed exactly once below its check's degree"); }
-            g->sc_walk_cycles = walk_cyc; g->sc_walk_ideal = walk_ideal;
-            std::vector<uint32_t> slot_fault((size_t)sc.nslots, 0xFFFFFFFFu), k1_slot((size_t)n, 0u);
-            for (int j = 0; j < n; ++j) { slot_fault[sc_slot[j]] = (uint32_t)j; k1_slot[bit_slot_of[j]] = (uint32_t)sc_slot[j]; }
-            g->h_sc_slot.assign(sc_slot.begin(), sc_slot.end());
-            std::vector<uint32_t> deg_w(m_pad / 64, 0u);
-            for (int w0 = 0; w0 < m; w0 += 64) {
-                int mx = 0, mn = 255;
-                for (int s = w0; s < std::min(m, w0 + 64); ++s) { mx = std::max(mx, (int)chk_deg[s]); mn = std::min(mn, (int)chk_deg[s]); }
-                deg_w[w0 / 64] = (uint32_t)((mx + 3) & ~3) | ((uint32_t)mx << 8) | ((uint32_t)mn << 16);
-            }
-            int rcs = 0;
-            rcs |= g->mem.upload(adjA, &sc.adjA); sc.adjB = sc.adjA;
-            rcs |= g->mem.upload(slot_fault, &sc.slot_fault); rcs |= g->mem.upload(k1_slot, &sc.k1_slot);
-            rcs |= g->mem.upload(deg_w, &sc.deg_w); rcs |= g->mem.upload(chk_deg, &sc.chk_deg);
-            if (rcs) { g->mem.release(); delete g; return fail(QD_EHIP, "device allocation failed while uploading the scatter adjacency"); }
-            sc.ok = 1;
-            // Several checks per lane (bp_scatter_wide.hip).  (a) windows the one-check-per-lane kernel cannot take: three checks per
-            // lane on 512 lanes (or two on 704 / 1024).  (b) windows it can take, on HALF the lanes with two checks each: the same number
-            // of wavefronts per CU in twice as many workgroups, i.e. half as many wavefronts per barrier -- headline BP 50.3 -> 44.2 ms per
-            // 65 536 shots, same bits (profiles/r03x_scatter_cpl2_ab.txt); taken when the LDS holds twice the workgroups.
-            // QD_SCATTER_CPL1=1 keeps one check per lane.  Measured and not kept (profiles/r03x_scatter_shapes2_ab.txt): four checks per
-            // lane on a quarter of the lanes (headline 46.2 -> 50.9 ms), 384 lanes x 4 checks for the QLP windows (19.2 -> 24.4 ms).
-            sc.wide_threads = shape_cpl > 1 ? shape_threads : 0; sc.wide_cpl = shape_cpl > 1 ? shape_cpl : 0;
-            if (sc.wide_threads) {
-                // deal the slot-waves (64 consecutive check slots, heaviest first) to the workgroup's wavefronts so that the largest
-                // number of edges a wavefront walks between two barriers is small: each goes to the wavefront with the fewest edges so
-                // far that still has a free round (longest-processing-time rule), then single moves / swaps out of the heaviest
-                // wavefront while they lower the maximum (QLP windows on 8 wavefronts x 3 rounds: 222 -> 202 edge steps)
-                const int nw = sc.wide_threads / 64, nsw = m_pad / 64, cpl = sc.wide_cpl;
-                const bool natural = std::getenv("QD_SCATTER_NATURAL_ROUNDS") != nullptr;      // A/B: round j of wavefront w = slot-wave j * nw + w
-                auto cost = [&](int sw) { return (int)(deg_w[sw] & 0xFF) + 6; };               // trip count + the per-check work outside the edge loops
-                std::vector<std::vector<int>> bins(nw);
-                std::vector<int> load(nw, 0);
-                for (int sw = 0; sw < nsw; ++sw) {
-                    int best = -1;
-                    if (natural) best = sw % nw;
-                    else
-                        for (int w = 0; w < nw; ++w)
-                            if ((int)bins[w].size() < cpl && (best < 0 || load[w] < load[best])) best = w;
-                    if (best < 0 || (int)bins[best].size() >= cpl) { g->mem.release(); delete g; return fail(QD_ECAPACITY, "scatter kernel shape does not cover the window"); }
-                    bins[best].push_back(sw); load[best] += cost(sw);
-                }
-                for (int pass = 0; pass < 1000 && !natural; ++pass) {
-                    const int hi = (int)(std::max_element(load.begin(), load.end()) - load.begin()), Lh = load[hi];
-                    int gain = 0, bi = -1, bw = -1, bk = -1;
-                    for (int i = 0; i < (int)bins[hi].size(); ++i) {
-                        const int x = cost(bins[hi][i]);
-                        for (int w = 0; w < nw; ++w) {
-                            if (w == hi) continue;
-                            if ((int)bins[w].size() < cpl) {
-                                const int nl = std::max(Lh - x, load[w] + x);
-                                if (Lh - nl > gain) { gain = Lh - nl; bi = i; bw = w; bk = -1; }
-                            }
-                            for (int k = 0; k < (int)bins[w].size(); ++k) {
-                                const int y = cost(bins[w][k]);
-                                if (y >= x) continue;
-                                const int nl = std::max(Lh - x + y, load[w] - y + x);
-                                if (Lh - nl > gain) { gain = Lh - nl; bi = i; bw = w; bk = k; }
-                            }
-                        }
-                    }
-                    if (bi < 0) break;
-                    const int x = cost(bins[hi][bi]);
-                    if (bk < 0) { bins[bw].push_back(bins[hi][bi]); bins[hi].erase(bins[hi].begin() + bi); load[hi] -= x; load[bw] += x; }
-                    else { const int y = cost(bins[bw][bk]); std::swap(bins[hi][bi], bins[bw][bk]); load[hi] += y - x; load[bw] += x - y; }
-                }
-                std::vector<int32_t> wmap((size_t)cpl * nw, -1);
-                for (int w = 0; w < nw; ++w)
-                    for (int j = 0; j < (int)bins[w].size(); ++j) wmap[(size_t)j * nw + w] = bins[w][j];
-                if (g->mem.upload(wmap, &sc.wave_map)) { g->mem.release(); delete g; return fail(QD_EHIP, "device allocation failed while uploading the scatter wave map"); }
-            }
+        adjA[((size_t)(k >> 2) * m_pad + s) * 4 + (k & 3)] = (uint32_t)sc.offA + slot * 4u;
+    }, &walk_cyc, &walk_ideal);
+    for (int i = 0; i < m && walk_ok; ++i) {               // every step below the degree taken exactly once
+        uint64_t seen_lo = 0, seen_hi = 0;
+        for (int e = row_ptr[i]; e < row_ptr[i + 1]; ++e) {
+            const int k = edge_step[e];
+            if (k == 0xFF) { walk_ok = false; break; }
+            uint64_t &w = k < 64 ? seen_lo : seen_hi;
+            if ((w >> (k & 63)) & 1u) { walk_ok = false; break; }
+            w |= 1ull << (k & 63);
         }
     }
+    if (!walk_ok) return fail(QD_ECAPACITY, "scatter walk: an edge was not placed exactly once below its check's degree");
+    g->sc_walk_cycles = walk_cyc; g->sc_walk_ideal = walk_ideal;
+    std::vector<uint32_t> slot_fault((size_t)sc.nslots, 0xFFFFFFFFu), k1_slot((size_t)n, 0u);
+    for (int j = 0; j < n; ++j) { slot_fault[sc_slot[j]] = (uint32_t)j; k1_slot[h.bit_slot_of[j]] = (uint32_t)sc_slot[j]; }
+    g->h_sc_slot.assign(sc_slot.begin(), sc_slot.end());
+    std::vector<uint32_t> deg_w(m_pad / 64, 0u);
+    for (int w0 = 0; w0 < m; w0 += 64) {
+        int mx = 0, mn = 255;
+        for (int s = w0; s < std::min(m, w0 + 64); ++s) { mx = std::max(mx, (int)h.chk_deg[s]); mn = std::min(mn, (int)h.chk_deg[s]); }
+        deg_w[w0 / 64] = (uint32_t)((mx + 3) & ~3) | ((uint32_t)mx << 8) | ((uint32_t)mn << 16);
+    }
+    int rcs = 0;
+    rcs |= g->mem.upload(adjA, &sc.adjA); sc.adjB = sc.adjA;
+    rcs |= g->mem.upload(slot_fault, &sc.slot_fault); rcs |= g->mem.upload(k1_slot, &sc.k1_slot);
+    rcs |= g->mem.upload(deg_w, &sc.deg_w); rcs |= g->mem.upload(h.chk_deg, &sc.chk_deg);
+    if (rcs) return fail(QD_EHIP, "device allocation failed while uploading the scatter adjacency");
+    sc.ok = 1;
+    // Several checks per lane (bp_scatter_wide.hip).  (a) windows the one-check-per-lane kernel cannot take: three checks per
+    // lane on 512 lanes (or two on 704 / 1024).  (b) windows it can take, on HALF the lanes with two checks each: the same number
+    // of wavefronts per CU in twice as many workgroups, i.e. half as many wavefronts per barrier -- headline BP 50.3 -> 44.2 ms per
+    // 65 536 shots, same bits (profiles/r03x_scatter_cpl2_ab.txt); taken when the LDS holds twice the workgroups.
+    // QD_SCATTER_CPL1=1 keeps one check per lane.  Measured and not kept (profiles/r03x_scatter_shapes2_ab.txt): four checks per
+    // lane on a quarter of the lanes (headline 46.2 -> 50.9 ms), 384 lanes x 4 checks for the QLP windows (19.2 -> 24.4 ms).
+    sc.wide_threads = shape_cpl > 1 ? shape_threads : 0; sc.wide_cpl = shape_cpl > 1 ? shape_cpl : 0;
+    if (!sc.wide_threads) return QD_OK;
+    // deal the slot-waves (64 consecutive check slots, heaviest first) to the workgroup's wavefronts so that the largest
+    // number of edges a wavefront walks between two barriers is small: each goes to the wavefront with the fewest edges so
+    // far that still has a free round (longest-processing-time rule), then single moves / swaps out of the heaviest
+    // wavefront while they lower the maximum (QLP windows on 8 wavefronts x 3 rounds: 222 -> 202 edge steps)
+    const int nw = sc.wide_threads / 64, nsw = m_pad / 64, cpl = sc.wide_cpl;
+    const bool natural = env.scatter_natural_rounds;                   // round j of wavefront w = slot-wave j * nw + w
+    auto cost = [&](int sw) { return (int)(deg_w[sw] & 0xFF) + 6; };   // trip count + the per-check work outside the edge loops
+    std::vector<std::vector<int>> bins(nw);
+    std::vector<int> load(nw, 0);
+    for (int sw = 0; sw < nsw; ++sw) {
+        int best = -1;
+        if (natural) best = sw % nw;
+        else
+            for (int w = 0; w < nw; ++w)
+                if ((int)bins[w].size() < cpl && (best < 0 || load[w] < load[best])) best = w;
+        if (best < 0 || (int)bins[best].size() >= cpl) return fail(QD_ECAPACITY, "scatter kernel shape does not cover the window");
+        bins[best].push_back(sw); load[best] += cost(sw);
+    }
+    for (int pass = 0; pass < 1000 && !natural; ++pass) {
+        const int hi = (int)(std::max_element(load.begin(), load.end()) - load.begin()), Lh = load[hi];
+        int gain = 0, bi = -1, bw = -1, bk = -1;
+        for (int i = 0; i < (int)bins[hi].size(); ++i) {
+            const int x = cost(bins[hi][i]);
+            for (int w = 0; w < nw; ++w) {
+                if (w == hi) continue;
+                if ((int)bins[w].size() < cpl) {
+                    const int nl = std::max(Lh - x, load[w] + x);
+                    if (Lh - nl > gain) { gain = Lh - nl; bi = i; bw = w; bk = -1; }
+                }
+                for (int k = 0; k < (int)bins[w].size(); ++k) {
+                    const int y = cost(bins[w][k]);
+                    if (y >= x) continue;
+                    const int nl = std::max(Lh - x + y, load[w] - y + x);
+                    if (Lh - nl > gain) { gain = Lh - nl; bi = i; bw = w; bk = k; }
+                }
+            }
+        }
+        if (bi < 0) break;
+        const int x = cost(bins[hi][bi]);
+        if (bk < 0) { bins[bw].push_back(bins[hi][bi]); bins[hi].erase(bins[hi].begin() + bi); load[hi] -= x; load[bw] += x; }
+        else { const int y = cost(bins[bw][bk]); std::swap(bins[hi][bi], bins[bw][bk]); load[hi] += y - x; load[bw] += x - y; }
+    }
+    std::vector<int32_t> wmap((size_t)cpl * nw, -1);
+    for (int w = 0; w < nw; ++w)
+        for (int j = 0; j < (int)bins[w].size(); ++j) wmap[(size_t)j * nw + w] = bins[w][j];
+    if (g->mem.upload(wmap, &sc.wave_map)) return fail(QD_EHIP, "device allocation failed while uploading the scatter wave map");
+    return QD_OK;
+}
 
-    // OSD view
+// The elimination kernels' view (OsdGraphDev): fault weights, CSC, the LDS layouts of the OSD kernels and the SR kernel's ELL columns
+static int build_osd(qd_graph *g, const HostGraph &h)
+{
+    const int m = h.m, n = h.n, m_pad = h.m_pad, max_cdeg = h.max_cdeg, out_words = g->bp.out_words;
     OsdGraphDev &od = g->osd;
+    std::vector<uint32_t> wfix((size_t)n);
+    for (int j = 0; j < n; ++j) {
+        double w = std::log(1.0 / h.priors[j]) * 262144.0;
+        wfix[j] = (uint32_t)std::llround(std::min(std::max(w, 0.0), 4294967295.0));
+        od.max_wfix = std::max(od.max_wfix, wfix[j]);
+    }
     od.m = m; od.n = n; od.m_pad = m_pad; od.max_cdeg = max_cdeg; od.mw = (m + 63) / 64;
     int np2 = 64;
     while (np2 < n) np2 <<= 1;
     od.npow2 = np2;
-    std::vector<uint32_t> csc_ptr(cp.begin(), cp.end());
-    std::vector<uint16_t> csc_row(ri.begin(), ri.end());
+    std::vector<uint32_t> csc_ptr(h.cp.begin(), h.cp.end());
+    std::vector<uint16_t> csc_row(h.ri.begin(), h.ri.end());
+    int rc = 0;
+    rc |= g->mem.upload(wfix, &od.wfix);
     rc |= g->mem.upload(csc_ptr, &od.csc_ptr);
     rc |= g->mem.upload(csc_row, &od.csc_row);
-    if (rc) { g->mem.release(); delete g; return fail(QD_EHIP, "device allocation/upload failed"); }
+    if (rc) return fail(QD_EHIP, "device allocation/upload failed");
     auto carve = [&](int *offs, int qbytes, int base) {
         int o = base;
         offs[0] = o; o += align16(qbytes);
@@ -842,7 +899,7 @@ extern "C" int qd_graph_create(int32_t m, int32_t n, const int32_t *row_ptr, con
         offs[6] = o; o += align16(64 * max_cdeg * 4);  // pairs
         offs[7] = o; o += 256;                         // cols
         offs[8] = o; o += 1024;                        // red: 96 words of pivot/flag/counter scratch + 2 x 64 words of block sums
-        offs[9] = o; o += align16(bp.out_words * 4);   // out
+        offs[9] = o; o += align16(out_words * 4);      // out
         return o;
     };
     int tmp[10];
@@ -851,10 +908,6 @@ extern "C" int qd_graph_create(int32_t m, int32_t n, const int32_t *row_ptr, con
     const int sort_bytes = np2 * 8;
     od.threads = m <= 256 ? 256 : (m <= 512 ? 512 : 1024);
     od.f_threads = m <= 256 ? 256 : 512;       // (256 threads with 4 rows each measured slower at m = 1008: 20.4 vs 16.3 ms)
-    if (const char *ev = std::getenv("QD_OSD_THREADS")) {          // tuning knob
-        const int v = std::atoi(ev);
-        if ((v == 256 || v == 512) && (m + v - 1) / v <= 4) od.f_threads = v;
-    }
     od.lds_bytes = 0; od.kw_lds = 0; od.f_lds_bytes = 0; od.f_kw = 0;
     if (sort_bytes <= q_budget) {
         od.kw_lds = std::min(od.mw, q_budget / (m_pad * 8));
@@ -868,7 +921,7 @@ extern "C" int qd_graph_create(int32_t m, int32_t n, const int32_t *row_ptr, con
         od.f_lds_bytes = 0; od.w_lds_bytes = 0;
         // `sweep`: higher-order OSD also keeps a pivot-column bit mask and the list of the first non-pivot columns
         auto lay = [&](int per_cu, bool sweep, int *offs, int &o_sort, int &o_order, int &o_piv, int &o_npl, int &kw) -> int {
-            const int extra = sweep ? align16(bp.out_words * 4) + 256 : 0;
+            const int extra = sweep ? align16(out_words * 4) + 256 : 0;
             const int f_budget = QD_LDS_BYTES / per_cu - 256 - small - sort_b - order_b - extra;
             kw = std::min(od.mw, std::max(0, f_budget / (m_pad * 8)));
             const int min_planes = sweep ? 6 : 2;          // the Q mirror holds at least the planes the kernel keeps in registers (QD_OSD_KWR / QD_OSD_KWR0)
@@ -877,14 +930,13 @@ extern "C" int qd_graph_create(int32_t m, int32_t n, const int32_t *row_ptr, con
             o_sort = o; o += sort_b;
             o_order = o; o += order_b;
             o_piv = o; o_npl = o;                       // unused by OSD-0
-            if (sweep) { o_piv = o; o += align16(bp.out_words * 4); o_npl = o; o += 256; }
+            if (sweep) { o_piv = o; o += align16(out_words * 4); o_npl = o; o += 256; }
             return o <= QD_LDS_BYTES / per_cu ? o : 0;
         };
         od.f_off_hist = 0;
-        // three workgroups per CU where the window allows it (two Q planes in LDS, the rest in the HBM spill): most of a shot is spent
-        // in single-wavefront phases, so the third workgroup is worth more than the planes (headline 10.8 -> 10.1 ms, p = 6e-3 164 -> 154 ms)
-        const int per_cu0 = std::getenv("QD_OSD_PER_CU") ? std::atoi(std::getenv("QD_OSD_PER_CU")) : 2;   // (the register budget of qd_osd0_reg_kernel<512, ., false>: two per CU)
-        for (int per_cu = per_cu0; per_cu >= 1 && od.f_lds_bytes == 0; --per_cu)
+        // OSD-0: the layout for two workgroups per CU where the window allows it, else for one (the register budget of
+        // qd_osd0_reg_kernel<512, ., false> admits two per CU, no more)
+        for (int per_cu = 2; per_cu >= 1 && od.f_lds_bytes == 0; --per_cu)
             od.f_lds_bytes = lay(per_cu, false, od.f_off, od.f_off_sort, od.f_off_order, od.f_off_pivmask, od.f_off_npl, od.f_kw);
         od.w_lds_bytes = lay(1, true, od.w_off, od.w_off_sort, od.w_off_order, od.w_off_pivmask, od.w_off_npl, od.w_kw);
     }
@@ -896,10 +948,10 @@ extern "C" int qd_graph_create(int32_t m, int32_t n, const int32_t *row_ptr, con
         while ((1 << dl) < max_cdeg) ++dl;
         std::vector<uint16_t> ell((size_t)n << dl, (uint16_t)0xFFFFu);
         for (int j = 0; j < n; ++j)
-            for (int e = cp[j]; e < cp[j + 1]; ++e) ell[((size_t)j << dl) + (e - cp[j])] = (uint16_t)ri[e];
-        if (g->mem.upload(ell, &od.csc_ell)) { g->mem.release(); delete g; return fail(QD_EHIP, "device allocation/upload failed"); }
+            for (int e = h.cp[j]; e < h.cp[j + 1]; ++e) ell[((size_t)j << dl) + (e - h.cp[j])] = (uint16_t)h.ri[e];
+        if (g->mem.upload(ell, &od.csc_ell)) return fail(QD_EHIP, "device allocation/upload failed");
         od.ell_log2 = dl;
-        const int lds = qd_osd_sr_layout(m, m_pad, n, bp.out_words, od.s_off, &od.s_threads, &od.s_rpt);
+        const int lds = qd_osd_sr_layout(m, m_pad, n, out_words, od.s_off, &od.s_threads, &od.s_rpt);
         if (lds > 0 && lds <= QD_LDS_BYTES) {
             od.s_lds_bytes = lds;
             od.s_per_cu = std::max(1, std::min(QD_LDS_BYTES / lds, QD_SR_WPS_OF(od.s_rpt) * 256 / od.s_threads));   // the kernel's register budget (wavefronts per SIMD)
@@ -907,13 +959,27 @@ extern "C" int qd_graph_create(int32_t m, int32_t n, const int32_t *row_ptr, con
     }
     // the full kernel sorts all n columns in LDS; windows too large for that rely on the register kernel alone
     if (od.lds_bytes == 0 && od.f_lds_bytes == 0) od.threads = 0;
-    if (bp.lds_bytes > QD_LDS_BYTES) {
-        g->mem.release();
-        const int need_lds = bp.lds_bytes;
-        delete g;
-        return fail(QD_ECAPACITY, "window needs %d bytes of LDS for BP state; the CU has %d", need_lds, QD_LDS_BYTES);
-    }
-    *out = g;
+    return QD_OK;
+}
+
+extern "C" int qd_graph_create(int32_t m, int32_t n, const int32_t *row_ptr, const int32_t *col_idx,
+                               const double *priors, int32_t device, qd_graph **out)
+{
+    if (!out) return fail(QD_EINVAL, "out is null");
+    *out = nullptr;
+    HostGraph h;
+    if (int rc = host_graph(m, n, row_ptr, col_idx, priors, h)) return rc;
+    std::unique_ptr<qd_graph> g(new qd_graph());      // (~qd_graph frees what the builders uploaded)
+    g->device = device; g->m = m; g->n = n; g->nnz = h.nnz; g->max_rdeg = h.max_rdeg; g->max_cdeg = h.max_cdeg;
+    if (hipSetDevice(device) != hipSuccess) return fail(QD_EHIP, "hipSetDevice(%d) failed", device);
+    const Switches env = read_switches();
+    const int form = scatter_form(h);
+    if (int rc = build_bp(g.get(), h, form != 0)) return rc;
+    if (int rc = build_gen(g.get(), h)) return rc;
+    if (int rc = build_scatter(g.get(), h, form, env)) return rc;
+    if (int rc = build_osd(g.get(), h)) return rc;
+    g->h_cp = h.cp; g->h_ri = h.ri; g->h_llr0 = h.llr0;
+    *out = g.release();
     return QD_OK;
 }
 
@@ -921,7 +987,6 @@ extern "C" void qd_graph_destroy(qd_graph *g)
 {
     if (!g) return;
     (void)hipSetDevice(g->device);
-    g->mem.release();
     delete g;
 }
 
@@ -1004,16 +1069,35 @@ extern "C" int qd_decoder_create(const qd_graph *g, const qd_params *p, qd_decod
     if (p->osd_method != QD_OSD_OFF && !lsd && g->osd.lds_bytes == 0 && g->osd.f_lds_bytes == 0)
         return fail(QD_ECAPACITY, "window %d x %d does not fit either OSD kernel's LDS layout", g->m, g->n);
     if (p->max_iter < 0 || p->ms_scaling_factor < 0) return fail(QD_EINVAL, "negative max_iter / ms_scaling_factor");
+    const Switches env = read_switches();
     qd_decoder *d = new qd_decoder();
-    d->g = g; d->prm = *p; d->lsd = lsd ? 1 : 0;
+    d->g = g; d->prm = *p;
     d->lsd_w = (lsd && p->osd_order > 0) ? (p->osd_method == QD_LSD_CS ? 1 : (p->osd_method == QD_LSD_E ? 2 : 0)) : 0;
-    d->general = (p->bp_method != QD_BP_MINIMUM_SUM || p->schedule != QD_SCHEDULE_PARALLEL || (p->reserved & QD_FLAG_EDGE_MESSAGES)) ? 1 : 0;
-    d->lds_edge = (d->general && p->bp_method == QD_BP_PRODUCT_SUM && p->schedule == QD_SCHEDULE_PARALLEL && !std::getenv("QD_NO_LDS_EDGE") &&
-                   qd_bp_ps_lds_bytes(g->gen, g->max_rdeg) > 0) ? 1 : 0;
     d->osd_w = osd0 || p->osd_method == QD_OSD_OFF ? 0 : (p->osd_method == QD_OSD_CS ? 1 : 2);
     if (d->osd_w) host_rank(const_cast<qd_graph *>(g));     // the sweep needs the complete factorisation: rank pivots
     if (d->prm.max_iter == 0) d->prm.max_iter = g->n;       // ldpc: max_iter = 0 -> number of bits
     if (d->prm.max_iter > QD_STATUS_ITER_MASK) d->prm.max_iter = QD_STATUS_ITER_MASK;
+    // ---- the post-processor
+    if (p->osd_method == QD_OSD_OFF) d->post = QD_POST_NONE;
+    else if (lsd) d->post = QD_POST_LSD;
+    else if (d->osd_w) {
+        // higher-order OSD: the panel kernel (osd_cs.hip) wherever its layout takes the window, else the row form (osd_kernels.hip)
+        if (g->osd.csc_ell && !env.osdcs_old)
+            d->cs_lds = qd_osdcs_layout(g->m, g->n, g->bp.out_words, g->osd.max_wfix, d->cs_off, &d->cs_variant, &d->cs_per_cu);
+        d->post = d->cs_lds > 0 ? QD_POST_OSD_CS_PANEL : QD_POST_OSD_W_OLD;
+    } else
+        d->post = g->osd.s_lds_bytes > 0 ? QD_POST_OSD0_SR : QD_POST_OSD0_REG;
+    // ---- the BP kernel: one message per edge for every method / schedule but flooding min-sum (and for that one with QD_FLAG_EDGE_MESSAGES),
+    // the gather kernel for it off the LLR grid, the gather or a scatter kernel on the grid (below)
+    const bool edge = p->bp_method != QD_BP_MINIMUM_SUM || p->schedule != QD_SCHEDULE_PARALLEL || (p->reserved & QD_FLAG_EDGE_MESSAGES);
+    if (edge)
+        d->bp = (p->bp_method == QD_BP_PRODUCT_SUM && p->schedule == QD_SCHEDULE_PARALLEL && qd_bp_ps_lds_bytes(g->gen, g->max_rdeg) > 0) ? BP_LDS_EDGE : BP_HBM_EDGE;
+    if (d->bp == BP_HBM_EDGE && p->schedule == QD_SCHEDULE_SERIAL) {
+        // the serial schedule in several launches with the survivors packed in between (GenStage), at the bounds that leave two iterations or more
+        int prev = 0;
+        for (int b : env.gen_stages)
+            if (b > prev && b + 2 <= d->prm.max_iter && d->gen_nbounds < QD_GEN_MAX_STAGES - 1) { d->gen_bounds[d->gen_nbounds++] = b; prev = b; }
+    }
     d->bp_fine = g->bp; d->bp_coarse = g->bp; d->llr0_q = g->gen.llr0;
     if (p->bp_method == QD_BP_MINIMUM_SUM && p->schedule == QD_SCHEDULE_PARALLEL && p->ms_scaling_factor == 1.0 &&
         !(p->reserved & QD_FLAG_RAW_LLR)) {
@@ -1046,7 +1130,8 @@ extern "C" int qd_decoder_create(const qd_graph *g, const qd_params *p, qd_decod
         std::vector<float> lq(g->n);
         for (int j = 0; j < g->n; ++j) lq[j] = on_grid(g->h_llr0[j], d->grid_k);
         rc |= d->mem.upload(lq, &d->llr0_q);
-        if (g->sc.ok && !std::getenv("QD_NO_SCATTER")) {
+        if (!edge) d->bp = BP_GATHER_GRID;
+        if (!edge && g->sc.ok && !env.no_scatter) {
             // scatter kernel: fine-grid priors of the bit slots as integers (grid units) and the second-minimum bound that
             // certifies a run (bp_scatter.hip): max|prior| + max_cdeg * max min2 < 2^23
             std::vector<int32_t> pg((size_t)g->sc.nslots, 0);      // (unused and trash slots: 0)
@@ -1059,9 +1144,8 @@ extern "C" int qd_decoder_create(const qd_graph *g, const qd_params *p, qd_decod
             const long long lim = ((1ll << 23) - mxp) / std::max(1, g->max_cdeg) - 1;
             if (mxp < (1ll << 22) && lim > 0) {
                 rc |= d->mem.upload(pg, &d->prior_g);
-                d->m2_limit = (float)lim;
-                if (const char *ev = std::getenv("QD_SCATTER_M2_LIMIT")) d->m2_limit = std::min(d->m2_limit, (float)std::atof(ev));   // test knob: force the recheck pass
-                d->scatter = 1;
+                d->m2_limit = std::min((float)lim, env.scatter_m2_limit);     // (QD_SCATTER_M2_LIMIT: tests force the recheck pass)
+                d->bp = g->sc.wide_threads ? BP_SCATTER_WIDE : BP_SCATTER;
             }
         }
         if (rc) { d->mem.release(); delete d; return fail(QD_EHIP, "device allocation failed while building the LLR grid"); }
@@ -1073,74 +1157,27 @@ extern "C" int qd_decoder_create(const qd_graph *g, const qd_params *p, qd_decod
 extern "C" int qd_decoder_info(const qd_decoder *d, int32_t *info)
 {
     if (!d || !info) return fail(QD_EINVAL, "null argument");
-    info[0] = d->grid_k; info[1] = d->grid_kc; info[2] = d->general; info[3] = d->scatter ? (d->g->sc.wide_threads ? 2 : 1) : 0;
+    info[0] = d->grid_k; info[1] = d->grid_kc; info[2] = d->bp == BP_LDS_EDGE || d->bp == BP_HBM_EDGE;
+    info[3] = d->bp == BP_SCATTER_WIDE ? 2 : (d->bp == BP_SCATTER ? 1 : 0);
     return QD_OK;
 }
 
-extern "C" int qd_decoder_postproc_kernel(const qd_decoder *d)
-{
-    if (!d) return -1;
-    if (d->prm.osd_method == QD_OSD_OFF) return QD_POST_NONE;
-    if (d->lsd) return QD_POST_LSD;
-    if (d->osd_w) {
-        // (the same decision qd_decoder_reserve takes when it sizes the workspace)
-        const char *ev = std::getenv("QD_OSDCS_OLD");
-        int off[16], var = 0, per = 0;
-        if (d->g->osd.csc_ell && !(ev && std::atoi(ev) == 1) &&
-            qd_osdcs_layout(d->g->m, d->g->n, d->g->bp.out_words, d->g->osd.max_wfix, off, &var, &per) > 0) return QD_POST_OSD_CS_PANEL;
-        return QD_POST_OSD_W_OLD;
-    }
-    const char *ev = std::getenv("QD_NO_OSD_SR");
-    if (d->g->osd.s_lds_bytes > 0 && !(ev && std::atoi(ev) == 1)) return QD_POST_OSD0_SR;
-    return QD_POST_OSD0_REG;
-}
+extern "C" int qd_decoder_postproc_kernel(const qd_decoder *d) { return d ? d->post : -1; }
 
 static void free_ws(qd_decoder *d)
 {
-    if (d->llr_ws) (void)hipFree(d->llr_ws);
-    if (d->fail_list) (void)hipFree(d->fail_list);
-    if (d->ctr_base) (void)hipFree(d->ctr_base);
-    d->ctr_base = nullptr;
-    if (d->host_fail) (void)hipHostFree(d->host_fail);
-    if (d->fail_ready) (void)hipEventDestroy(d->fail_ready);
-    d->host_fail = nullptr; d->fail_ready = nullptr; d->fail_pending = false;
-    if (d->order_ws) (void)hipFree(d->order_ws);
-    if (d->q_spill) (void)hipFree(d->q_spill);
-    if (d->q_spill_fast) (void)hipFree(d->q_spill_fast);
-    d->q_spill_fast = nullptr;
-    if (d->q_spill_sr) (void)hipFree(d->q_spill_sr);
-    d->q_spill_sr = nullptr;
-    if (d->mt_ws) (void)hipFree(d->mt_ws);
-    d->mt_ws = nullptr;
-    if (d->cs_ws) (void)hipFree(d->cs_ws);
-    d->cs_ws = nullptr; d->osd_blocks_cs = 0;
-    if (d->gws.b2c) (void)hipFree(d->gws.b2c);
-    if (d->gws.c2b) (void)hipFree(d->gws.c2b);
-    if (d->gws.th) (void)hipFree(d->gws.th);
-    if (d->gws.pre) (void)hipFree(d->gws.pre);
-    if (d->gws.llr) (void)hipFree(d->gws.llr);
-    if (d->gws.syn) (void)hipFree(d->gws.syn);
-    if (d->gws.slot) (void)hipFree(d->gws.slot);
-    d->gws = GenWs{};
-    if (d->gsp.msg2) (void)hipFree(d->gsp.msg2);
-    if (d->gsp.syn2) (void)hipFree(d->gsp.syn2);
-    if (d->gsp.host_counts) (void)hipHostFree(d->gsp.host_counts);
-    if (d->gsp.counts_ready) (void)hipEventDestroy(d->gsp.counts_ready);
-    if (d->gsp.lists[0]) (void)hipFree(d->gsp.lists[0]);
-    if (d->gsp.lists[1]) (void)hipFree(d->gsp.lists[1]);
-    if (d->gsp.counts) (void)hipFree(d->gsp.counts);
-    d->gsp = GenStagePlan{};
-    if (d->hard_list) (void)hipFree(d->hard_list);
-    if (d->hard_list2) (void)hipFree(d->hard_list2);
-    if (d->redo_list) (void)hipFree(d->redo_list);
-    if (d->recheck_list) (void)hipFree(d->recheck_list);
-    d->recheck_list = nullptr; d->recheck_cap = 0;
-    if (d->lsd_ws) (void)hipFree(d->lsd_ws);
-    d->lsd_ws = nullptr;
-    d->redo_list = nullptr; d->redo_cap = 0;
-    d->hard_list = nullptr; d->hard_list2 = nullptr;
-    d->llr_ws = nullptr; d->fail_list = nullptr; d->fail_count = nullptr; d->order_ws = nullptr; d->q_spill = nullptr;
-    d->cap = 0;
+    auto dev = [](auto *&p) { if (p) (void)hipFree(p); p = nullptr; };
+    auto host = [](auto *&p) { if (p) (void)hipHostFree(p); p = nullptr; };
+    auto event = [](hipEvent_t &e) { if (e) (void)hipEventDestroy(e); e = nullptr; };
+    dev(d->llr_ws); dev(d->fail_list); dev(d->ctr_base); dev(d->order_ws); dev(d->q_spill); dev(d->q_spill_fast); dev(d->q_spill_sr);
+    dev(d->mt_ws); dev(d->cs_ws); dev(d->hard_list); dev(d->hard_list2); dev(d->redo_list); dev(d->recheck_list); dev(d->lsd_ws);
+    dev(d->gws.b2c); dev(d->gws.c2b); dev(d->gws.th); dev(d->gws.pre); dev(d->gws.llr); dev(d->gws.syn); dev(d->gws.slot);
+    dev(d->gsp.msg2); dev(d->gsp.syn2); dev(d->gsp.lists[0]); dev(d->gsp.lists[1]); dev(d->gsp.counts);
+    host(d->host_fail); host(d->gsp.host_counts);
+    event(d->fail_ready); event(d->gsp.counts_ready);
+    d->gws = GenWs{}; d->gsp = GenStagePlan{};
+    d->fail_count = nullptr; d->fail_pending = false;
+    d->post_blocks = d->redo_cap = d->recheck_cap = 0; d->cap = 0;
 }
 
 extern "C" void qd_decoder_destroy(qd_decoder *d)
@@ -1161,21 +1198,20 @@ extern "C" int qd_decoder_reserve(qd_decoder *d, int64_t max_batch)
     HIP_TRY(hipDeviceSynchronize());
     free_ws(d);
     const qd_graph *g = d->g;
-    const bool osd = d->prm.osd_method != QD_OSD_OFF;
     HIP_TRY(hipMalloc((void **)&d->ctr_base, 512));
     HIP_TRY(hipMemset(d->ctr_base, 0, 512));
-    d->fail_count = d->ctr_base; d->cset = 0; d->set_clean[0] = d->set_clean[1] = true;
+    d->fail_count = d->ctr_base; d->cset = 0; d->set_clean[0] = d->set_clean[1] = false;     // (see qd_decoder::ctr_base)
     HIP_TRY(hipHostMalloc((void **)&d->host_fail, 2 * sizeof(int32_t)));
     HIP_TRY(hipEventCreateWithFlags(&d->fail_ready, hipEventDisableTiming));
-    if (d->grid_k >= 0 && !d->general) {
+    if (d->bp == BP_SCATTER_WIDE || d->bp == BP_SCATTER || d->bp == BP_GATHER_GRID) {
         d->redo_cap = (int)(d->grid_floor ? max_batch : std::min<int64_t>(max_batch, 4096));
         HIP_TRY(hipMalloc((void **)&d->redo_list, sizeof(int32_t) * (size_t)d->redo_cap));
-        if (d->scatter) {
+        if (d->bp != BP_GATHER_GRID) {
             d->recheck_cap = (int)max_batch;
             HIP_TRY(hipMalloc((void **)&d->recheck_list, sizeof(int32_t) * (size_t)d->recheck_cap));
         }
     }
-    if (osd) {
+    if (d->post != QD_POST_NONE) {
         int ncu = 256;
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, g->device) == hipSuccess && prop.multiProcessorCount > 0) ncu = prop.multiProcessorCount;
@@ -1183,42 +1219,18 @@ extern "C" int qd_decoder_reserve(qd_decoder *d, int64_t max_batch)
         d->osd_blocks = g->osd.lds_bytes > 0 ? ncu * std::min(per_cu, 2048 / std::max(1, g->osd.threads)) : 0;
         const int per_cu_fast = std::max(1, QD_LDS_BYTES / std::max(1, g->osd.f_lds_bytes));
         d->osd_blocks_fast = ncu * std::min(per_cu_fast, 2048 / std::max(1, g->osd.f_threads));
-        if (const char *ev = std::getenv("QD_OSD_BLOCKS_PER_CU")) {       // tuning knob
-            const int v = std::atoi(ev);
-            if (v > 0) d->osd_blocks_fast = ncu * v;
-        }
         if (d->osd_w) d->osd_blocks_fast = ncu;                                   // higher-order OSD by row: w_* layout, one workgroup per CU
-        if (d->lsd) {
+        if (d->post == QD_POST_LSD) {
             const int lds = qd_lsd_lds_bytes(g->m, g->n, g->bp.out_words);
-            d->lsd_blocks = ncu * std::max(1, std::min(8, QD_LDS_BYTES / std::max(1, lds)));     // one wavefront per shot, several shots per CU
-            d->lsd_ws = nullptr;
-            HIP_TRY(hipMalloc((void **)&d->lsd_ws, qd_lsd_ws_bytes(g->m, g->n, d->lsd_blocks, d->lsd_w)));   // Q planes + work counter (+ debug timers) + pivot columns (+ sweep scratch)
-        }
-        d->osd_blocks_sr = 0;
-        {
-            const char *ev = std::getenv("QD_NO_OSD_SR");
-            if (!d->osd_w && !d->lsd && g->osd.s_lds_bytes > 0 && !(ev && std::atoi(ev) == 1)) {
-                int per = g->osd.s_per_cu;
-                if (const char *e2 = std::getenv("QD_OSD_SR_PER_CU")) { const int v = std::atoi(e2); if (v > 0) per = std::min(v, QD_LDS_BYTES / g->osd.s_lds_bytes); }
-                d->osd_blocks_sr = ncu * per;
-                HIP_TRY(hipMalloc((void **)&d->q_spill_sr, sizeof(uint64_t) * (size_t)d->osd_blocks_sr *
-                                                           qd_osd_sr_ws_words(g->osd.m_pad, g->osd.mw, g->osd.s_threads, g->osd.s_rpt)));
-            }
-        }
-        d->osd_blocks_cs = 0;
-        {
-            // higher-order OSD: the rebuilt column-form kernel (osd_cs.hip) wherever its layout takes the window; QD_OSDCS_OLD=1 keeps
-            // the row form (osd_kernels.hip) for A/B runs
-            const char *ev = std::getenv("QD_OSDCS_OLD");
-            if (d->osd_w && !d->lsd && g->osd.csc_ell && !(ev && std::atoi(ev) == 1)) {
-                int per = 0;
-                d->cs_lds = qd_osdcs_layout(g->m, g->n, g->bp.out_words, g->osd.max_wfix, d->cs_off, &d->cs_variant, &per);
-                if (d->cs_lds > 0) {
-                    if (const char *e2 = std::getenv("QD_OSDCS_PER_CU")) { const int v = std::atoi(e2); if (v > 0) per = std::min(v, QD_LDS_BYTES / d->cs_lds); }
-                    d->osd_blocks_cs = ncu * per;
-                    HIP_TRY(hipMalloc((void **)&d->cs_ws, sizeof(uint64_t) * (size_t)d->osd_blocks_cs * qd_osdcs_ws_words(d->cs_variant)));
-                }
-            }
+            d->post_blocks = ncu * std::max(1, std::min(8, QD_LDS_BYTES / std::max(1, lds)));     // one wavefront per shot, several shots per CU
+            HIP_TRY(hipMalloc((void **)&d->lsd_ws, qd_lsd_ws_bytes(g->m, g->n, d->post_blocks, d->lsd_w)));   // Q planes + work counter (+ debug timers) + pivot columns (+ sweep scratch)
+        } else if (d->post == QD_POST_OSD0_SR) {
+            d->post_blocks = ncu * g->osd.s_per_cu;
+            HIP_TRY(hipMalloc((void **)&d->q_spill_sr, sizeof(uint64_t) * (size_t)d->post_blocks *
+                                                       qd_osd_sr_ws_words(g->osd.m_pad, g->osd.mw, g->osd.s_threads, g->osd.s_rpt)));
+        } else if (d->post == QD_POST_OSD_CS_PANEL) {
+            d->post_blocks = ncu * d->cs_per_cu;
+            HIP_TRY(hipMalloc((void **)&d->cs_ws, sizeof(uint64_t) * (size_t)d->post_blocks * qd_osdcs_ws_words(d->cs_variant)));
         }
         const int spill_fast = g->osd.mw - (d->osd_w ? g->osd.w_kw : g->osd.f_kw);
         if (g->osd.f_lds_bytes > 0 && spill_fast > 0)
@@ -1235,33 +1247,17 @@ extern "C" int qd_decoder_reserve(qd_decoder *d, int64_t max_batch)
         if (d->osd_blocks > 0 && spill_planes > 0)
             HIP_TRY(hipMalloc((void **)&d->q_spill, sizeof(uint64_t) * (size_t)d->osd_blocks * spill_planes * g->osd.m_pad));
     }
-    if (d->general && !d->lds_edge) {
+    if (d->bp == BP_HBM_EDGE) {
         // [index][shot] message planes for a chunk of S shots; a batch larger than S is decoded chunk by chunk
         const bool ps = d->prm.bp_method == QD_BP_PRODUCT_SUM, serial = d->prm.schedule == QD_SCHEDULE_SERIAL;
         // edge planes: flooding b2c + c2b (+ th for product-sum); serial: messages (th or b2c) + suffixes (the c2b plane), and a row plane
         const int planes = serial ? 2 : (ps ? 3 : 2);
         const bool pre_plane = serial && g->gen.nslots == 0;       // the rows' running prefixes: LDS slots when the graph allows
-        // Serial schedule in several launches with the survivors packed in between (GenStage): bounds after iterations 3, 6, 10, 14, 20, ...
-        // (x ~1.4) while at least two iterations remain; QD_GEN_STAGES="3,6" sets them, QD_GEN_STAGES=0 = one launch.  Costs a second workspace.
+        // Serial schedule in several launches (qd_decoder_create chose the bounds): costs a second workspace.
         GenStagePlan &sp = d->gsp;
         sp = GenStagePlan{};
-        if (serial) {
-            static const int dflt[] = {3, 6, 10, 14, 20, 28, 40, 56, 80, 112};     // (max_iter 10: "3,6" 50.5 ms, "3,5,7" 51.4, "4" 51.4, one launch 56.0: profiles/r06_k1g_staged_ab.txt)
-            std::vector<int> bnd(dflt, dflt + sizeof(dflt) / sizeof(dflt[0]));
-            if (const char *ev = std::getenv("QD_GEN_STAGES")) {
-                bnd.clear();
-                for (const char *q = ev; *q;) {
-                    char *end = nullptr;
-                    const long v = std::strtol(q, &end, 10);
-                    if (end == q) break;
-                    if (v > 0) bnd.push_back((int)v);
-                    q = *end ? end + 1 : end;
-                }
-            }
-            int prev = 0;
-            for (int b : bnd)
-                if (b > prev && b + 2 <= d->prm.max_iter && sp.nbounds < QD_GEN_MAX_STAGES - 1) { sp.bounds[sp.nbounds++] = b; prev = b; }
-        }
+        sp.nbounds = d->gen_nbounds;
+        std::copy(d->gen_bounds, d->gen_bounds + d->gen_nbounds, sp.bounds);
         // (the launches alternate between two message planes and two syndrome planes; suffixes, prefixes, posteriors and fail slots are scratch of
         //  ONE launch and shared.  If the second message plane would push the batch into more workspace chunks, the schedule stays in one launch:
         //  a chunk more costs a whole dependency chain, more than packing returns -- W = 3 windows, ten decoders in a 96 GB budget: 98 -> 128 ms)
@@ -1269,9 +1265,7 @@ extern "C" int qd_decoder_reserve(qd_decoder *d, int64_t max_batch)
         size_t per_shot = per_shot1 + (sp.nbounds > 0 ? (size_t)g->nnz * sizeof(float) + g->m + 2 * sizeof(int32_t) : 0);
         // Default budget 48 GB of the 288: the kernel is latency-bound (one wavefront per 64 shots), so a launch costs about
         // the same for 8 K or 64 K shots and chunks should be as large as memory allows -- and of equal size.
-        double budget_gb = 48.0;
-        if (const char *ev = std::getenv("QD_GENERAL_WS_GB")) budget_gb = std::max(0.001, std::atof(ev));
-        if (d->gen_ws_limit > 0) budget_gb = (double)d->gen_ws_limit / 1073741824.0;
+        const double budget_gb = d->gen_ws_limit > 0 ? (double)d->gen_ws_limit / 1073741824.0 : 48.0;
         const auto chunks_for = [&](size_t ps) { const int64_t s_ = std::max<int64_t>(256, (int64_t)(budget_gb * 1073741824.0 / (double)ps) & ~(int64_t)255); return (max_batch + s_ - 1) / s_; };
         if (sp.nbounds > 0 && chunks_for(per_shot) > chunks_for(per_shot1)) { sp.nbounds = 0; per_shot = per_shot1; }
         int64_t S = (int64_t)(budget_gb * 1073741824.0 / (double)per_shot) & ~(int64_t)255;
@@ -1308,7 +1302,7 @@ extern "C" int qd_decoder_set_workspace_limit(qd_decoder *d, int64_t bytes)
 {
     if (!d || bytes <= 0) return fail(QD_EINVAL, "bad workspace limit");
     d->gen_ws_limit = bytes;
-    if (d->general && d->cap > 0) {          // takes effect at the next reserve: drop what is there
+    if (d->bp == BP_HBM_EDGE && d->cap > 0) {          // takes effect at the next reserve: drop what is there
         HIP_TRY(hipSetDevice(d->g->device));
         HIP_TRY(hipDeviceSynchronize());
         free_ws(d);
@@ -1349,119 +1343,151 @@ extern "C" int qd_decoder_profile(qd_decoder *d, double *out, int32_t reset)
     return QD_OK;
 }
 
-static int decode_impl(qd_decoder *d, const uint8_t *d_det, int64_t det_stride, int64_t det_offset, const uint8_t *d_upd,
-                       int64_t upd_stride, int32_t upd_rows, int64_t B, uint32_t *d_err_bits, int32_t *d_status, int stage,
-                       void *stream)
+// The batch arguments of qd_decode_batch / qd_decode_stage / qd_osd0_batch (B = 0 is valid and decodes nothing)
+static int check_batch(const qd_decoder *d, int64_t det_stride, int64_t det_offset, const uint8_t *d_upd, int64_t upd_stride, int32_t upd_rows, int64_t B)
 {
-    if (!d || !d_det || !d_err_bits || !d_status) return fail(QD_EINVAL, "null argument");
-    if (stage < 1 || stage > 3) return fail(QD_EINVAL, "stage must be 1 (BP), 2 (OSD) or 3 (both)");
     if (B < 0 || B > 0x7FFFFFFF) return fail(QD_EINVAL, "batch size out of range");
     if (B == 0) return QD_OK;
     if (det_offset < 0 || det_stride < det_offset + d->g->m) return fail(QD_EINVAL, "detector slice [%lld, %lld) exceeds the row stride %lld", (long long)det_offset, (long long)(det_offset + d->g->m), (long long)det_stride);
     if (d_upd && (upd_rows < 0 || upd_rows > d->g->m || upd_stride < upd_rows)) return fail(QD_EINVAL, "bad syndrome-update shape");
-    HIP_TRY(hipSetDevice(d->g->device));
-    if (B > d->cap) {
-        if (stage == 2) return fail(QD_EINVAL, "OSD stage without a preceding BP stage of this batch size");
-        int rc = qd_decoder_reserve(d, B);
-        if (rc) return rc;
-    }
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const bool osd = d->prm.osd_method != QD_OSD_OFF;
-    if (stage & 1) {                                     // a new call: the other counter set (see qd_decoder::ctr_base)
-        d->cset ^= 1;
-        d->fail_count = d->ctr_base + 64 * d->cset;
-        if (!d->set_clean[d->cset] || std::getenv("QD_COUNTER_FILLS")) {
-            HIP_TRY(hipMemsetAsync(d->fail_count, 0, 3 * sizeof(int32_t), s));
-            HIP_TRY(hipMemsetAsync(d->fail_count + 40, 0, 2 * sizeof(int32_t), s));
-        }
-        d->set_clean[d->cset] = false;
-        d->last_B = B;
-    }
+    return QD_OK;
+}
+
+// The kernels' arguments for one call: the caller's buffers and the decoder's workspace, with the counter set of the call in flight
+static DecodeArgs decode_args(const qd_decoder *d, const uint8_t *d_det, int64_t det_stride, int64_t det_offset, const uint8_t *d_upd,
+                              int64_t upd_stride, int32_t upd_rows, uint32_t *d_err_bits, int32_t *d_status)
+{
     DecodeArgs a{};
     a.det = d_det; a.det_stride = det_stride; a.det_offset = det_offset;
     a.upd = d_upd; a.upd_stride = upd_stride; a.upd_rows = d_upd ? upd_rows : 0;
-    a.max_iter = d->prm.max_iter; a.ms_scale = (float)d->prm.ms_scaling_factor; a.want_llr = osd ? 1 : 0;
+    a.max_iter = d->prm.max_iter; a.ms_scale = (float)d->prm.ms_scaling_factor; a.want_llr = d->post != QD_POST_NONE ? 1 : 0;
     a.err_bits = d_err_bits; a.status = d_status;
     a.llr_ws = d->llr_ws; a.fail_list = d->fail_list; a.fail_count = d->fail_count;
     a.order_ws = d->order_ws; a.q_spill = d->q_spill; a.q_spill_fast = d->q_spill_fast; a.q_spill_sr = d->q_spill_sr; a.mt_ws = d->mt_ws;
     a.hard_list = d->hard_list; a.hard_list2 = d->hard_list2; a.hard_count = d->fail_count + 1;
     a.dbg = reinterpret_cast<unsigned long long *>(d->ctr_base) + 2;   // bytes 16..143 of the counter block (first set, never zeroed by a call)
     a.osd_w = d->osd_w; a.osd_order = d->prm.osd_order; a.rank = d->g->rank;
-    auto span = [&](int kind, hipEvent_t &t0) -> int {
+    return a;
+}
+
+// Stage 1: BP over the batch
+static int launch_bp(qd_decoder *d, const DecodeArgs &a, int64_t B, hipStream_t s)
+{
+    const qd_graph *g = d->g;
+    GenGraphDev gg = g->gen;
+    gg.llr0 = d->llr0_q;
+    switch (d->bp) {
+    case BP_LDS_EDGE: HIP_TRY(qd_launch_bp_ps_lds(gg, g->bp, a, B, s)); break;
+    case BP_GATHER_RAW: HIP_TRY(qd_launch_bp(g->bp, a, B, s)); break;
+    case BP_HBM_EDGE:
+        for (int64_t b0 = 0; b0 < B; b0 += d->gws.S)
+            HIP_TRY(qd_launch_bp_general(gg, g->bp, a, d->gws, d->prm.bp_method, d->prm.schedule, b0,
+                                         (int)std::min<int64_t>(d->gws.S, B - b0), s, d->gsp.nbounds > 0 ? &d->gsp : nullptr));
+        break;
+    case BP_SCATTER_WIDE:
+    case BP_SCATTER:
+    case BP_GATHER_GRID: {
+        // grid arithmetic: first pass on the fine grid parks the shots whose exactness bound tripped; they are decoded
+        // again on the coarse grid by a second launch (one workgroup per parked shot; the others exit at once)
+        int32_t *redo_count = d->fail_count + 40;       // bytes 160..163 of the counter set (16..143 of the first set are the debug counters)
+        DecodeArgs a1 = a;
+        a1.s_limit = std::ldexp(1.0f, 23 - d->grid_k);
+        a1.redo_list = d->redo_list; a1.redo_count = redo_count; a1.redo_cap = d->redo_cap;
+        if (d->bp == BP_GATHER_GRID)
+            HIP_TRY(qd_launch_bp(d->bp_fine, a1, B, s));
+        else {
+            // scatter kernel first; the shots its (looser) bound cannot certify are decoded again by the gather kernel,
+            // which carries the per-fault bound the coarse-grid rule is stated on
+            int32_t *recheck_count = d->fail_count + 41;
+            ScatArgs x{};
+            x.prior_g = d->prior_g; x.grid_inv = std::ldexp(1.0f, -d->grid_k); x.m2_limit = d->m2_limit;
+            x.recheck_list = d->recheck_list; x.recheck_count = recheck_count; x.recheck_cap = d->recheck_cap;
+            if (d->bp == BP_SCATTER_WIDE) HIP_TRY(qd_launch_bp_scatter_wide(d->bp_fine, g->sc, a1, x, B, s));
+            else HIP_TRY(qd_launch_bp_scatter(d->bp_fine, g->sc, a1, x, B, s));
+            a1.shot_list = d->recheck_list; a1.shot_count = recheck_count;
+            HIP_TRY(qd_launch_bp(d->bp_fine, a1, std::min<int64_t>(B, d->recheck_cap), s));
+        }
+        DecodeArgs a2 = a;
+        a2.s_limit = std::ldexp(1.0f, 23 - d->grid_kc);
+        a2.shot_list = d->redo_list; a2.shot_count = redo_count; a2.status_or = QD_STATUS_COARSE_GRID;
+        HIP_TRY(qd_launch_bp(d->bp_coarse, a2, std::min<int64_t>(B, d->redo_cap), s));
+        break;
+    }
+    }
+    return QD_OK;
+}
+
+// Stage 2: the post-processor over the shots BP parked
+static int launch_post(const qd_decoder *d, const DecodeArgs &a, int64_t B, hipStream_t s)
+{
+    const qd_graph *g = d->g;
+    const int blocks = (int)std::min<int64_t>(B, d->post_blocks);
+    const int fast = (int)std::min<int64_t>(B, d->osd_blocks_fast), full = (int)std::min<int64_t>(B, d->osd_blocks);
+    switch (d->post) {
+    case QD_POST_LSD:
+        HIP_TRY(qd_launch_lsd0(g->gen, g->bp, a, d->lsd_ws, d->post_blocks, blocks, d->lsd_w, d->prm.osd_order, g->osd.wfix, s));
+        break;
+    case QD_POST_OSD_CS_PANEL:
+        HIP_TRY(qd_launch_osdcs(g->osd, g->bp, a, d->cs_off, d->cs_variant, d->cs_lds, d->cs_ws, blocks, s));
+        break;
+    case QD_POST_OSD0_SR:
+        // OSD-0: many pivots per round (osd_sr.hip); shots whose syndrome is outside the column space come back on the hard list
+        // and are decoded by the one-pivot-per-round kernel, whose lowest-row rule defines their answer
+        HIP_TRY(qd_launch_osd0_sr(g->osd, g->bp, a, blocks, s));
+        HIP_TRY(qd_launch_osd0(g->osd, g->bp, a, fast, full, s, true));
+        break;
+    default:                                            // QD_POST_OSD0_REG, QD_POST_OSD_W_OLD
+        HIP_TRY(qd_launch_osd0(g->osd, g->bp, a, fast, full, s));
+    }
+    return QD_OK;
+}
+
+static int decode_impl(qd_decoder *d, const uint8_t *d_det, int64_t det_stride, int64_t det_offset, const uint8_t *d_upd,
+                       int64_t upd_stride, int32_t upd_rows, int64_t B, uint32_t *d_err_bits, int32_t *d_status, int stage,
+                       void *stream)
+{
+    if (!d || !d_det || !d_err_bits || !d_status) return fail(QD_EINVAL, "null argument");
+    if (stage < 1 || stage > 3) return fail(QD_EINVAL, "stage must be 1 (BP), 2 (OSD) or 3 (both)");
+    if (int rc = check_batch(d, det_stride, det_offset, d_upd, upd_stride, upd_rows, B)) return rc;
+    if (B == 0) return QD_OK;
+    HIP_TRY(hipSetDevice(d->g->device));
+    if (B > d->cap && stage == 2) return fail(QD_EINVAL, "OSD stage without a preceding BP stage of this batch size");
+    if (int rc = B > d->cap ? qd_decoder_reserve(d, B) : QD_OK) return rc;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const bool post = d->post != QD_POST_NONE;
+    if (stage & 1) {                                     // a new call: the other counter set (see qd_decoder::ctr_base)
+        d->cset ^= 1;
+        d->fail_count = d->ctr_base + 64 * d->cset;
+        if (!d->set_clean[d->cset]) {
+            HIP_TRY(hipMemsetAsync(d->fail_count, 0, 3 * sizeof(int32_t), s));
+            HIP_TRY(hipMemsetAsync(d->fail_count + 40, 0, 2 * sizeof(int32_t), s));
+        }
+        d->set_clean[d->cset] = false;
+        d->last_B = B;
+    }
+    const DecodeArgs a = decode_args(d, d_det, det_stride, det_offset, d_upd, upd_stride, upd_rows, d_err_bits, d_status);
+    auto span = [&](int kind) -> int {
         if (!d->profiling) return QD_OK;
-        hipEvent_t t1;
+        hipEvent_t t0, t1;
         HIP_TRY(hipEventCreate(&t0)); HIP_TRY(hipEventCreate(&t1));
         d->ev.push_back({kind, t0, t1});
         HIP_TRY(hipEventRecord(t0, s));
         return QD_OK;
     };
     if (stage & 1) {
-        int32_t *redo_count = d->fail_count + 40;       // bytes 160..163 of the counter set (16..143 of the first set are the debug counters)
-        hipEvent_t t0 = nullptr;
-        if (int rc = span(0, t0)) return rc;
-        if (d->lds_edge) {
-            GenGraphDev gg = d->g->gen;
-            gg.llr0 = d->llr0_q;
-            HIP_TRY(qd_launch_bp_ps_lds(gg, d->g->bp, a, B, s));
-        } else if (d->general) {
-            GenGraphDev gg = d->g->gen;
-            gg.llr0 = d->llr0_q;
-            for (int64_t b0 = 0; b0 < B; b0 += d->gws.S)
-                HIP_TRY(qd_launch_bp_general(gg, d->g->bp, a, d->gws, d->prm.bp_method, d->prm.schedule, b0,
-                                             (int)std::min<int64_t>(d->gws.S, B - b0), s, d->gsp.nbounds > 0 ? &d->gsp : nullptr));
-        } else if (d->grid_k >= 0) {
-            // grid arithmetic: first pass on the fine grid parks the shots whose exactness bound tripped; they are decoded
-            // again on the coarse grid by a second launch (one workgroup per parked shot; the others exit at once)
-            DecodeArgs a1 = a;
-            a1.s_limit = std::ldexp(1.0f, 23 - d->grid_k);
-            a1.redo_list = d->redo_list; a1.redo_count = redo_count; a1.redo_cap = d->redo_cap;
-            if (d->scatter) {
-                // scatter kernel first; the shots its (looser) bound cannot certify are decoded again by the gather kernel,
-                // which carries the per-fault bound the coarse-grid rule is stated on
-                int32_t *recheck_count = d->fail_count + 41;
-                ScatArgs x{};
-                x.prior_g = d->prior_g; x.grid_inv = std::ldexp(1.0f, -d->grid_k); x.m2_limit = d->m2_limit;
-                x.recheck_list = d->recheck_list; x.recheck_count = recheck_count; x.recheck_cap = d->recheck_cap;
-                if (d->g->sc.wide_threads) HIP_TRY(qd_launch_bp_scatter_wide(d->bp_fine, d->g->sc, a1, x, B, s));
-                else HIP_TRY(qd_launch_bp_scatter(d->bp_fine, d->g->sc, a1, x, B, s));
-                a1.shot_list = d->recheck_list; a1.shot_count = recheck_count;
-                HIP_TRY(qd_launch_bp(d->bp_fine, a1, std::min<int64_t>(B, d->recheck_cap), s));
-            } else
-                HIP_TRY(qd_launch_bp(d->bp_fine, a1, B, s));
-            DecodeArgs a2 = a;
-            a2.s_limit = std::ldexp(1.0f, 23 - d->grid_kc);
-            a2.shot_list = d->redo_list; a2.shot_count = redo_count; a2.status_or = QD_STATUS_COARSE_GRID;
-            HIP_TRY(qd_launch_bp(d->bp_coarse, a2, std::min<int64_t>(B, d->redo_cap), s));
-        } else
-            HIP_TRY(qd_launch_bp(d->g->bp, a, B, s));
+        if (int rc = span(0)) return rc;
+        if (int rc = launch_bp(d, a, B, s)) return rc;
         if (d->profiling) HIP_TRY(hipEventRecord(d->ev.back().t1, s));
-        if (std::getenv("QD_DEBUG_SYNC")) { std::fprintf(stderr, "[qd] BP stage queued (B = %lld)\n", (long long)B); HIP_TRY(hipStreamSynchronize(s)); std::fprintf(stderr, "[qd] BP stage done\n"); }
     }
-    if ((stage & 2) && osd) {
-        hipEvent_t t0 = nullptr;
-        if (int rc = span(1, t0)) return rc;
-        if (d->lsd)
-            HIP_TRY(qd_launch_lsd0(d->g->gen, d->g->bp, a, d->lsd_ws, d->lsd_blocks, (int)std::min<int64_t>(B, d->lsd_blocks), d->lsd_w,
-                                   d->prm.osd_order, d->g->osd.wfix, s));
-        else if (d->osd_blocks_cs > 0)
-            HIP_TRY(qd_launch_osdcs(d->g->osd, d->g->bp, a, d->cs_off, d->cs_variant, d->cs_lds, d->cs_ws,
-                                    (int)std::min<int64_t>(B, d->osd_blocks_cs), s));
-        else if (d->osd_blocks_sr > 0) {
-            // OSD-0: many pivots per round (osd_sr.hip); shots whose syndrome is outside the column space come back on the hard list
-            // and are decoded by the one-pivot-per-round kernel, whose lowest-row rule defines their answer
-            HIP_TRY(qd_launch_osd0_sr(d->g->osd, d->g->bp, a, (int)std::min<int64_t>(B, d->osd_blocks_sr), s));
-            HIP_TRY(qd_launch_osd0(d->g->osd, d->g->bp, a, (int)std::min<int64_t>(B, d->osd_blocks_fast),
-                                   (int)std::min<int64_t>(B, d->osd_blocks), s, true));
-        } else
-            HIP_TRY(qd_launch_osd0(d->g->osd, d->g->bp, a, (int)std::min<int64_t>(B, d->osd_blocks_fast),
-                                   (int)std::min<int64_t>(B, d->osd_blocks), s));
+    if ((stage & 2) && post) {
+        if (int rc = span(1)) return rc;
+        if (int rc = launch_post(d, a, B, s)) return rc;
         if (d->profiling) HIP_TRY(hipEventRecord(d->ev.back().t1, s));
-        if (std::getenv("QD_DEBUG_SYNC")) { std::fprintf(stderr, "[qd] post-processing stage queued (B = %lld)\n", (long long)B); HIP_TRY(hipStreamSynchronize(s)); std::fprintf(stderr, "[qd] post-processing stage done\n"); }
-    }
-    if ((stage & 2) && osd && !d->fail_pending && d->host_fail) {      // (see qd_decoder::host_fail)
-        HIP_TRY(hipMemcpyAsync(d->host_fail, d->fail_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipEventRecord(d->fail_ready, s));
-        d->fail_pending = true; d->fail_pending_B = d->last_B;
+        if (!d->fail_pending && d->host_fail) {          // (see qd_decoder::host_fail)
+            HIP_TRY(hipMemcpyAsync(d->host_fail, d->fail_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipEventRecord(d->fail_ready, s));
+            d->fail_pending = true; d->fail_pending_B = d->last_B;
+        }
     }
     if ((stage & 2) && !d->set_clean[d->cset ^ 1]) {     // the next call's counters, zeroed behind this call's last stage (nothing waits for these fills)
         int32_t *other = d->ctr_base + 64 * (d->cset ^ 1);
@@ -1473,7 +1499,7 @@ static int decode_impl(qd_decoder *d, const uint8_t *d_det, int64_t det_stride, 
 }
 
 // See include/quits_amd.h.  Heavy = the post-processor will want whole CUs for about as long as a BP stage or longer: OSD-CS / OSD-E (two workgroups of
-// 78 KB of LDS per CU), BP-LSD, and OSD-0 when at least QD_POST_HEAD_FRAC (0.75) of the batch failed (headline p = 3e-3: 48 %, p = 5e-3: 95 %).  Measured, same box, 30 us
+// 78 KB of LDS per CU), BP-LSD, and OSD-0 when at least three quarters of the batch failed (headline p = 3e-3: 48 %, p = 5e-3: 95 %).  Measured, same box, 30 us
 // against none: OSD-CS(1) 361 -> 482 k shots/s, lsd_cs(1) 888 -> 940 k, p = 6e-3 488 -> 569 k, W = 5 / F = 3 1.125 -> 1.153 M; the headline (OSD-0 over
 // 48 % of the shots, 4.4 ms beside 40 ms of BP) is the one that loses, 1.552 -> 1.539 M -- even to an EMPTY launch at this point of the BP stream, so an
 // OSD-0 decoder launches nothing unless an earlier call's failure count (qd_decoder::host_fail) says "heavy" (profiles/r06_post_head_start.txt).
@@ -1481,18 +1507,15 @@ extern "C" int qd_decoder_post_head_start(qd_decoder *d, int32_t microseconds, v
 {
     if (!d) return fail(QD_EINVAL, "null decoder");
     if (microseconds < 0) microseconds = 50;
-    if (const char *ev = std::getenv("QD_POST_HEAD_START_US")) microseconds = std::atoi(ev);
-    if (microseconds <= 0 || d->prm.osd_method == QD_OSD_OFF || !d->ctr_base || d->last_B <= 0) return QD_OK;
+    if (microseconds <= 0 || d->post == QD_POST_NONE || !d->ctr_base || d->last_B <= 0) return QD_OK;
     microseconds = std::min(microseconds, 5000);
     HIP_TRY(hipSetDevice(d->g->device));
-    const bool always = d->lsd || d->osd_blocks_cs > 0;
-    double frac = 0.75;
-    if (const char *ev = std::getenv("QD_POST_HEAD_FRAC")) frac = std::atof(ev);
+    const bool always = d->post == QD_POST_LSD || d->post == QD_POST_OSD_CS_PANEL;
+    const double frac = 0.75;
     if (d->fail_pending && qd_event_done(d->fail_ready)) {
         d->fail_pending = false;
         if (d->fail_pending_B > 0) d->fail_frac_hint = (double)d->host_fail[0] / (double)d->fail_pending_B;
     }
-    if (std::getenv("QD_DEBUG_HEAD")) std::fprintf(stderr, "[qd] head start: decoder %p always %d hint %.3f host_fail %d pending_B %lld last_B %lld\n", (void *)d, (int)always, d->fail_frac_hint, d->host_fail ? d->host_fail[0] : -1, (long long)d->fail_pending_B, (long long)d->last_B);
     if (!always && d->fail_frac_hint < 0.8 * frac) return QD_OK;        // OSD-0 over a minority of the shots (or nothing known yet): no launch at all
     const int threshold = (int)std::min<double>(2147483647.0, std::max(1.0, frac * (double)d->last_B));
     HIP_TRY(qd_launch_hold(always ? nullptr : d->fail_count, threshold, microseconds, reinterpret_cast<hipStream_t>(stream)));
@@ -1518,46 +1541,18 @@ extern "C" int qd_osd0_batch(qd_decoder *d, const uint8_t *d_det, int64_t det_st
                              uint32_t *d_err_bits, int32_t *d_status, void *stream)
 {
     if (!d || !d_det || !d_llr || !d_err_bits || !d_status) return fail(QD_EINVAL, "null argument");
-    if (d->prm.osd_method == QD_OSD_OFF) return fail(QD_EINVAL, "decoder was created with osd_method = off");
-    const bool lsd_only = d->lsd != 0;
-    if (B < 0 || B > 0x7FFFFFFF) return fail(QD_EINVAL, "batch size out of range");
+    if (d->post == QD_POST_NONE) return fail(QD_EINVAL, "decoder was created with osd_method = off");
+    if (int rc = check_batch(d, det_stride, det_offset, d_upd, upd_stride, upd_rows, B)) return rc;
     if (B == 0) return QD_OK;
-    if (det_offset < 0 || det_stride < det_offset + d->g->m) return fail(QD_EINVAL, "detector slice exceeds the row stride");
-    if (d_upd && (upd_rows < 0 || upd_rows > d->g->m || upd_stride < upd_rows)) return fail(QD_EINVAL, "bad syndrome-update shape");
     HIP_TRY(hipSetDevice(d->g->device));
-    if (B > d->cap) {
-        int rc = qd_decoder_reserve(d, B);
-        if (rc) return rc;
-    }
+    if (int rc = B > d->cap ? qd_decoder_reserve(d, B) : QD_OK) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    DecodeArgs a{};
-    a.det = d_det; a.det_stride = det_stride; a.det_offset = det_offset;
-    a.upd = d_upd; a.upd_stride = upd_stride; a.upd_rows = d_upd ? upd_rows : 0;
-    a.max_iter = d->prm.max_iter; a.ms_scale = (float)d->prm.ms_scaling_factor; a.want_llr = 1;
-    a.err_bits = d_err_bits; a.status = d_status;
-    a.llr_ws = d->llr_ws; a.fail_list = d->fail_list; a.fail_count = d->fail_count;
-    a.order_ws = d->order_ws; a.q_spill = d->q_spill; a.q_spill_fast = d->q_spill_fast; a.q_spill_sr = d->q_spill_sr; a.mt_ws = d->mt_ws;
-    a.hard_list = d->hard_list; a.hard_list2 = d->hard_list2; a.hard_count = d->fail_count + 1;
-    a.dbg = reinterpret_cast<unsigned long long *>(d->ctr_base) + 2;
-    a.osd_w = d->osd_w; a.osd_order = d->prm.osd_order; a.rank = d->g->rank;
+    const DecodeArgs a = decode_args(d, d_det, det_stride, det_offset, d_upd, upd_stride, upd_rows, d_err_bits, d_status);
     HIP_TRY(hipMemsetAsync(d->fail_count, 0, 3 * sizeof(int32_t), s));
     d->set_clean[d->cset] = false;
     HIP_TRY(qd_launch_stage_llr(d_llr, d->g->n, d->g->bp.n_pad, d->g->bp.bit_orig, B, d->llr_ws, d->fail_list, d->fail_count,
                                 d_status, s));
-    if (lsd_only)
-        HIP_TRY(qd_launch_lsd0(d->g->gen, d->g->bp, a, d->lsd_ws, d->lsd_blocks, (int)std::min<int64_t>(B, d->lsd_blocks), d->lsd_w,
-                                   d->prm.osd_order, d->g->osd.wfix, s));
-    else if (d->osd_blocks_cs > 0)
-        HIP_TRY(qd_launch_osdcs(d->g->osd, d->g->bp, a, d->cs_off, d->cs_variant, d->cs_lds, d->cs_ws,
-                                (int)std::min<int64_t>(B, d->osd_blocks_cs), s));
-    else if (d->osd_blocks_sr > 0) {
-        HIP_TRY(qd_launch_osd0_sr(d->g->osd, d->g->bp, a, (int)std::min<int64_t>(B, d->osd_blocks_sr), s));
-        HIP_TRY(qd_launch_osd0(d->g->osd, d->g->bp, a, (int)std::min<int64_t>(B, d->osd_blocks_fast),
-                               (int)std::min<int64_t>(B, d->osd_blocks), s, true));
-    } else
-        HIP_TRY(qd_launch_osd0(d->g->osd, d->g->bp, a, (int)std::min<int64_t>(B, d->osd_blocks_fast),
-                               (int)std::min<int64_t>(B, d->osd_blocks), s));
-    return QD_OK;
+    return launch_post(d, a, B, s);
 }
 
 extern "C" int qd_decoder_debug_counters(qd_decoder *d, uint64_t *out16)

@@ -139,6 +139,8 @@ class DeviceWindowPlan:
             budget = float(os.environ.get("QD_GENERAL_WS_GB", "96")) * (1 << 30)
             for d in decs:
                 d.set_workspace_limit(max(1 << 28, int(budget / len(decs))))
+        elif os.environ.get("QD_GENERAL_WS_GB"):                  # one decoder: the whole budget (unset: the library's 48 GB)
+            decs[0].set_workspace_limit(int(max(0.001, float(os.environ["QD_GENERAL_WS_GB"])) * (1 << 30)))
         # calls of two or more chunks: the post-processing of one chunk beside the BP of another (_decode_pipelined_impl);
         # QD_NO_PIPELINE=1 or plan.pipeline = False keeps everything on the caller's stream.  Not the default where BP runs in the
         # per-edge kernel: HBM-bound, it loses more to the co-running post-processor than the overlap returns (W = 5 / F = 3

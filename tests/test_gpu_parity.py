@@ -413,12 +413,11 @@ def test_general_serial_staged_launches_equal_one_launch(gpu, monkeypatch):
             assert torch.equal(bits, bits_b) and torch.equal(st, st_b), (method, "no convergence", rep)
         bits, st = d.decode(det)
         assert torch.equal(bits, bits_1) and torch.equal(st, st_1), (method, "after the switch")
-        monkeypatch.setenv("QD_GENERAL_WS_GB", "0.02")          # ~ 256-shot chunks (two message planes of them)
         monkeypatch.delenv("QD_GEN_STAGES", raising=False)
         d = BatchDecoder(g, **kw)
+        d.set_workspace_limit(int(0.02 * 2**30))               # ~ 256-shot chunks (two message planes of them)
         bits, st = d.decode(det)
         assert torch.equal(bits, bits_1) and torch.equal(st, st_1), (method, "chunks")
-        monkeypatch.delenv("QD_GENERAL_WS_GB")
         from quits_amd.decoder.device import unpack_bits
         synd = det[:200].cpu().numpy()
         go, form = orc.device_arithmetic(H, pri, method, "serial", 9, 1.0)
@@ -439,8 +438,8 @@ def test_general_chunking_and_compressed_agreement(gpu, monkeypatch):
     g = WindowGraph(H, pri)
     a = BatchDecoder(g, max_iter=20, osd_method="osd_0", edge_messages=True)
     bits_a, st_a = a.decode(det)
-    monkeypatch.setenv("QD_GENERAL_WS_GB", "0.02")          # ~ 256-shot chunks
     b = BatchDecoder(g, max_iter=20, osd_method="osd_0", edge_messages=True)
+    b.set_workspace_limit(int(0.02 * 2**30))                # ~ 256-shot chunks
     bits_b, st_b = b.decode(det)
     assert torch.equal(bits_a, bits_b) and torch.equal(st_a, st_b)
     c = BatchDecoder(g, max_iter=20, osd_method="osd_0")

@@ -1,5 +1,5 @@
-# same-box A/B of the serial BP kernel through bench.py: an environment switch (default QD_NO_LDS_PREFIX=1 = prefixes in the HBM plane) against the default path
-SW=${1:-QD_NO_LDS_PREFIX}
+# same-box A/B of the serial BP kernel through bench.py: the environment switch named by the first argument (set to 1) against the default path
+SW=${1:?usage: tools/ab_lib.sh SWITCH}
 timeout 600 python -m pytest tests -m gpu -q -x -k "general or serial or reference_defaults or randomised" 2>&1 | tail -2
 for a in "--schedule serial --window 5 3 --osd-method osd_cs --osd-order 1" "--schedule serial --window 3 1" "--schedule serial" "--bp-method minimum_sum --schedule serial" "--schedule serial --window 5 3 --shots 81920" "--schedule serial --code bb72 --window 3 1"; do
   for sw in 1 0 1 0; do
