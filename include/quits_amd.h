@@ -45,7 +45,10 @@ extern "C" {
 /* status word written per shot by qd_decode_batch */
 #define QD_STATUS_ITER_MASK 0x3FFF      /* BP iterations used (max_iter is capped at 16383)           */
 #define QD_STATUS_COARSE_GRID (1 << 14) /* flooding min-sum: decoded on the coarse LLR grid (see qd_decoder_info)          */
-#define QD_STATUS_INEXACT (1 << 15)     /* ... and even there the exactness bound tripped: float rounding may have occurred */
+#define QD_STATUS_INEXACT (1 << 15)     /* ... and even there the exactness bound tripped: float rounding may have occurred.
+                                         * Also set, WITHOUT QD_STATUS_COARSE_GRID, on a shot that left the fine grid but found the
+                                         * coarse-grid list full: the list holds min(batch, 4096) shots of a call (the whole batch where
+                                         * the fine grid sits on the 2^-10 floor, see qd_decoder_info); such a shot keeps its fine-grid result */
 #define QD_STATUS_CONVERGED (1 << 16)   /* BP reproduced the syndrome                                 */
 #define QD_STATUS_OSD (1 << 17)         /* OSD post-processing produced the output                    */
 #define QD_STATUS_INCONSISTENT (1 << 18)/* OSD: syndrome outside the column space of the window matrix */
@@ -150,6 +153,7 @@ int qd_decoder_release_workspace(qd_decoder *d);
  *      whole batch of shots, including the syndrome preparation in front of them (:168-169,179-180):
  *        syndrome[b][i] = d_det[b * det_stride + det_offset + i]  (i < m)   XOR   d_upd[b * upd_stride + i] (i < upd_rows)
  *      d_det: one byte per detector (0/1), i.e. the `zcheck_samples` array; d_upd may be NULL.
+ *      B = 0 is valid: QD_OK whatever the pointers (NULL included), nothing is read, written or launched.
  *      Outputs: d_err_bits[b][w], w < ceil(n/32): bit (j & 31) of word (j >> 5) = decoded fault j;
  *               d_status[b]: QD_STATUS_* flags | iterations. */
 int qd_decode_batch(qd_decoder *d, const uint8_t *d_det, int64_t det_stride, int64_t det_offset,

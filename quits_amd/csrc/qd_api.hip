@@ -1446,10 +1446,11 @@ static int decode_impl(qd_decoder *d, const uint8_t *d_det, int64_t det_stride, 
                        int64_t upd_stride, int32_t upd_rows, int64_t B, uint32_t *d_err_bits, int32_t *d_status, int stage,
                        void *stream)
 {
-    if (!d || !d_det || !d_err_bits || !d_status) return fail(QD_EINVAL, "null argument");
+    if (!d) return fail(QD_EINVAL, "null decoder");
     if (stage < 1 || stage > 3) return fail(QD_EINVAL, "stage must be 1 (BP), 2 (OSD) or 3 (both)");
     if (int rc = check_batch(d, det_stride, det_offset, d_upd, upd_stride, upd_rows, B)) return rc;
-    if (B == 0) return QD_OK;
+    if (B == 0) return QD_OK;                            // whatever the pointers: an empty batch has none (a torch tensor of no rows: data_ptr() = 0)
+    if (!d_det || !d_err_bits || !d_status) return fail(QD_EINVAL, "null argument");
     HIP_TRY(hipSetDevice(d->g->device));
     if (B > d->cap && stage == 2) return fail(QD_EINVAL, "OSD stage without a preceding BP stage of this batch size");
     if (int rc = B > d->cap ? qd_decoder_reserve(d, B) : QD_OK) return rc;
@@ -1540,10 +1541,11 @@ extern "C" int qd_osd0_batch(qd_decoder *d, const uint8_t *d_det, int64_t det_st
                              const uint8_t *d_upd, int64_t upd_stride, int32_t upd_rows, int64_t B, const float *d_llr,
                              uint32_t *d_err_bits, int32_t *d_status, void *stream)
 {
-    if (!d || !d_det || !d_llr || !d_err_bits || !d_status) return fail(QD_EINVAL, "null argument");
+    if (!d) return fail(QD_EINVAL, "null decoder");
     if (d->post == QD_POST_NONE) return fail(QD_EINVAL, "decoder was created with osd_method = off");
     if (int rc = check_batch(d, det_stride, det_offset, d_upd, upd_stride, upd_rows, B)) return rc;
     if (B == 0) return QD_OK;
+    if (!d_det || !d_llr || !d_err_bits || !d_status) return fail(QD_EINVAL, "null argument");
     HIP_TRY(hipSetDevice(d->g->device));
     if (int rc = B > d->cap ? qd_decoder_reserve(d, B) : QD_OK) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
