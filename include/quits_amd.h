@@ -76,6 +76,8 @@ typedef struct qd_circuit qd_circuit;   /* compiled circuit program of the frame
  *   QD_SCATTER_NATURAL_ROUNDS  G  ... its wavefronts take the slot-waves in natural order (no balancing of their rounds)
  *   QD_SCATTER_BANKS_BY_SLOT   G  the scatter accumulators' banks = the degree-sorted bit slots mod 32 (no balancing)
  *   QD_SCATTER_WALK_GREEDY     G  the scatter kernels' walk without matching: every check takes its least busy bank
+ *   QD_BP_NO_FAST_START=1      D  the several-checks-per-lane kernel runs gather pass 0 itself and the full last gather pass, instead of starting
+ *                                 from the decoder's first-pass table and folding only the hard-decision parity in the last pass
  *   QD_OSDCS_OLD=1             D  higher-order OSD by row (osd_kernels.hip) instead of the panel kernel (osd_cs.hip)
  *   QD_GEN_STAGES="3,6" / =0   D  iteration bounds between the launches of the serial schedule (one-message-per-edge kernel) / one launch */
 
@@ -90,7 +92,7 @@ typedef struct qd_params {
     double ms_scaling_factor;   /* not exposed by the reference wrapper -> ldpc default 1.0; 0 = 1-2^-it */
 } qd_params;
 
-int qd_version(void);                 /* 104 (104: qd_circuit_* + qd_sample_circuit; 103: qd_decoder_post_head_start; 101: qd_graph_info wrote 12 entries; 102: 10 again + qd_graph_info_ex) */
+int qd_version(void);                 /* 105 (105: qd_decoder_fast_start; 104: qd_circuit_* + qd_sample_circuit; 103: qd_decoder_post_head_start; 101: qd_graph_info wrote 12 entries; 102: 10 again + qd_graph_info_ex) */
 const char *qd_last_error(void);
 /* Number of visible HIP devices (0 if none): lets a host fail loudly before building anything. */
 int qd_device_count(void);
@@ -127,6 +129,10 @@ void qd_decoder_destroy(qd_decoder *d);
  * lane for windows of more than 1024 checks or rows of 65..96 faults).
  * No reference counterpart (ldpc computes in double). */
 int qd_decoder_info(const qd_decoder *d, int32_t *info);
+/* 1 if the several-checks-per-lane scatter kernel of this decoder starts from the first-pass table (gather pass 0 of flooding min-sum reads the
+ * priors alone, so what it finds is made once, when the decoder is created) and runs its last gather pass in the thin form; 0 otherwise
+ * (another BP kernel, max_iter < 1, QD_BP_NO_FAST_START=1).  Same results either way, bit for bit. */
+int qd_decoder_fast_start(const qd_decoder *d);
 /* Which kernel post-processes the shots BP leaves unconverged (decoder/device.py reports it; bench.py labels its roofline.osd object
  * with it).  No reference counterpart: ldpc has one OsdDecoder / LsdDecoder. */
 #define QD_POST_NONE 0          /* osd_method = osd_off                                                                          */

@@ -29,6 +29,9 @@ typedef __attribute__((address_space(3))) int32_t qs_lds_i32;
 // two edges of a pair -- the first is remembered in `hpa`, the second folds both in with one v_bitop3_b32 (a ^ b ^ c): half an instruction per edge
 // QS_SIGN31(sb): the sign this check sent on the edge (bit `sb` of sgnw) moved to bit 31.  (Keeping sgnw pre-shifted so that the shift amounts are
 // immediates instead of one scalar each measured slower: 42.6 -> 43.1 ms, profiles/r05_k1sw_micro_ab.txt.)
+// QS_ACC(off): the accumulator itself -- an LDS read in the kernels; the first-pass table (bp_scatter_wide.hip) redefines it to read the priors from
+// global memory.
+#define QS_ACC(off) (*QS_LDS(QS_ADDR(off)))
 #define QS_SIGN31(sb) (((sgnw >> (sb)) & 1u) << 31)
 #define QS_HP1(A_) hp ^= (uint32_t)(A_);
 #define QS_HPA(A_) hpa = (uint32_t)(A_);
@@ -36,7 +39,7 @@ typedef __attribute__((address_space(3))) int32_t qs_lds_i32;
 #define QS_EDGE(off, k_, sb, TAILFIX) QS_EDGE_H(off, k_, sb, TAILFIX, QS_HP1)
 #define QS_EDGE_H(off, k_, sb, TAILFIX, HP)                                                                  \
     {                                                                                                        \
-        const int A_ = *QS_LDS(QS_ADDR(off));                                                                \
+        const int A_ = QS_ACC(off);                                                                          \
         const float mag_ = ((uint32_t)(k_) == kold) ? s2 : s1;                                               \
         const float prev_ = __uint_as_float(QS_SIGN31(sb) | __float_as_uint(mag_));                          \
         float d_ = (float)A_ - prev_;                                                                        \

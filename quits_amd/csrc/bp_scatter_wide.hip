@@ -40,6 +40,14 @@
 #endif
 // QSW_PRIO_BASE: added to every priority this kernel sets (gather rounds 0 / 1 / 2, scatter pass QS_PRIO, 0 in between): above 0 the wavefronts of a
 // kernel running beside this one at the default priority (the pipelined driver's post-processing) only issue when these do not
+// QSW_FAST_START / QSW_THIN_LAST: the two halves of the fast start (table of gather pass 0; hard-decision parity alone in the last pass), 0 = that half
+// as the generic loop does it (step-by-step A/B, profiles/bp_fast_start_ab.txt)
+#ifndef QSW_FAST_START
+#define QSW_FAST_START 1
+#endif
+#ifndef QSW_THIN_LAST
+#define QSW_THIN_LAST 1
+#endif
 #ifndef QSW_PRIO_BASE
 #define QSW_PRIO_BASE 0
 #endif
@@ -136,10 +144,48 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
 #endif
 #define QS_ADJ_FIRST qs_as_uint4(__builtin_amdgcn_raw_buffer_load_b128(adj_rsrc, cs[0] * 16, 0, 0))
     uint4 pf = QS_ADJ_FIRST;
+    // ---- fast start.  Gather pass 0 reads the priors alone (nothing has been sent: S1 = S2 = 0, O = 0, KOLD none), so the minima, the argmin and
+    // the incoming signs it finds are constants of the decoder: they come from the table qd_bp_first_pass_kernel made with the same walk.  Only `flip`
+    // depends on the shot, through the check's own syndrome bit; the pass's convergence vote is never read (t >= 1 below).  The kernel then enters
+    // the loop at scatter pass 0, behind the barriers of the set-up above.
+    const bool fast = x.first_pass != nullptr && a.max_iter >= 1;
+    bool have = false;                                  // A1 / A2 / KST / Q already hold what the gather pass of this iteration would find
+    if (QSW_FAST_START && fast) {
+#pragma unroll
+        for (int j = 0; j < CPL; ++j)
+            if (act[j]) {
+                const uint4 *rp = reinterpret_cast<const uint4 *>(x.first_pass) + 2 * cs[j];
+                const uint4 r0 = rp[0], r1 = rp[1];
+                const uint32_t negw[3] = {r0.w, r1.x, r1.y};
+                const uint32_t flip = 0u - ((synd[j] ^ r1.z) & 1u);
+                A1[j] = __uint_as_float(r0.x); A2[j] = __uint_as_float(r0.y); KST[j] = r0.z;
+#pragma unroll
+                for (int w = 0; w < NSW; ++w) Q[j][w] = negw[w] ^ flip;
+                mx2 = fmaxf(mx2, A2[j]);
+            }
+        have = true;
+    }
+    // the convergence vote of a gather pass: one flag per wavefront, read by everybody behind the barrier the pass ends at
+#define QSW_VOTE(us_, anyun_)                                                                          \
+        {                                                                                              \
+            const unsigned long long bal = __ballot(us_);                                              \
+            if ((tid & 63) == 0) misc[32 + (tid >> 6)] = (bal != 0ull);                                \
+        }                                                                                              \
+        __syncthreads();                                                                               \
+        anyun_ = 0;                                                                                    \
+        {                                                                                              \
+            const int4 *f4 = reinterpret_cast<const int4 *>(misc + 32);                                \
+            for (int w = 0; w < (NW + 3) / 4; ++w) {                                                   \
+                const int4 v = f4[w];                                                                  \
+                anyun_ |= v.x | v.y | v.z | v.w;                                                       \
+            }                                                                                          \
+        }
     int t = 0, converged = 0;
     for (;;) {
+      if (!have) {
         // ---- gather pass t+1 over L(t); the parity of the hard decisions it meets is the convergence test of iteration t
         bool us = false;
+        if (QSW_THIN_LAST && fast && t == a.max_iter) break;      // the last pass runs behind the loop, in its thin form
 #pragma unroll
         for (int j = 0; j < CPL; ++j) {
             float a1 = FLT_MAX, a2 = FLT_MAX;
@@ -148,81 +194,7 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
             if (j == 0) __builtin_amdgcn_s_setprio(QSW_PRIO_BASE); else if (j == CPL - 1) __builtin_amdgcn_s_setprio((QSW_PRIO_BASE + 2) & 3); else __builtin_amdgcn_s_setprio((QSW_PRIO_BASE + 1) & 3);
 #endif
             if (act[j]) {
-                // (the round's loop bounds are re-derived from one scalar every pass: hoisted out of the iteration loop they, and everything computed
-                //  from them for CPL rounds x NSW words, outgrow the scalar registers and come back through v_readlane)
-                int dwj = dws[j];
-                asm volatile("" : "+s"(dwj));
-                const int trip = dwj & 0xFF, wmax = (dwj >> 8) & 0xFF, wmin = (dwj >> 16) & 0xFF, wmin4 = wmin & ~3;
-                const int adj_voff = cs[j] * 16;
-                QS_ABL_ADJC
-                const float s1 = S1[j], s2 = S2[j];
-                const uint32_t kold = KOLD[j];
-                const int dc = dcs[j];
-                uint32_t hp = 0u, hpa = 0u, par = 0u;
-                uint32_t neg[NSW];
-#pragma unroll
-                for (int w = 0; w < NSW; ++w) {
-                    neg[w] = 0u;
-                    const int k0 = 32 * w;
-                    if (k0 < trip) {
-                        const uint32_t sgnw = O[j][w];
-                        uint32_t neww = 0u, ltw = 0u;
-                        const int kend = min(trip - k0, 32);                  // multiple of 4
-                        const int kplain = min(max(wmin4 - k0, 0), kend);     // groups every lane of the wavefront has in full
-                        const int row0 = k0 >> 2;
-                        uint4 nx = (QSW_PREFETCH && j == 0 && w == 0) ? pf : QS_ADJ(row0);
-                        int kk = 0;
-                        {
-                            uint4 eb;                                         // two groups per trip on two register sets (bp_scatter.hip)
-#pragma unroll 1
-                            for (; kk + 8 <= kplain; kk += 8) {
-                                eb = QS_ADJ(row0 + (kk >> 2) + 1);            // (the table has spare group rows)
-                                {
-                                    const int sb = kend - 1 - kk, k = k0 + kk;
-                                    QS_EDGE_H(nx.x, k, sb, QS_NOFIX, QS_HPA) QS_EDGE_H(nx.y, k + 1, sb - 1, QS_NOFIX, QS_HPB)
-                                    QS_EDGE_H(nx.z, k + 2, sb - 2, QS_NOFIX, QS_HPA) QS_EDGE_H(nx.w, k + 3, sb - 3, QS_NOFIX, QS_HPB)
-                                }
-                                nx = QS_ADJ(row0 + (kk >> 2) + 2);
-                                {
-                                    const int sb = kend - 5 - kk, k = k0 + kk + 4;
-                                    QS_EDGE_H(eb.x, k, sb, QS_NOFIX, QS_HPA) QS_EDGE_H(eb.y, k + 1, sb - 1, QS_NOFIX, QS_HPB)
-                                    QS_EDGE_H(eb.z, k + 2, sb - 2, QS_NOFIX, QS_HPA) QS_EDGE_H(eb.w, k + 3, sb - 3, QS_NOFIX, QS_HPB)
-                                }
-                            }
-                        }
-#pragma unroll 1
-                        for (; kk < kplain; kk += 4) {
-                            const uint4 e4 = nx;
-                            nx = QS_ADJ(row0 + (kk >> 2) + 1);
-                            const int sb = kend - 1 - kk, k = k0 + kk;
-                            QS_EDGE_H(e4.x, k, sb, QS_NOFIX, QS_HPA)
-                            QS_EDGE_H(e4.y, k + 1, sb - 1, QS_NOFIX, QS_HPB)
-                            QS_EDGE_H(e4.z, k + 2, sb - 2, QS_NOFIX, QS_HPA)
-                            QS_EDGE_H(e4.w, k + 3, sb - 3, QS_NOFIX, QS_HPB)
-                        }
-                        // an edge below the smallest degree of the wavefront is real on every lane (no fix), one at or beyond the largest is
-                        // nobody's; only in between does a lane have to ask (wave-uniform tests; k < wmax: a group starts below the largest degree)
-#define QS_TAIL_EDGE(off, q_)                                                                                     \
-                            if (k + (q_) < wmin) QS_EDGE(off, k + (q_), sb - (q_), QS_NOFIX)                      \
-                            else if (k + (q_) < wmax) QS_EDGE(off, k + (q_), sb - (q_), QS_TAILFIX)               \
-                            else { neww <<= 1; ltw <<= 1; }
-#pragma unroll 1
-                        for (; kk + 4 < kend; kk += 4) {
-                            const uint4 e4 = nx;
-                            nx = QS_ADJ(row0 + (kk >> 2) + 1);
-                            const int sb = kend - 1 - kk, k = k0 + kk;
-                            QS_TAIL_EDGE(e4.x, 0) QS_TAIL_EDGE(e4.y, 1) QS_TAIL_EDGE(e4.z, 2) QS_TAIL_EDGE(e4.w, 3)
-                        }
-                        if (kk < kend) {              // the word's last group (for rows of 33..36 faults the second word's only one): nothing to request behind it, no copy
-                            const int sb = kend - 1 - kk, k = k0 + kk;
-                            QS_TAIL_EDGE(nx.x, 0) QS_TAIL_EDGE(nx.y, 1) QS_TAIL_EDGE(nx.z, 2) QS_TAIL_EDGE(nx.w, 3)
-                        }
-#undef QS_TAIL_EDGE
-                        neg[w] = neww;
-                        par ^= neww;
-                        if (ltw) kst = (uint32_t)(k0 + kend - 1 - (int)__builtin_ctz(ltw));   // a later word's improvement overrides an earlier one's
-                    }
-                }
+#include "bp_scatter_wide_walk.inc"
                 // outgoing sign on edge k = syndrome ^ (parity of all incoming signs) ^ incoming sign k
                 const uint32_t flip = 0u - ((synd[j] ^ (uint32_t)__popc(par)) & 1u);
 #pragma unroll
@@ -236,23 +208,14 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
         __builtin_amdgcn_s_setprio(QSW_PRIO_BASE);
 #endif
         if (QSW_PREFETCH) pf = QS_ADJ_FIRST;              // for the scatter pass behind the barrier
-        {
-            const unsigned long long bal = __ballot(us);
-            if ((tid & 63) == 0) misc[32 + (tid >> 6)] = (bal != 0ull);
-        }
-        __syncthreads();
-        int anyun = 0;
-        {
-            const int4 *f4 = reinterpret_cast<const int4 *>(misc + 32);
-            for (int w = 0; w < (NW + 3) / 4; ++w) {
-                const int4 v = f4[w];
-                anyun |= v.x | v.y | v.z | v.w;
-            }
-        }
+        int anyun;
+        QSW_VOTE(us, anyun)
 #ifndef QS_ABL_FORCE_ITERS       /* timing experiments only: every shot runs max_iter iterations, whatever the (wrong) arithmetic of an ablation build does */
         if (t >= 1 && !anyun) { converged = 1; break; }
 #endif
         if (t == a.max_iter) break;
+      }
+        have = false;
         // ---- scatter pass, in place: each edge's accumulator moves by (new message) - (message sent last time)
         __builtin_amdgcn_s_setprio((QSW_PRIO_BASE + QS_PRIO) & 3);
 #pragma unroll
@@ -372,6 +335,49 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
         __syncthreads();
         ++t;
     }
+    if (QSW_THIN_LAST && fast && !converged) {
+        // ---- the gather pass at t = max_iter (the loop left before it).  No scatter pass follows, so its minima, signs and argmin would be thrown
+        // away; what is left is the parity of the hard decisions, the convergence test of the last iteration.  Steps beyond a check's degree read a
+        // trash slot, which holds 0: they cannot set bit 31.  The pass's second minima do not enter mx2 either: they are magnitudes of messages of
+        // iteration max_iter + 1, which nobody sends -- every sum that was computed is covered by the minima of the passes before.
+        bool us = false;
+#pragma unroll
+        for (int j = 0; j < CPL; ++j) {
+#if QSW_GPRIO
+            if (j == 0) __builtin_amdgcn_s_setprio(QSW_PRIO_BASE); else if (j == CPL - 1) __builtin_amdgcn_s_setprio((QSW_PRIO_BASE + 2) & 3); else __builtin_amdgcn_s_setprio((QSW_PRIO_BASE + 1) & 3);
+#endif
+            if (act[j]) {
+                int dwj = dws[j];
+                asm volatile("" : "+s"(dwj));
+                const int ng = (dwj & 0xFF) >> 2;
+                const int adj_voff = cs[j] * 16;
+                QS_ABL_ADJC
+                uint32_t hp = 0u, hpa = 0u;
+#define QS_HP_GROUP(e4) { QS_HPA(QS_ACC(e4.x)) QS_HPB(QS_ACC(e4.y)) QS_HPA(QS_ACC(e4.z)) QS_HPB(QS_ACC(e4.w)) }
+                uint4 nx = (QSW_PREFETCH && j == 0) ? pf : QS_ADJ(0);
+                int gi = 0;
+#pragma unroll 1
+                for (; gi + 2 <= ng; gi += 2) {               // two groups per trip on two register sets, as in the full pass
+                    const uint4 eb = QS_ADJ(gi + 1);          // (the table has two spare group rows)
+                    QS_HP_GROUP(nx)
+                    nx = QS_ADJ(gi + 2);
+                    QS_HP_GROUP(eb)
+                }
+                if (gi < ng) QS_HP_GROUP(nx)
+#undef QS_HP_GROUP
+                us = us || (((synd[j] ^ (hp >> 31)) & 1u) != 0u);
+            }
+        }
+#if QSW_GPRIO
+        __builtin_amdgcn_s_setprio(QSW_PRIO_BASE);
+#endif
+        int anyun;
+        QSW_VOTE(us, anyun)
+#ifndef QS_ABL_FORCE_ITERS
+        if (!anyun) converged = 1;                  // (t = max_iter >= 1)
+#endif
+    }
+#undef QSW_VOTE
 #undef QS_ADJ
 #undef QS_ADJ_FIRST
 #undef QS_ADJ_LOAD
@@ -406,6 +412,52 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
         if (tid == 0) a.fail_list[slot] = (int32_t)shot;
     }
     if (tid == 0) a.status[shot] = t | (converged << 16) | a.status_or;
+}
+
+// ---- the first-pass table: gather pass 0 of every check slot, once per decoder (qd_decoder_create).  One wavefront per 64 consecutive check slots,
+// as a round of the kernel above has them; the walk is that kernel's own program text with the accumulators read from the priors in global memory.
+// A record is 8 words (ScatArgs::first_pass), so that a lane fetches its check with two 16-byte loads.
+#undef QS_ACC
+#define QS_ACC(off) (prior_g[((uint32_t)(off) - (uint32_t)sg.offA) >> 2])
+#define QS_ADJ(row_) qs_as_uint4(__builtin_amdgcn_raw_buffer_load_b128(adj_rsrc, adj_voff, (row_) * adj_row, 0))
+#define QS_ABL_ADJC
+template <int NSW>
+__global__ void __launch_bounds__(64) qd_bp_first_pass_kernel(BpGraphDev g, ScatGraphDev sg, const int32_t *prior_g, uint32_t *rec)
+{
+    static_assert(NSW == 3, "the record has room for three sign words");
+    const int c = (int)blockIdx.x * 64 + (int)threadIdx.x;
+    const bool actv = c < g.m;
+    constexpr int j = 0;
+    const int cs[1] = {c}, dws[1] = {__builtin_amdgcn_readfirstlane((int)sg.deg_w[blockIdx.x])}, dcs[1] = {actv ? (int)sg.chk_deg[c] : 0};
+    const float S1[1] = {0.f}, S2[1] = {0.f};           // nothing has been sent
+    const uint32_t KOLD[1] = {0xFFFFFFFFu}, O[1][NSW] = {{0u, 0u, 0u}};
+    const __amdgpu_buffer_rsrc_t adj_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)sg.adjA, 0, (g.max_rdeg_pad / 4 + 2) * g.m_pad * 16, 0x00020000);
+    const int adj_row = g.m_pad * 16;
+    const uint4 pf = qs_as_uint4(__builtin_amdgcn_raw_buffer_load_b128(adj_rsrc, c * 16, 0, 0));
+    float a1 = FLT_MAX, a2 = FLT_MAX;
+    uint32_t kst = 0u;
+    uint4 r0 = make_uint4(__float_as_uint(FLT_MAX), __float_as_uint(FLT_MAX), 0u, 0u);      // (a slot beyond the window: what the kernel's own pass leaves there)
+    uint4 r1 = make_uint4(0u, 0u, 0u, (uint32_t)sg.offA + (uint32_t)(sg.nslots - 32 + (int)(threadIdx.x & 31)) * 4u);
+    if (actv) {
+#include "bp_scatter_wide_walk.inc"
+        (void)hp;
+        r0 = make_uint4(__float_as_uint(a1), __float_as_uint(a2), kst, neg[0]);
+        r1 = make_uint4(neg[1], neg[2], (uint32_t)__popc(par) & 1u,
+                        __builtin_amdgcn_raw_buffer_load_b32(adj_rsrc, (int)((kst >> 2) * (uint32_t)adj_row + (kst & 3u) * 4u) + c * 16, 0, 0));
+    }
+    uint4 *out = reinterpret_cast<uint4 *>(rec) + 2 * c;
+    out[0] = r0; out[1] = r1;
+}
+#undef QS_ADJ
+#undef QS_ABL_ADJC
+#undef QS_ACC
+
+// rec: [m_pad][8] words
+hipError_t qd_launch_bp_first_pass(const BpGraphDev &g, const ScatGraphDev &sg, const int32_t *prior_g, uint32_t *rec, hipStream_t s)
+{
+    if (g.max_rdeg_pad > 96 || g.m_pad % 64) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(qd_bp_first_pass_kernel<3>, dim3((unsigned)(g.m_pad / 64)), dim3(64), 0, s, g, sg, prior_g, rec);
+    return hipGetLastError();
 }
 
 template <int T, int MW, int CPL, int NSW>

@@ -17,6 +17,7 @@
 hipError_t qd_launch_bp(const BpGraphDev &g, const DecodeArgs &a, int64_t B, hipStream_t s);
 hipError_t qd_launch_bp_scatter(const BpGraphDev &g, const ScatGraphDev &sg, const DecodeArgs &a, const ScatArgs &x, int64_t B, hipStream_t s);
 hipError_t qd_launch_bp_scatter_wide(const BpGraphDev &g, const ScatGraphDev &sg, const DecodeArgs &a, const ScatArgs &x, int64_t B, hipStream_t s);
+hipError_t qd_launch_bp_first_pass(const BpGraphDev &g, const ScatGraphDev &sg, const int32_t *prior_g, uint32_t *rec, hipStream_t s);
 hipError_t qd_launch_bp_general(const GenGraphDev &g, const BpGraphDev &bg, const DecodeArgs &a, const GenWs &w, int bp_method,
                                 int schedule, int64_t shot0, int nshots, hipStream_t s, GenStagePlan *plan);
 hipError_t qd_launch_hold(const int32_t *count, int threshold, int microseconds, hipStream_t s);
@@ -86,7 +87,7 @@ struct DevAllocs {
 // The validation switches of include/quits_amd.h: each selects an alternative that the tests compare bit for bit against the default.
 // Read here alone, when a graph or a decoder is created; nothing on the decode path reads the environment.
 struct Switches {
-    bool no_scatter, scatter_cpl1, scatter_wide_t704, scatter_natural_rounds, scatter_banks_by_slot, scatter_walk_greedy, osdcs_old;
+    bool no_scatter, scatter_cpl1, scatter_wide_t704, scatter_natural_rounds, scatter_banks_by_slot, scatter_walk_greedy, osdcs_old, bp_no_fast_start;
     float scatter_m2_limit;             // +inf: not set
     std::vector<int> gen_stages;        // iteration bounds between the launches of the serial schedule in the one-message-per-edge kernel
 };
@@ -101,7 +102,9 @@ static Switches read_switches()
     w.scatter_natural_rounds = env("QD_SCATTER_NATURAL_ROUNDS") != nullptr;
     w.scatter_banks_by_slot = env("QD_SCATTER_BANKS_BY_SLOT") != nullptr;
     w.scatter_walk_greedy = env("QD_SCATTER_WALK_GREEDY") != nullptr;
-    const char *ev = env("QD_OSDCS_OLD");
+    const char *ev = env("QD_BP_NO_FAST_START");
+    w.bp_no_fast_start = ev && std::atoi(ev) == 1;
+    ev = env("QD_OSDCS_OLD");
     w.osdcs_old = ev && std::atoi(ev) == 1;
     ev = env("QD_SCATTER_M2_LIMIT");
     w.scatter_m2_limit = ev ? (float)std::atof(ev) : INFINITY;
@@ -196,6 +199,7 @@ struct qd_decoder {
     int redo_cap = 0;
     const int32_t *prior_g = nullptr;          // [n_pad] fine-grid channel LLRs of the bit slots in grid units (scatter kernels)
     float m2_limit = 0.f;
+    const uint32_t *first_pass = nullptr;      // [m_pad][8] gather pass 0 of every check slot (ScatArgs::first_pass); null: the kernel runs it (QD_BP_NO_FAST_START=1, one check per lane)
     int32_t *recheck_list = nullptr;           // shots the scatter kernel's bound could not certify
     int recheck_cap = 0;
     DevAllocs mem;
@@ -366,7 +370,7 @@ static void scatter_walk(int m, const int32_t *row_ptr, const int32_t *col_idx, 
     }
 }
 
-extern "C" int qd_version(void) { return 104; }      // 104: qd_circuit_* and qd_sample_circuit; 103: qd_decoder_post_head_start; 102: qd_graph_info fills 10 entries again, qd_graph_info_ex(g, info, n) the rest; 101: qd_decoder_postproc_kernel
+extern "C" int qd_version(void) { return 105; }      // 105: qd_decoder_fast_start; 104: qd_circuit_* and qd_sample_circuit; 103: qd_decoder_post_head_start; 102: qd_graph_info fills 10 entries again, qd_graph_info_ex(g, info, n) the rest; 101: qd_decoder_postproc_kernel
 extern "C" const char *qd_last_error(void) { return g_err; }
 extern "C" int qd_device_count(void)
 {
@@ -1146,6 +1150,14 @@ extern "C" int qd_decoder_create(const qd_graph *g, const qd_params *p, qd_decod
                 rc |= d->mem.upload(pg, &d->prior_g);
                 d->m2_limit = std::min((float)lim, env.scatter_m2_limit);     // (QD_SCATTER_M2_LIMIT: tests force the recheck pass)
                 d->bp = g->sc.wide_threads ? BP_SCATTER_WIDE : BP_SCATTER;
+                if (d->bp == BP_SCATTER_WIDE && !env.bp_no_fast_start && rc == 0) {
+                    // gather pass 0 does not depend on the shot: made here once, on the device, by the kernel's own walk (bp_scatter_wide.hip)
+                    const std::vector<uint32_t> zero((size_t)g->bp.m_pad * 8, 0u);
+                    rc |= d->mem.upload(zero, &d->first_pass);
+                    if (rc == 0 && (qd_launch_bp_first_pass(d->bp_fine, g->sc, d->prior_g, const_cast<uint32_t *>(d->first_pass), nullptr) != hipSuccess ||
+                                    hipStreamSynchronize(nullptr) != hipSuccess))
+                        rc = -1;
+                }
             }
         }
         if (rc) { d->mem.release(); delete d; return fail(QD_EHIP, "device allocation failed while building the LLR grid"); }
@@ -1161,6 +1173,8 @@ extern "C" int qd_decoder_info(const qd_decoder *d, int32_t *info)
     info[3] = d->bp == BP_SCATTER_WIDE ? 2 : (d->bp == BP_SCATTER ? 1 : 0);
     return QD_OK;
 }
+
+extern "C" int qd_decoder_fast_start(const qd_decoder *d) { return d ? (d->first_pass != nullptr && d->prm.max_iter >= 1) : -1; }
 
 extern "C" int qd_decoder_postproc_kernel(const qd_decoder *d) { return d ? d->post : -1; }
 
@@ -1402,6 +1416,7 @@ static int launch_bp(qd_decoder *d, const DecodeArgs &a, int64_t B, hipStream_t 
             ScatArgs x{};
             x.prior_g = d->prior_g; x.grid_inv = std::ldexp(1.0f, -d->grid_k); x.m2_limit = d->m2_limit;
             x.recheck_list = d->recheck_list; x.recheck_count = recheck_count; x.recheck_cap = d->recheck_cap;
+            x.first_pass = d->first_pass;
             if (d->bp == BP_SCATTER_WIDE) HIP_TRY(qd_launch_bp_scatter_wide(d->bp_fine, g->sc, a1, x, B, s));
             else HIP_TRY(qd_launch_bp_scatter(d->bp_fine, g->sc, a1, x, B, s));
             a1.shot_list = d->recheck_list; a1.shot_count = recheck_count;

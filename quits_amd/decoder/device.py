@@ -91,8 +91,9 @@ class BatchDecoder:
         _lib.check(self._L.qd_decoder_info(self._h, arr))
         post = {0: "none", 1: "qd_osd0_sr_kernel", 2: "qd_osd0_reg_kernel", 3: "qd_osd0_reg_kernel<row form>", 4: "qd_osdcs_kernel",
                 5: "qd_lsd0_kernel"}.get(int(self._L.qd_decoder_postproc_kernel(self._h)), "?")
+        fast = hasattr(self._L, "qd_decoder_fast_start") and int(self._L.qd_decoder_fast_start(self._h)) == 1
         return {"llr_grid_bits": int(arr[0]), "llr_coarse_bits": int(arr[1]), "edge_kernel": bool(arr[2]),
-                "scatter_kernel": bool(arr[3]), "scatter_wide_kernel": int(arr[3]) == 2, "post_kernel": post}
+                "scatter_kernel": bool(arr[3]), "scatter_wide_kernel": int(arr[3]) == 2, "bp_fast_start": fast, "post_kernel": post}
 
     def set_workspace_limit(self, nbytes: int):
         """Cap the HBM message workspace of the one-message-per-edge BP kernel (product_sum / serial); no effect on the LDS kernel."""
