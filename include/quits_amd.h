@@ -92,7 +92,7 @@ typedef struct qd_params {
     double ms_scaling_factor;   /* not exposed by the reference wrapper -> ldpc default 1.0; 0 = 1-2^-it */
 } qd_params;
 
-int qd_version(void);                 /* 105 (105: qd_decoder_fast_start; 104: qd_circuit_* + qd_sample_circuit; 103: qd_decoder_post_head_start; 101: qd_graph_info wrote 12 entries; 102: 10 again + qd_graph_info_ex) */
+int qd_version(void);                 /* 106 (106: qd_circuit_create accepts the biased-noise opcodes Y_ERROR / PAULI_CHANNEL_1 / PAULI_CHANNEL_2, no new export; 105: qd_decoder_fast_start; 104: qd_circuit_* + qd_sample_circuit; 103: qd_decoder_post_head_start; 101: qd_graph_info wrote 12 entries; 102: 10 again + qd_graph_info_ex) */
 const char *qd_last_error(void);
 /* Number of visible HIP devices (0 if none): lets a host fail loudly before building anything. */
 int qd_device_count(void);
@@ -234,7 +234,9 @@ int qd_sample_dem(const qd_spmat *Ht, const qd_spmat *Lt, const double *priors, 
  *      separate_observables=True) returns, simulation.py:8-28), without gauge randomisation: exact when every detector and observable
  *      is deterministic, as in every QUITS circuit.  quits_amd/frame.py compiles the circuit text into `program` (int32 words; the layout
  *      and the frame rules are in its docstring), one threshold floor(p * 2^32) per distinct noise probability, and the measurement ring
- *      length max_lookback (>= the largest rec[-k] look-back and >= the widest measurement instruction).  Every index in the program is
+ *      length max_lookback (>= the largest rec[-k] look-back and >= the widest measurement instruction).  A Pauli channel
+ *      (PAULI_CHANNEL_1 / PAULI_CHANNEL_2, since version 106) names the first of 3 / 15 consecutive thresholds, floor(2^32 x) of the partial
+ *      sums of its probabilities, which must not decrease.  Every index in the program is
  *      checked here; QD_ECAPACITY when 8 * (2 nq + max_lookback + nobs) bytes exceed the kernel's 64 KiB of LDS per 64 shots. */
 int qd_circuit_create(const int32_t *program, int64_t program_len, int32_t nq, int32_t nmeas, int32_t ndet, int32_t nobs,
                       const uint32_t *thresholds, int32_t nthr, int32_t max_lookback, int32_t device, qd_circuit **out);
@@ -243,7 +245,7 @@ void qd_circuit_destroy(qd_circuit *c);
 int qd_circuit_info(const qd_circuit *c, int64_t *info);
 /* Shots shot0 .. shot0 + B - 1.  Noise site j of shot s fires iff r < threshold, r = word (j & 3) of
  * Philox4x32-10(key = (seed lo, seed hi), counter = (s lo, s hi, j >> 2, 1)); a depolarizing site's Pauli comes from the same r
- * (1 + r mod 3, or 1 + r mod 15 split as (v >> 2, v & 3)).  The stream depends on (seed, shot, site) only: calls with
+ * (1 + r mod 3, or 1 + r mod 15 split as (v >> 2, v & 3)); a Pauli channel applies component k iff T_{k-1} <= r < T_k.  The stream depends on (seed, shot, site) only: calls with
  * consecutive shot0 compose.  d_det: B x det_stride bytes (first ndet columns written), d_obs: B x obs_stride bytes.  Asynchronous. */
 int qd_sample_circuit(const qd_circuit *c, uint64_t seed, int64_t shot0, int64_t B, uint8_t *d_det, int64_t det_stride,
                       uint8_t *d_obs, int64_t obs_stride, void *stream);

@@ -370,7 +370,7 @@ static void scatter_walk(int m, const int32_t *row_ptr, const int32_t *col_idx, 
     }
 }
 
-extern "C" int qd_version(void) { return 105; }      // 105: qd_decoder_fast_start; 104: qd_circuit_* and qd_sample_circuit; 103: qd_decoder_post_head_start; 102: qd_graph_info fills 10 entries again, qd_graph_info_ex(g, info, n) the rest; 101: qd_decoder_postproc_kernel
+extern "C" int qd_version(void) { return 106; }      // 106: qd_circuit_create takes Y_ERROR / PAULI_CHANNEL_1 / PAULI_CHANNEL_2 programs (no new export); 105: qd_decoder_fast_start; 104: qd_circuit_* and qd_sample_circuit; 103: qd_decoder_post_head_start; 102: qd_graph_info fills 10 entries again, qd_graph_info_ex(g, info, n) the rest; 101: qd_decoder_postproc_kernel
 extern "C" const char *qd_last_error(void) { return g_err; }
 extern "C" int qd_device_count(void)
 {
@@ -1711,8 +1711,10 @@ struct qd_circuit {
     DevAllocs mem;
 };
 
-static int frame_check_program(const int32_t *p, int64_t len, int nq, int nmeas, int ndet, int nobs, int nthr, int ring, int64_t *nsites)
+static int frame_check_program(const int32_t *p, int64_t len, int nq, int nmeas, int ndet, int nobs, const uint32_t *thr, int nthr, int ring,
+                               int64_t *nsites, int *channels)
 {
+    *channels = 0;
     std::vector<int64_t> seen((size_t)nq, -1);     // qubit -> pc of the last gate part that used it
     int64_t pc = 0, sites = 0, meas = 0;
     int next_det = 0;
@@ -1726,8 +1728,8 @@ static int frame_check_program(const int32_t *p, int64_t len, int nq, int nmeas,
         switch (op) {
         case QD_FOP_R: case QD_FOP_H: width = 2 + (int64_t)n; break;
         case QD_FOP_CX: case QD_FOP_M: case QD_FOP_MX: case QD_FOP_MR: width = 2 + 2 * (int64_t)n; break;
-        case QD_FOP_XERR: case QD_FOP_ZERR: case QD_FOP_DEP1: width = 4 + (int64_t)n; break;
-        case QD_FOP_DEP2: width = 4 + 2 * (int64_t)n; break;
+        case QD_FOP_XERR: case QD_FOP_ZERR: case QD_FOP_DEP1: case QD_FOP_YERR: case QD_FOP_PC1: width = 4 + (int64_t)n; break;
+        case QD_FOP_DEP2: case QD_FOP_PC2: width = 4 + 2 * (int64_t)n; break;
         case QD_FOP_FLUSH: width = 3; break;
         default: width = 3 + (int64_t)n; break;                 // DET, OBS
         }
@@ -1747,12 +1749,21 @@ static int frame_check_program(const int32_t *p, int64_t len, int nq, int nmeas,
                     if (a[2 * i + 1] < 0 || a[2 * i + 1] >= ring) return bad("ring slot out of range");
                 meas += n;
             }
-        } else if (op <= QD_FOP_DEP2) {
+        } else if (op <= QD_FOP_DEP2 || op >= QD_FOP_YERR) {
+            if (op >= QD_FOP_YERR) *channels = 1;
+            const int K = op == QD_FOP_PC1 ? 3 : (op == QD_FOP_PC2 ? 15 : 1);      // thresholds the instruction reads: a[0] .. a[0] + K - 1
             if (a[0] < 0 || a[0] >= nthr) return bad("threshold index out of range");
+            if ((int64_t)a[0] + K > nthr) return bad("threshold table runs past the end of the thresholds");
+            for (int k = 1; k < K; ++k)
+                if (thr[a[0] + k] < thr[a[0] + k - 1]) return bad("threshold table must be non-decreasing (cumulative)");
             if (a[1] < 0 || (a[1] & 3)) return bad("first site must be a non-negative multiple of 4");
-            const int nt = op == QD_FOP_DEP2 ? 2 * n : n;
+            const bool pairs = op == QD_FOP_DEP2 || op == QD_FOP_PC2;
+            const int nt = pairs ? 2 * n : n;
             for (int i = 0; i < nt; ++i)
                 if (a[2 + i] < 0 || a[2 + i] >= nq) return bad("qubit out of range");
+            if (op == QD_FOP_PC2)
+                for (int i = 0; i < n; ++i)
+                    if (a[2 + 2 * i] == a[3 + 2 * i]) return bad("the two targets of a pair must differ");
             sites += n;
         } else if (op == QD_FOP_FLUSH) {
             if (n < 1 || n > QD_WAVE || a[0] < 0 || (a[0] & (QD_WAVE - 1)) || a[0] + n > ndet) return bad("bad detector block");
@@ -1786,7 +1797,8 @@ extern "C" int qd_circuit_create(const int32_t *program, int64_t program_len, in
         return fail(QD_ECAPACITY, "circuit needs %lld B of LDS per wavefront (%d qubits, %d-measurement ring, %d observables), budget %d B",
                     (long long)lds, nq, max_lookback, nobs, QD_FRAME_LDS_MAX);
     int64_t nsites = 0;
-    int rc = frame_check_program(program, program_len, nq, nmeas, ndet, nobs, nthr, max_lookback, &nsites);
+    int channels = 0;
+    int rc = frame_check_program(program, program_len, nq, nmeas, ndet, nobs, thresholds, nthr, max_lookback, &nsites, &channels);
     if (rc) return rc;
     if (hipSetDevice(device) != hipSuccess) return fail(QD_EHIP, "hipSetDevice(%d) failed", device);
     qd_circuit *c = new qd_circuit();
@@ -1797,6 +1809,7 @@ extern "C" int qd_circuit_create(const int32_t *program, int64_t program_len, in
         c->mem.release(); delete c; return fail(QD_EHIP, "device allocation/upload failed");
     }
     c->d.prog_len = (int)program_len; c->d.nq = nq; c->d.ring = max_lookback; c->d.nobs = nobs; c->d.lds_bytes = (int)lds;
+    c->d.channels = channels;
     c->nq = nq; c->nmeas = nmeas; c->ndet = ndet; c->nobs = nobs; c->nsites = nsites;
     *out = c;
     return QD_OK;

@@ -316,10 +316,14 @@ __device__ __forceinline__ void qd_philox4x32_10(uint32_t c0, uint32_t c1, uint3
 
 // Circuit program of the frame sampler (frame_sampler.hip); opcodes and layout as quits_amd/frame.py writes them.
 enum QdFrameOp { QD_FOP_R = 0, QD_FOP_H, QD_FOP_CX, QD_FOP_M, QD_FOP_MX, QD_FOP_MR, QD_FOP_XERR, QD_FOP_ZERR, QD_FOP_DEP1, QD_FOP_DEP2,
-                 QD_FOP_DET, QD_FOP_FLUSH, QD_FOP_OBS, QD_FOP_COUNT };
+                 QD_FOP_DET, QD_FOP_FLUSH, QD_FOP_OBS, QD_FOP_YERR, QD_FOP_PC1, QD_FOP_PC2, QD_FOP_COUNT };
+// Read-only device data addressed identically by every lane (a channel's threshold table): the constant address space makes the
+// compiler fetch it with scalar loads into SGPRs instead of one vector load per lane.
+typedef const __attribute__((address_space(4))) uint32_t QdUniformU32;
 #define QD_FRAME_LDS_MAX (64 * 1024)   // LDS of one wavefront (64 shots): 2 x nq frame words + ring words + observable words, 8 B each
 struct FrameDev {
     const int32_t *prog;
     const uint32_t *thr;
     int prog_len, nq, ring, nobs, lds_bytes;
+    int channels;               // the program holds Y_ERROR / PAULI_CHANNEL_1 / PAULI_CHANNEL_2: which kernel instantiation runs it
 };

@@ -102,7 +102,8 @@ def sliding_window_bposd_phenom_mem(zcheck_samples, hz, lz, W, F, eff_error_rate
 def sliding_window_bposd_circuit_mem(zcheck_samples, circuit, hz, lz, W, F, max_iter=2, osd_order=0,
                                      bp_method='product_sum', schedule='serial', osd_method='osd_cs', tqdm_on=False):
     """Circuit-level sliding-window BP-OSD on the space-time detector error model (reference bposd.py:54-86); same
-    signature and defaults.  `circuit` may be a stim.Circuit, the circuit text, or a quits_amd.dem.Circuit.
+    signature and defaults.  `circuit` may be a stim.Circuit, the circuit text, or a quits_amd.dem.Circuit.  A circuit with
+    PAULI_CHANNEL_1/2 has a detector error model only as Stim's approximation: pass `Circuit(text, approximate_disjoint_errors=True)`.
 
     :return logical_z_pred: int64 (# trials, # logical qubits)
     """

@@ -255,7 +255,8 @@ class CircuitSampler:
     """Device-side circuit-level sampler (qd_sample_circuit): a Pauli-frame simulation of the circuit, what the reference gets from
     `circuit.compile_detector_sampler().sample(shots, separate_observables=True)` (simulation.py:8-28).  Same surface as DemSampler.
     `circuit`: circuit text, quits_amd.dem.Circuit, stim.Circuit, or a quits_amd.frame.CompiledCircuit.  The semantics, the random
-    stream and its assumption (deterministic detectors) are in quits_amd/frame.py."""
+    stream and its assumption (deterministic detectors) are in quits_amd/frame.py.  Biased noise (Y_ERROR, PAULI_CHANNEL_1,
+    PAULI_CHANNEL_2) is sampled exactly and needs no `approximate_disjoint_errors`: that setting concerns detector error models only."""
 
     def __init__(self, circuit, device: Optional[int] = None):
         from ..frame import CompiledCircuit, compile_circuit

@@ -512,9 +512,17 @@ def _freeze(v):
 
 def _circuit_fingerprint(circuit):
     """sha1 of the circuit text (stim.Circuit, quits_amd.dem.Circuit and plain text all print as Stim text); an object that is
-    already a detector error model goes by its printed form as well."""
+    already a detector error model goes by its printed form as well.  A quits_amd.dem.Circuit that carries
+    `approximate_disjoint_errors` gives another detector error model than its bare text (which has none, if the circuit holds a
+    Pauli channel), so the setting is part of the fingerprint."""
     import hashlib
-    return hashlib.sha1(str(circuit).encode()).hexdigest()
+    h = hashlib.sha1(str(circuit).encode())
+    setting = getattr(circuit, "approximate_disjoint_errors", False)
+    if isinstance(setting, (bool, int, float)):
+        setting = float(setting)                             # True and 1.0 are the same threshold
+    if setting:                                              # (some other object's attribute of that name goes by its printed form)
+        h.update(("\0approximate_disjoint_errors=%r" % (setting,)).encode())
+    return h.hexdigest()
 
 
 def _matrix_fingerprint(mat):

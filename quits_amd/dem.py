@@ -9,6 +9,13 @@ the build image).  Semantics restated from Stim's error analyser (
 * X_ERROR/Z_ERROR(p): one mechanism;  DEPOLARIZE1(p): X, Y, Z components, each with the
   independent-equivalent probability  q = 1/2 - 1/2*sqrt(1 - 4p/3);  DEPOLARIZE2(p): 15 components
   with  q = 1/2 - 1/2*(1 - 16p/15)**(1/8);
+* Y_ERROR(p): one mechanism, the X and the Z symptom together;
+* PAULI_CHANNEL_1(px, py, pz) / PAULI_CHANNEL_2(pIX .. pZZ): the components of one channel exclude each other, so they are not
+  independent mechanisms and Stim refuses the conversion unless the caller passes `approximate_disjoint_errors`; so does
+  `circuit_to_dem`.  With `approximate_disjoint_errors=True` (or a threshold in (0, 1]) every component becomes an independent
+  mechanism with its STATED probability -- symptoms X, Y = X ^ Z, Z, or the 15 products as for DEPOLARIZE2 -- and a component
+  above the threshold is a ValueError (True = threshold 1).  The error is of relative order p.  This is Stim's documented
+  approximation restated from memory, like the rest of this file; it is not pinned against Stim (DESIGN.md section 6);
 * mechanisms with identical (detectors, observables) symptom combine  p <- p(1-q) + q(1-p);
   empty symptoms are dropped;
 * errors are emitted sorted lexicographically by target list, detectors before observables.  That is
@@ -100,7 +107,8 @@ def _bits(x: int) -> List[int]:
     return out
 
 
-_NOISE = ("X_ERROR", "Z_ERROR", "DEPOLARIZE1", "DEPOLARIZE2")
+_NOISE = ("X_ERROR", "Z_ERROR", "DEPOLARIZE1", "DEPOLARIZE2", "Y_ERROR")     # one probability per instruction: what the structure cache replays
+_CHANNELS = ("PAULI_CHANNEL_1", "PAULI_CHANNEL_2")                          # one probability per component: never cached
 
 # Structure cache.  The reference's notebooks call the decoder once per physical error rate (doc/06B_end_to_end_demo_bb.ipynb cell 5)
 # with circuits that differ in nothing but the noise arguments, and the analysis below is pure Python (11 s for the QLP [[1020,136]]
@@ -151,7 +159,7 @@ def _structure_key(ops, num_meas, num_det, num_obs) -> str:
 
 def _mechanism_probability(op) -> float:
     """Independent-equivalent probability of ONE component of the noise instruction (see the module docstring)."""
-    if op.name in ("X_ERROR", "Z_ERROR"):
+    if op.name in ("X_ERROR", "Z_ERROR", "Y_ERROR"):
         return op.arg
     if op.name == "DEPOLARIZE1":
         if op.arg > 0.75:
@@ -202,10 +210,39 @@ def _replay_probabilities(st: dict, ops) -> np.ndarray:
     return prob
 
 
-def circuit_to_dem(text: str) -> DetectorErrorModel:
-    """Backward Pauli-sensitivity analysis of a QUITS-dialect Stim circuit."""
-    ops, num_meas, num_det, num_obs = flatten(text)
-    cap = _struct_cap()
+def _disjoint_threshold(approximate_disjoint_errors) -> float:
+    """Stim's `approximate_disjoint_errors` argument as a threshold: False -> 0.0 (refuse), True -> 1.0, a float in (0, 1] itself."""
+    if approximate_disjoint_errors is False or approximate_disjoint_errors is None:
+        return 0.0
+    if approximate_disjoint_errors is True:
+        return 1.0
+    t = float(approximate_disjoint_errors)
+    if t == 0.0:
+        return 0.0
+    if not 0.0 < t <= 1.0:
+        raise ValueError("approximate_disjoint_errors must be a bool or a threshold in (0, 1], got %r" % (approximate_disjoint_errors,))
+    return t
+
+
+def circuit_to_dem(text: str, approximate_disjoint_errors=False) -> DetectorErrorModel:
+    """Backward Pauli-sensitivity analysis of a QUITS-dialect Stim circuit.  PAULI_CHANNEL_1/2 need `approximate_disjoint_errors`
+    (True, or the largest component probability to accept), as in Stim; see the module docstring."""
+    ops, num_meas, num_det, num_obs = flatten(text, channels=True)
+    thr = _disjoint_threshold(approximate_disjoint_errors)
+    channels = False
+    for op in ops:
+        if op.name in _CHANNELS:
+            channels = True
+            if thr == 0.0:
+                raise NotImplementedError(
+                    "%s has mutually exclusive components: a detector error model of it exists only as an approximation; pass "
+                    "approximate_disjoint_errors=True (or a threshold) as in Stim, e.g. Circuit(text, approximate_disjoint_errors=True)"
+                    % op.name)
+            if max(op.args) > thr:
+                raise ValueError("%s component probability %r is above the approximate_disjoint_errors threshold %r"
+                                 % (op.name, max(op.args), thr))
+    # the structure cache replays ONE probability per noise instruction; a channel has one per component, so it takes the full pass
+    cap = 0 if channels else _struct_cap()
     skey = _structure_key(ops, num_meas, num_det, num_obs) if cap > 0 else None
     st = None
     if skey is not None:
@@ -291,6 +328,23 @@ def circuit_to_dem(text: str) -> DetectorErrorModel:
         elif name == "Z_ERROR":
             for q in t:
                 add(zs[q], op.arg)
+        elif name == "Y_ERROR":
+            for q in t:
+                add(xs[q] ^ zs[q], op.arg)
+        elif name == "PAULI_CHANNEL_1":
+            px, py, pz = op.args
+            for q in t:
+                x, z = xs[q], zs[q]
+                add(x, px)
+                add(x ^ z, py)
+                add(z, pz)
+        elif name == "PAULI_CHANNEL_2":
+            for i in range(0, len(t), 2):
+                a, b = t[i], t[i + 1]
+                pa = (empty, xs[a], xs[a] ^ zs[a], zs[a])
+                pb = (empty, xs[b], xs[b] ^ zs[b], zs[b])
+                for k in range(1, 16):                 # IX, IY, IZ, XI, .. ZZ: first target k >> 2, second k & 3
+                    add(pa[k >> 2] ^ pb[k & 3], op.args[k - 1])
         elif name == "DEPOLARIZE1":
             q1 = _mechanism_probability(op)
             for q in t:
@@ -335,16 +389,33 @@ def circuit_to_dem(text: str) -> DetectorErrorModel:
 
 
 class Circuit(str):
-    """Circuit text with the one Stim method the decoder path calls (`decoder/base.py:151`)."""
+    """Circuit text with the one Stim method the decoder path calls (`decoder/base.py:151`).
 
+    `approximate_disjoint_errors` is Stim's argument of that method (False, True or a threshold), kept on the instance because the
+    decoder entry points call `detector_error_model(decompose_errors=False)` and nothing else: a biased-noise circuit
+    (PAULI_CHANNEL_1/2) is decoded at circuit level as `Circuit(text, approximate_disjoint_errors=True)`."""
+
+    approximate_disjoint_errors = False
     _dem_cache = None
 
-    def detector_error_model(self, decompose_errors: bool = False, **_ignored) -> DetectorErrorModel:
+    def __new__(cls, text="", approximate_disjoint_errors=None):
+        self = super().__new__(cls, text)
+        if approximate_disjoint_errors is None:                 # a copy of a Circuit keeps that circuit's setting
+            approximate_disjoint_errors = getattr(text, "approximate_disjoint_errors", False)
+        self.approximate_disjoint_errors = approximate_disjoint_errors
+        return self
+
+    def detector_error_model(self, decompose_errors: bool = False, approximate_disjoint_errors=None, **_ignored) -> DetectorErrorModel:
         if decompose_errors:
             raise NotImplementedError("decompose_errors=True is not used by the QUITS decoder path")
+        if approximate_disjoint_errors is None:
+            approximate_disjoint_errors = self.approximate_disjoint_errors
         if self._dem_cache is None:
-            self._dem_cache = circuit_to_dem(str(self))
-        return self._dem_cache
+            self._dem_cache = {}
+        key = _disjoint_threshold(approximate_disjoint_errors)
+        if key not in self._dem_cache:
+            self._dem_cache[key] = circuit_to_dem(str(self), approximate_disjoint_errors)
+        return self._dem_cache[key]
 
     @property
     def num_detectors(self) -> int:

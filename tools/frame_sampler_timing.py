@@ -2,10 +2,17 @@
 """Time the circuit-level frame sampler against the DEM sampler and the headline decode on the same shots.
 
     python tools/frame_sampler_timing.py [--shots 1048576] [--reps 5] [--out profiles/frame_sampler_timing.json]
+    python tools/frame_sampler_timing.py --channels [--parent-lib OLD/libquits_amd.so] [--out profiles/frame_sampler_channels_timing.json]
 
 Circuit bb144_custom_r12_p0.003.  After one warm-up of each, device events time `reps` calls of CircuitSampler.sample and
 DemSampler.sample (2^20 shots each) and one headline decode (minimum_sum, parallel, max_iter=50, OSD-0, the whole history as one
-window) of the circuit-sampled shots; the median call is reported.  Prints one JSON line."""
+window) of the circuit-sampled shots; the median call is reported.  Prints one JSON line.
+
+--channels times the biased-noise path instead: the same circuit with every DEPOLARIZE1(p) rewritten as PAULI_CHANNEL_1(p/3, p/3, p/3)
+and every DEPOLARIZE2(p) as the uniform 15-entry PAULI_CHANNEL_2 -- the same distribution through the threshold tables -- next to the
+unchanged text, `shots` shots each, median and min - max of `reps` calls after a warm-up.  With --parent-lib the unchanged text is timed
+with that library too (an older build of libquits_amd.so, which need not know the channel opcodes).  Every measurement runs in a child
+process of its own (QUITS_AMD_LIB names the library), one after the other; this process does not touch the GPU."""
 import argparse
 import json
 import os
@@ -34,12 +41,75 @@ def timed(fn, reps):
     return out, float(np.median(ms)), ms
 
 
+def _stats(ms):
+    return dict(median_ms=round(float(np.median(ms)), 3), min_ms=round(min(ms), 3), max_ms=round(max(ms), 3), all_ms=[round(x, 3) for x in ms])
+
+
+def sampler_only(a):
+    """Child of --channels: time CircuitSampler.sample on the unchanged text and, if this library knows the channel opcodes, on the
+    rewritten one.  Prints one JSON line."""
+    import torch
+    import channel_circuits
+    from quits_amd import _lib
+    from quits_amd.decoder.device import CircuitSampler
+    name = "bb144_custom_r12_p0.003"
+    text = helpers.circuit_text(name)
+    version = int(_lib.load().qd_version())
+    row = dict(library=os.path.basename(_lib.LIB_PATH), library_version=version, device=torch.cuda.get_device_name(0))
+    texts = [("depolarize", text)] + ([("pauli_channel", channel_circuits.uniform(text))] if version >= 106 else [])
+    for key, t in texts:
+        cs = CircuitSampler(t)
+        cs.sample(a.shots, seed=1)                                 # warm-up
+        _, _, ms = timed(lambda: cs.sample(a.shots, seed=7), a.reps)
+        row[key] = dict(_stats(ms), info=cs.info())
+    torch.cuda.synchronize()
+    print(json.dumps(row), flush=True)
+
+
+def channels(a):
+    import subprocess
+
+    def child(lib):
+        env = dict(os.environ)
+        if lib:
+            env["QUITS_AMD_LIB"] = os.path.abspath(lib)
+        out = subprocess.run([sys.executable, os.path.abspath(__file__), "--sampler-only", "--shots", str(a.shots), "--reps", str(a.reps)],
+                             env=env, capture_output=True, text=True, timeout=600)
+        if out.returncode != 0:
+            raise RuntimeError("timing child failed (%d): %s" % (out.returncode, out.stderr[-2000:]))
+        return json.loads(out.stdout.strip().splitlines()[-1])
+    row = dict(circuit="bb144_custom_r12_p0.003", shots=a.shots, reps=a.reps,
+               rewrite="DEPOLARIZE1(p) -> PAULI_CHANNEL_1(p/3 x 3), DEPOLARIZE2(p) -> PAULI_CHANNEL_2(p/15 x 15)")
+    if a.parent_lib:
+        row["parent_library"] = child(a.parent_lib)
+    row["this_library"] = child(None)
+    new = row["this_library"]
+    row["pauli_channel_over_depolarize"] = round(new["pauli_channel"]["median_ms"] / new["depolarize"]["median_ms"], 4)
+    if a.parent_lib:
+        old = row["parent_library"]["depolarize"]
+        row["depolarize_over_parent"] = round(new["depolarize"]["median_ms"] / old["median_ms"], 4)
+        row["depolarize_within_parent_range"] = bool(new["depolarize"]["median_ms"] <= old["max_ms"])
+    line = json.dumps(row)
+    print(line, flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shots", type=int, default=1 << 20)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--channels", action="store_true", help="time the PAULI_CHANNEL_1/2 rewrite next to the unchanged circuit")
+    ap.add_argument("--parent-lib", default=None, help="with --channels: an older libquits_amd.so to time the unchanged circuit with")
+    ap.add_argument("--sampler-only", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.sampler_only:
+        return sampler_only(a)
+    if a.channels:
+        return channels(a)
     import torch
     from quits_amd.decoder.base import detector_error_model_to_matrix
     from quits_amd.decoder.device import BatchDecoder, CircuitSampler, DemSampler, WindowGraph
