@@ -27,7 +27,7 @@ extern "C" {
 #define QD_EINVAL (-1)      /* bad argument                                             */
 #define QD_EUNSUPPORTED (-2)/* legal for ldpc, not implemented on the device path      */
 #define QD_EHIP (-3)        /* HIP runtime error                                        */
-#define QD_ECAPACITY (-4)   /* graph does not fit the kernels' on-chip layout          */
+#define QD_ECAPACITY (-4)   /* graph beyond the kernels' limits (m > 32767, n > 65000, row / column weight; OSD row state) */
 
 /* bp_method / schedule / osd_method: the string options of quits/decoder/bposd.py:27-29 as integers */
 #define QD_BP_PRODUCT_SUM 0
@@ -65,6 +65,10 @@ typedef struct qd_circuit qd_circuit;   /* compiled circuit program of the frame
 /* qd_params.reserved: keep the channel LLRs as (float)log((1-p)/p) instead of putting them on a binary grid (round-1
  * arithmetic: float rounding in every sum).  Validation aid; see qd_decoder_info. */
 #define QD_FLAG_RAW_LLR 2
+/* qd_params.reserved: decode a window that fits the CU the way an off-chip window is decoded (see qd_graph_create): every BP method and
+ * schedule in the one-message-per-edge kernel -- flooding min-sum on the LLR grid with the exactness certificate and the coarse-grid redo
+ * pass -- and OSD-0 in qd_osd0_offchip_kernel.  Same results as the default kernels, bit for bit.  Validation aid. */
+#define QD_FLAG_OFF_CHIP 4
 
 /* Validation switches: environment variables that make a graph (G: read by qd_graph_create) or a decoder (D: read by qd_decoder_create)
  * take an alternative that the tests compare bit for bit against the default.  None changes a result and none is needed in normal
@@ -92,7 +96,7 @@ typedef struct qd_params {
     double ms_scaling_factor;   /* not exposed by the reference wrapper -> ldpc default 1.0; 0 = 1-2^-it */
 } qd_params;
 
-int qd_version(void);                 /* 106 (106: qd_circuit_create accepts the biased-noise opcodes Y_ERROR / PAULI_CHANNEL_1 / PAULI_CHANNEL_2, no new export; 105: qd_decoder_fast_start; 104: qd_circuit_* + qd_sample_circuit; 103: qd_decoder_post_head_start; 101: qd_graph_info wrote 12 entries; 102: 10 again + qd_graph_info_ex) */
+int qd_version(void);                 /* 107 (107: off-chip windows decode, QD_FLAG_OFF_CHIP, QD_POST_OSD0_OFFCHIP, no new export; 106: qd_circuit_create accepts the biased-noise opcodes Y_ERROR / PAULI_CHANNEL_1 / PAULI_CHANNEL_2, no new export; 105: qd_decoder_fast_start; 104: qd_circuit_* + qd_sample_circuit; 103: qd_decoder_post_head_start; 101: qd_graph_info wrote 12 entries; 102: 10 again + qd_graph_info_ex) */
 const char *qd_last_error(void);
 /* Number of visible HIP devices (0 if none): lets a host fail loudly before building anything. */
 int qd_device_count(void);
@@ -100,12 +104,19 @@ int qd_device_count(void);
 /* ---- graph: replaces the sparse-matrix half of BpOsdDecoder.__init__ (call sites
  *      decoder/sliding_window.py:61,69,149,152).  CSR of the window check matrix (m detectors x n faults, column
  *      indices ascending in each row) and the n channel probabilities (`channel_probs`, sliding_window.py:148,151;
- *      pass n copies of `error_rate` for the phenomenological variant, bposd.py:43,49). */
+ *      pass n copies of `error_rate` for the phenomenological variant, bposd.py:43,49).
+ *      Limits: m <= 32767, n <= 65000, row weight <= 255, column weight <= 16 (QD_ECAPACITY beyond).  A window whose BP state the CU's
+ *      LDS cannot hold (16 bytes per detector + 4 per fault > 160 KB, or more than 4094 detectors) is an OFF-CHIP window (since version
+ *      107; QD_ECAPACITY before): BP of every method and schedule runs in the one-message-per-edge kernel, messages in HBM -- flooding
+ *      min-sum with ms_scaling_factor = 1 on the LLR grid, certified per shot and decoded again on the coarse grid exactly as
+ *      qd_decoder_info describes -- and OSD-0 (osd_0, or osd_cs / osd_e of order 0) in qd_osd0_offchip_kernel, which needs 17 bytes of LDS
+ *      per detector (m <= 4608 fits for any n; QD_ECAPACITY from qd_decoder_create beyond what fits).  Order > 0 and BP-LSD are
+ *      QD_EUNSUPPORTED there. */
 int qd_graph_create(int32_t m, int32_t n, const int32_t *row_ptr, const int32_t *col_idx, const double *priors,
                     int32_t device, qd_graph **out);
 void qd_graph_destroy(qd_graph *g);
-/* info[0..9] = m, n, nnz, max row weight, max column weight, BP block threads, BP LDS bytes, OSD block threads,
- *              OSD LDS bytes, GF(2) rank of the matrix.  Exactly 10 entries are written (as in library version 100; version 101
+/* info[0..9] = m, n, nnz, max row weight, max column weight, BP block threads, BP LDS bytes (both 0: an off-chip window), OSD block
+ *              threads, OSD LDS bytes, GF(2) rank of the matrix.  Exactly 10 entries are written (as in library version 100; version 101
  *              wrote 12 -- callers built against that header should move to qd_graph_info_ex). */
 int qd_graph_info(const qd_graph *g, int32_t *info);
 /* The same with the caller saying how many int32 entries `info` has room for; entries 10, 11 = modelled LDS cycles of one pass of
@@ -141,6 +152,7 @@ int qd_decoder_fast_start(const qd_decoder *d);
 #define QD_POST_OSD_W_OLD 3     /* OSD-CS / OSD-E by row (qd_osd0_reg_kernel<.., true>, osd_kernels.hip): windows the panel kernel does not take */
 #define QD_POST_OSD_CS_PANEL 4  /* OSD-CS / OSD-E, round 5: qd_osdcs_kernel (osd_cs.hip), one panel of 64 sorted columns at a time */
 #define QD_POST_LSD 5           /* BP-LSD: qd_lsd0_kernel (lsd_kernels.hip)                                                      */
+#define QD_POST_OSD0_OFFCHIP 6  /* OSD-0 of an off-chip window (or QD_FLAG_OFF_CHIP): qd_osd0_offchip_kernel (osd_offchip.hip)   */
 int qd_decoder_postproc_kernel(const qd_decoder *d);
 /* Pre-size the device workspace for batches of up to max_batch shots (otherwise grown on demand, which
  * synchronises). */

@@ -68,10 +68,13 @@ __device__ __forceinline__ uint32_t qd_lanes_or(uint32_t v, uint32_t (*red)[64],
 
 // D: bound on the column weight the instantiation unrolls for (4, 8 or QD_MAX_COL_DEG; registers: five arrays of D in the serial schedule)
 //    LP: serial schedule with the rows' running prefixes in LDS slots (GenGraphDev::nslots > 0)
+//    CERT: flooding min-sum on the LLR grid with the exactness certificate of bp_kernels.hip (off-chip windows, QD_FLAG_OFF_CHIP): the bit pass
+//          keeps S_j = |llr0_j| + sum |c2b| per fault and a shot with some S_j >= a.s_limit is parked on a.redo_list instead of returning a result;
+//          the redo pass (a.shot_list: column c of the launch holds shot a.shot_list[shot0 + c], the coarse-grid LLRs in llr0) decodes it again
 #ifndef QD_GEN_WPE
 #define QD_GEN_WPE 1          // wavefronts per SIMD the serial instantiations for column weight <= 8 are budgeted for (1: no bound)
 #endif
-template <int METHOD, int SCHED, int G, int D, bool LP>
+template <int METHOD, int SCHED, int G, int D, bool LP, bool CERT = false>
 __global__ void __launch_bounds__(64 * G, (SCHED == QD_SCHEDULE_SERIAL && D <= 8) ? QD_GEN_WPE : 1) qd_bp_edge_kernel(GenGraphDev g, const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
                                                             const int32_t *__restrict__ cp, const int32_t *__restrict__ ri,
                                                             const int32_t *__restrict__ c2r, const float *__restrict__ llr0,
@@ -80,6 +83,12 @@ __global__ void __launch_bounds__(64 * G, (SCHED == QD_SCHEDULE_SERIAL && D <= 8
 {
     __shared__ uint32_t red[G][64];
     if (st.in_count) nshots = *st.in_count;                          // a later launch of the staged serial schedule: the survivors of the one before
+    if (CERT && a.shot_list) {                                       // redo pass: the parked shots from shot0 on, at most the columns of this launch
+        const int left = min(nshots, max(*a.shot_count - (int)shot0, 0));
+        const int c = (int)blockIdx.x * 64 + (int)threadIdx.x;
+        if (threadIdx.x < 64 && c >= left && c < nshots) w.slot[c] = -1;   // (the publishing kernel walks every column of the launch)
+        nshots = left;
+    }
     if ((int)blockIdx.x * 64 >= nshots) return;
     extern __shared__ float pls[];                                   // [nslots][64]  (LP)
     const int lane = threadIdx.x & 63;
@@ -88,7 +97,7 @@ __global__ void __launch_bounds__(64 * G, (SCHED == QD_SCHEDULE_SERIAL && D <= 8
     bool active = ls < nshots;
     // (the shot index is worked out where it is used, at the two ends: held across the sweeps it costs the registers that decide whether five
     //  workgroups fit a CU or four -- 93 -> 97 registers measured 55 -> 76 ms per launch)
-#define QD_GEN_SHOT (st.in_shot ? (int64_t)st.in_shot[lsc] : shot0 + lsc)
+#define QD_GEN_SHOT ((CERT && a.shot_list) ? (int64_t)a.shot_list[shot0 + lsc] : (st.in_shot ? (int64_t)st.in_shot[lsc] : shot0 + lsc))
     // workspace: [index][S shots] -- wavefronts advance through the graph at nearly the same pace, so at any moment they
     // touch the same few index planes: the pages in use are shared by all of them.  (A per-wavefront tiling
     // [tile][index][64] keeps each wavefront's data contiguous but multiplies the pages in flight by the number of
@@ -106,7 +115,7 @@ __global__ void __launch_bounds__(64 * G, (SCHED == QD_SCHEDULE_SERIAL && D <= 8
     // ---- window syndrome (sliding_window.py:168-169)
     if (active && wv == 0) w.slot[ls] = -1;
     if (st.it0 == 0) {               // (a later launch finds syndrome and messages in its planes)
-    const int64_t shot = shot0 + lsc;
+    const int64_t shot = (CERT && a.shot_list) ? (int64_t)a.shot_list[shot0 + lsc] : shot0 + lsc;
     const uint8_t *det = a.det + shot * a.det_stride + a.det_offset;
     const uint8_t *upd = a.upd ? a.upd + shot * a.upd_stride : nullptr;
     uint32_t any = 0;
@@ -122,7 +131,7 @@ __global__ void __launch_bounds__(64 * G, (SCHED == QD_SCHEDULE_SERIAL && D <= 8
         if (wv == 0) {
             uint32_t *out = a.err_bits + shot * g.out_words;
             for (int x = 0; x < g.out_words; ++x) out[x] = 0u;
-            a.status[shot] = (1 << 16) | (1 << 19);
+            a.status[shot] = (1 << 16) | (1 << 19) | (CERT ? a.status_or : 0);
         }
         active = false;
     }
@@ -140,6 +149,7 @@ __global__ void __launch_bounds__(64 * G, (SCHED == QD_SCHEDULE_SERIAL && D <= 8
     if (G > 1) __syncthreads();
     }
     const bool ran = active;
+    bool trip = false;                                               // CERT: some S_j of this shot reached a.s_limit (this wavefront's columns)
 
     int iters = 0, converged = 0;
     for (int it = st.it0 + 1; it <= st.it_end; ++it) {
@@ -253,6 +263,13 @@ __global__ void __launch_bounds__(64 * G, (SCHED == QD_SCHEDULE_SERIAL && D <= 8
                 for (int k = 0; k < D; ++k)
                     if (k < deg) cv[k] = c2b[(size_t)c2r[c0 + k] * S];
                 float temp = llr0[j];
+                if (CERT) {
+                    float sabs = fabsf(temp);                        // a sum of non-negative grid values: exact whenever it is below the limit
+#pragma unroll
+                    for (int k = 0; k < D; ++k)
+                        if (k < deg) sabs += fabsf(cv[k]);
+                    trip |= sabs >= a.s_limit;
+                }
 #pragma unroll
                 for (int k = 0; k < D; ++k)
                     if (k < deg) { pre[k] = temp; temp += cv[k]; }
@@ -445,6 +462,21 @@ __global__ void __launch_bounds__(64 * G, (SCHED == QD_SCHEDULE_SERIAL && D <= 8
             if (active && wv == 0) st.out_shot[dcol] = (int32_t)QD_GEN_SHOT;
         }
     }
+    // ---- grid arithmetic: did the bound hold?  A shot that left the grid is parked for the redo pass if its list has room (and returns
+    // nothing from this pass), else it keeps this result and is flagged (quits_amd.h, QD_STATUS_INEXACT)
+    int status_or = 0;
+    if (CERT) {
+        status_or = a.status_or;
+        const uint32_t tripped = qd_lanes_or<G>((ran && trip) ? 1u : 0u, red, wv, lane);
+        uint32_t parked = 0u;
+        if (tripped && a.redo_list && wv == 0) {
+            const int at = atomicAdd(a.redo_count, 1);
+            if (at < a.redo_cap) { a.redo_list[at] = (int32_t)QD_GEN_SHOT; parked = 1u; }
+        }
+        parked = qd_lanes_or<G>(parked, red, wv, lane);
+        if (parked) return;
+        if (tripped) status_or |= QD_STATUS_INEXACT;
+    }
     // ---- hard decision, packed by fault index
     if (!ran || (!st.last && active)) return;
     const int64_t shot = QD_GEN_SHOT;
@@ -456,7 +488,7 @@ __global__ void __launch_bounds__(64 * G, (SCHED == QD_SCHEDULE_SERIAL && D <= 8
         out[x] = word;
     }
     if (wv != 0) return;
-    a.status[shot] = iters | (converged << 16);
+    a.status[shot] = iters | (converged << 16) | status_or;
     if (!converged && a.want_llr) {
         const int slot = atomicAdd(a.fail_count, 1);
         a.fail_list[slot] = (int32_t)shot;
@@ -717,7 +749,7 @@ __global__ void __launch_bounds__(256) qd_publish_llr_kernel(const float *__rest
 
 #define QD_GEN_G 8            // wavefronts per 64 shots in the flooding schedule
 
-template <int METHOD, int SCHED, int G, int D>
+template <int METHOD, int SCHED, int G, int D, bool CERT = false>
 static hipError_t launch_kd(const GenGraphDev &g, const DecodeArgs &a, const GenWs &w, int64_t shot0, int nshots, const GenStage &st, hipStream_t s)
 {
     const dim3 grid((unsigned)((nshots + 63) / 64)), block(64 * G);
@@ -725,21 +757,21 @@ static hipError_t launch_kd(const GenGraphDev &g, const DecodeArgs &a, const Gen
         hipLaunchKernelGGL((qd_bp_edge_kernel<METHOD, SCHED, G, D, SCHED == QD_SCHEDULE_SERIAL>), grid, block, (size_t)g.nslots * 256, s, g, g.rp, g.ci,
                            g.cp, g.ri, g.c2r, g.llr0, g.srec, a, w, shot0, nshots, st);
     else
-        hipLaunchKernelGGL((qd_bp_edge_kernel<METHOD, SCHED, G, D, false>), grid, block, 0, s, g, g.rp, g.ci,
+        hipLaunchKernelGGL((qd_bp_edge_kernel<METHOD, SCHED, G, D, false, CERT>), grid, block, 0, s, g, g.rp, g.ci,
                            g.cp, g.ri, g.c2r, g.llr0, g.srec, a, w, shot0, nshots, st);
     return hipGetLastError();
 }
 
-template <int METHOD, int SCHED, int G>
+template <int METHOD, int SCHED, int G, bool CERT = false>
 static hipError_t launch_k(const GenGraphDev &g, int max_cdeg, const DecodeArgs &a, const GenWs &w, int64_t shot0, int nshots, const GenStage &st, hipStream_t s)
 {
     switch (qd_gen_unroll(max_cdeg)) {
-    case 4: return launch_kd<METHOD, SCHED, G, 4>(g, a, w, shot0, nshots, st, s);
+    case 4: return launch_kd<METHOD, SCHED, G, 4, CERT>(g, a, w, shot0, nshots, st, s);
 #if QD_GEN_D6
-    case 6: return launch_kd<METHOD, SCHED, G, 6>(g, a, w, shot0, nshots, st, s);
+    case 6: return launch_kd<METHOD, SCHED, G, 6, CERT>(g, a, w, shot0, nshots, st, s);
 #endif
-    case 8: return launch_kd<METHOD, SCHED, G, 8>(g, a, w, shot0, nshots, st, s);
-    default: return launch_kd<METHOD, SCHED, G, QD_MAX_COL_DEG>(g, a, w, shot0, nshots, st, s);
+    case 8: return launch_kd<METHOD, SCHED, G, 8, CERT>(g, a, w, shot0, nshots, st, s);
+    default: return launch_kd<METHOD, SCHED, G, QD_MAX_COL_DEG, CERT>(g, a, w, shot0, nshots, st, s);
     }
 }
 
@@ -774,6 +806,8 @@ hipError_t qd_launch_bp_general(const GenGraphDev &g, const BpGraphDev &bg, cons
         if (bp_method == QD_BP_PRODUCT_SUM)
             e = schedule == QD_SCHEDULE_PARALLEL ? launch_k<QD_BP_PRODUCT_SUM, QD_SCHEDULE_PARALLEL, QD_GEN_G>(g, cd, a, wk, shot0, nshots, st, s)
                                                  : launch_k<QD_BP_PRODUCT_SUM, QD_SCHEDULE_SERIAL, QD_GEN_GS>(g, cd, a, wk, shot0, nshots, st, s);
+        else if (schedule == QD_SCHEDULE_PARALLEL && a.s_limit > 0.f)   // on the LLR grid with the exactness certificate (off-chip windows)
+            e = launch_k<QD_BP_MINIMUM_SUM, QD_SCHEDULE_PARALLEL, QD_GEN_G, true>(g, cd, a, wk, shot0, nshots, st, s);
         else
             e = schedule == QD_SCHEDULE_PARALLEL ? launch_k<QD_BP_MINIMUM_SUM, QD_SCHEDULE_PARALLEL, QD_GEN_G>(g, cd, a, wk, shot0, nshots, st, s)
                                                  : launch_k<QD_BP_MINIMUM_SUM, QD_SCHEDULE_SERIAL, QD_GEN_GS>(g, cd, a, wk, shot0, nshots, st, s);

@@ -27,204 +27,11 @@
 //                        rows in registers with a write-through LDS mirror, ~80 KB of LDS -> two workgroups per CU.
 //   qd_osd0_full_kernel  sorts every column up front, all state in LDS, one workgroup per CU; used when a window has
 //                        more than 2048 detectors.  Same results by construction: both consume the same column order.
+// (The full kernel's elimination, qd_osd_eliminate, lives in osd_shared.h: qd_osd0_offchip_kernel, osd_offchip.hip, runs it tier by tier
+//  on the windows neither kernel here takes.)
 #include "osd_shared.h"
 #include <cstdlib>
 #include <algorithm>
-
-struct OsdLds {
-    uint64_t *q;          // Q planes resident in LDS
-    uint64_t *tb;         // [m_pad] image of the 64 batch columns
-    uint8_t *sp;          // [m_pad] transformed syndrome
-    int16_t *rowpiv;      // [m_pad] row -> pivot order or -1
-    uint16_t *prow;       // [m_pad] pivot order -> row
-    uint32_t *pcol;       // [m_pad] pivot order -> fault
-    uint32_t *pairs;      // [64 * max_cdeg] column-in-batch | pivot order << 8
-    uint32_t *bcols;      // [64]
-    uint32_t *red;        // [0..15] keys A, [16..31] keys B, [32..47] flags A, [48..63] flags B, [64..] counters
-    uint32_t *outw;       // packed solution
-};
-
-template <bool SPILL>
-__device__ __forceinline__ uint64_t qd_q_load(const OsdLds &S, uint64_t *qglb, int kw_lds, int m_pad, int w, int r)
-{
-    if (SPILL && w >= kw_lds) return qglb[(size_t)(w - kw_lds) * m_pad + r];
-    return S.q[(size_t)w * m_pad + r];
-}
-template <bool SPILL>
-__device__ __forceinline__ void qd_q_store(const OsdLds &S, uint64_t *qglb, int kw_lds, int m_pad, int w, int r, uint64_t v)
-{
-    if (SPILL && w >= kw_lds) qglb[(size_t)(w - kw_lds) * m_pad + r] = v;
-    else S.q[(size_t)w * m_pad + r] = v;
-}
-
-// Elimination over order[0..ncols).  kcap = number of pivots the Q storage can hold.
-// Returns 0 when finished (early stop, rank exhausted or every column consumed with ncols == n), 1 when it ran out of
-// sorted columns (ncols < n) or of Q capacity before finishing -- the caller must then redo the shot with more.
-//
-// One barrier per pivot: a round is  [own rows -> candidate key] -> wave min -> LDS -> BARRIER -> every thread reads the
-// 16 partials -> every thread updates its own rows from row p (which its owner leaves alone this round).  The barrier
-// of round i+1 also separates the updates of round i from those of round i+1, and the two reduction buffers alternate.
-template <int T, bool SPILL>
-__device__ int qd_osd_eliminate(const OsdGraphDev &g, const OsdLds &S, uint64_t *qglb, int kw_lds, int kcap,
-                                const uint16_t *order, int ncols, const uint8_t *det, const uint8_t *upd,
-                                int upd_rows, int out_words, int *npiv_out, int *inconsistent_out,
-                                unsigned long long *a_dbg = nullptr)
-{
-    const int tid = threadIdx.x;
-    constexpr int NW = T / 64;
-    uint32_t *red = S.red;
-    for (int r = tid; r < g.m_pad; r += T) {
-        uint8_t s = 0;
-        if (r < g.m) {
-            s = det[r] & 1u;
-            if (upd && r < upd_rows) s ^= upd[r] & 1u;
-        }
-        S.sp[r] = s;
-        S.rowpiv[r] = -1;
-    }
-    for (int i = tid; i < kw_lds * g.m_pad; i += T) S.q[i] = 0ull;
-    if (SPILL && qglb)
-        for (int i = tid; i < (g.mw - kw_lds) * g.m_pad; i += T) qglb[i] = 0ull;
-    for (int w = tid; w < out_words; w += T) S.outw[w] = 0u;
-    if (tid < 32) red[tid] = QD_NOKEY;
-    else if (tid < 64) red[tid] = 0u;
-    __syncthreads();
-
-    int npiv = 0, done = 0, hard = 0, phase = 0;
-    for (int base = 0; base < ncols && !done && !hard; base += 64) {
-        // ---- transform the next 64 columns: tb[r] bit c = (T * column_c)[r]
-        for (int r = tid; r < g.m_pad; r += T) S.tb[r] = 0ull;
-        if (tid == 0) red[64] = 0u;
-        if (tid < 64) S.bcols[tid] = (base + tid < ncols) ? (uint32_t)order[base + tid] : 0xFFFFFFFFu;
-        __syncthreads();
-        for (int x = tid; x < 64 * g.max_cdeg; x += T) {
-            const int c = x / g.max_cdeg, q = x - c * g.max_cdeg;
-            const uint32_t col = S.bcols[c];
-            if (col != 0xFFFFFFFFu) {
-                const uint32_t e0 = g.csc_ptr[col], e1 = g.csc_ptr[col + 1];
-                if (e0 + q < e1) {
-                    const int r = g.csc_row[e0 + q];
-                    atomicXor(reinterpret_cast<unsigned long long *>(&S.tb[r]), 1ull << c);
-                    const int k = S.rowpiv[r];
-                    if (k >= 0) S.pairs[atomicAdd(&red[64], 1u)] = (uint32_t)c | ((uint32_t)k << 8);
-                }
-            }
-        }
-        __syncthreads();
-        const int np = (int)red[64];
-        if (np)
-            for (int r = tid; r < g.m; r += T) {
-                uint64_t x = S.tb[r];
-                for (int i = 0; i < np; ++i) {
-                    const uint32_t pr = S.pairs[i];
-                    const int k = (int)(pr >> 8);
-                    const uint64_t qw = qd_q_load<SPILL>(S, qglb, kw_lds, g.m_pad, k >> 6, r);
-                    x ^= ((qw >> (k & 63)) & 1ull) << (pr & 63u);
-                }
-                S.tb[r] = x;
-            }
-        // ---- take pivots out of the batch, in column order
-        for (;;) {
-            uint32_t key = QD_NOKEY;
-            int resid = 0;
-            for (int r = tid; r < g.m; r += T)
-                if (S.rowpiv[r] < 0) {
-                    const uint64_t x = S.tb[r];
-                    if (x) key = min(key, ((uint32_t)__builtin_ctzll(x) << 16) | (uint32_t)r);
-                    resid |= S.sp[r];
-                }
-            key = qd_wave_umin(key);
-            const unsigned long long bal = __ballot(resid);
-            if ((tid & 63) == 0) { red[phase * 16 + (tid >> 6)] = key; red[32 + phase * 16 + (tid >> 6)] = (bal != 0ull); }
-            __syncthreads();
-            key = QD_NOKEY;
-            int anyres = 0;
-            {
-                const uint4 *kv = reinterpret_cast<const uint4 *>(red + phase * 16);
-                const uint4 *fv = reinterpret_cast<const uint4 *>(red + 32 + phase * 16);
-#pragma unroll
-                for (int w = 0; w < (NW + 3) / 4; ++w) {       // entries beyond NW hold NOKEY / 0 (set once per call)
-                    const uint4 k4 = kv[w], f4 = fv[w];
-                    key = min(key, min(min(k4.x, k4.y), min(k4.z, k4.w)));
-                    anyres |= (int)(f4.x | f4.y | f4.z | f4.w);
-                }
-            }
-            phase ^= 1;
-            if (!anyres) { done = 1; break; }            // syndrome already in the span of the pivots found
-            if (key == QD_NOKEY) break;                   // rest of the batch depends on earlier pivots
-            if (npiv >= kcap) { hard = 1; break; }        // no room for another pivot in this kernel's Q storage
-            const int c = (int)(key >> 16), p = (int)(key & 0xFFFFu);
-            const int K = npiv, kw = K >> 6;
-            const uint64_t kb = 1ull << (K & 63);
-            const uint64_t tp = S.tb[p];
-            const uint8_t spp = S.sp[p];
-            for (int r = tid; r < g.m; r += T) {
-                if (r == p) { S.rowpiv[r] = (int16_t)K; S.prow[K] = (uint16_t)p; S.pcol[K] = S.bcols[c]; }   // the owner records the pivot
-                else if ((S.tb[r] >> c) & 1ull) {
-                    S.tb[r] ^= tp;
-                    S.sp[r] ^= spp;
-                    for (int w = 0; w <= kw; ++w) {
-                        uint64_t v = qd_q_load<SPILL>(S, qglb, kw_lds, g.m_pad, w, r) ^ qd_q_load<SPILL>(S, qglb, kw_lds, g.m_pad, w, p);
-                        if (w == kw) v ^= kb;
-                        qd_q_store<SPILL>(S, qglb, kw_lds, g.m_pad, w, r, v);
-                    }
-                }
-            }
-            npiv = K + 1;
-        }
-        __syncthreads();                                  // last round's updates, before the next batch re-uses tb / reads rowpiv
-    }
-    if (!done && !hard && ncols < g.n) {
-        // out of sorted columns: finished only if the syndrome happens to be resolved already or no row is left
-        int resid = 0;
-        for (int r = tid; r < g.m; r += T)
-            if (S.rowpiv[r] < 0) resid |= S.sp[r];
-        const unsigned long long bal = __ballot(resid);
-        if ((tid & 63) == 0) red[32 + phase * 16 + (tid >> 6)] = (bal != 0ull);
-        __syncthreads();
-        int anyres = 0;
-        for (int w = 0; w < NW; ++w) anyres |= (int)red[32 + phase * 16 + w];
-        if (anyres && npiv < g.m) hard = 1;
-        phase ^= 1;
-        __syncthreads();
-    }
-    if (hard) return 1;
-    // residual left on a non-pivot row <=> syndrome outside the column space
-    int inconsistent = 0;
-    {
-        int resid = 0;
-        for (int r = tid; r < g.m; r += T)
-            if (S.rowpiv[r] < 0) resid |= S.sp[r];
-        const unsigned long long bal = __ballot(resid);
-        if ((tid & 63) == 0) red[32 + phase * 16 + (tid >> 6)] = (bal != 0ull);
-        __syncthreads();
-        for (int w = 0; w < NW; ++w) inconsistent |= (int)red[32 + phase * 16 + w];
-    }
-    // OSD-0 solution
-    for (int k = tid; k < npiv; k += T)
-        if (S.sp[S.prow[k]]) {
-            const uint32_t j = S.pcol[k];
-            atomicOr(&S.outw[j >> 5], 1u << (j & 31u));
-        }
-    __syncthreads();
-    *npiv_out = npiv;
-    *inconsistent_out = inconsistent;
-    return 0;
-}
-
-__device__ __forceinline__ void qd_osd_carve(unsigned char *smem, const int *off, OsdLds &S)
-{
-    S.q = reinterpret_cast<uint64_t *>(smem + off[0]);
-    S.tb = reinterpret_cast<uint64_t *>(smem + off[1]);
-    S.sp = smem + off[2];
-    S.rowpiv = reinterpret_cast<int16_t *>(smem + off[3]);
-    S.prow = reinterpret_cast<uint16_t *>(smem + off[4]);
-    S.pcol = reinterpret_cast<uint32_t *>(smem + off[5]);
-    S.pairs = reinterpret_cast<uint32_t *>(smem + off[6]);
-    S.bcols = reinterpret_cast<uint32_t *>(smem + off[7]);
-    S.red = reinterpret_cast<uint32_t *>(smem + off[8]);
-    S.outw = reinterpret_cast<uint32_t *>(smem + off[9]);
-}
 
 // ---- register-resident path ------------------------------------------------------------------------------------------------
 

@@ -33,6 +33,11 @@ size_t qd_osdcs_ws_words(int variant);
 hipError_t qd_launch_osdcs(const OsdGraphDev &g, const BpGraphDev &bg, const DecodeArgs &a, const int *off, int variant, int lds,
                            uint64_t *ws, int blocks, hipStream_t s);
 size_t qd_osd_sr_ws_words(int m_pad, int mw, int threads, int rpt);
+// osd_offchip.hip: OSD-0 for off-chip windows
+int qd_osd_offchip_layout(int m, int n, int max_cdeg, int *off, int *off_sort, int *off_order, int *kw, int *threads, int *per_cu);
+size_t qd_osd_offchip_ws_words(int m, int kw);
+hipError_t qd_launch_osd0_offchip(const OsdGraphDev &g, const BpGraphDev &bg, const DecodeArgs &a, const int *off, int off_sort, int off_order,
+                                  int kw, int threads, int lds, uint64_t *q_ws, int blocks, hipStream_t s);
 hipError_t qd_launch_lsd0(const GenGraphDev &gg, const BpGraphDev &bg, const DecodeArgs &d, uint64_t *q_ws, int blocks_alloc, int blocks,
                           int lsd_w, int lsd_order, const uint32_t *wfix, hipStream_t s);
 size_t qd_lsd_ws_bytes(int m, int n, int blocks, int lsd_w);
@@ -138,13 +143,19 @@ struct qd_graph {
     std::vector<uint32_t> h_bit_orig;  // bit slot -> fault
     std::vector<int32_t> h_sc_slot;    // fault -> accumulator slot of the scatter kernels (empty: they are not used)
     long long sc_walk_cycles = 0, sc_walk_ideal = 0;   // modelled LDS cycles of one pass of the scatter kernels' walk, and without any bank conflict
+    // Off-chip window: build_bp cannot lay out the gather kernel's LDS state.  bp then holds the shapes and the slot orders alone (threads = lds_bytes = 0),
+    // there is no scatter view, BP runs in the one-message-per-edge kernel and OSD-0 in qd_osd0_offchip_kernel.
+    bool off_chip = false;
+    // LDS layout of qd_osd0_offchip_kernel (x_lds = 0: even its row state does not fit): any window can take it (QD_FLAG_OFF_CHIP)
+    int x_off[10] = {0}, x_off_sort = 0, x_off_order = 0, x_kw = 0, x_threads = 0, x_per_cu = 0, x_lds = 0;
     ~qd_graph() { mem.release(); }
 };
 
 // The BP kernel(s) of a decoder's stage 1, chosen once by qd_decoder_create
 enum BpPath {
     BP_LDS_EDGE,        // flooding product-sum, one message per edge, every message in LDS (qd_launch_bp_ps_lds)
-    BP_HBM_EDGE,        // one message per edge in an HBM workspace (bp_general.hip): every other method / schedule, and QD_FLAG_EDGE_MESSAGES
+    BP_HBM_EDGE,        // one message per edge in an HBM workspace (bp_general.hip): every other method / schedule, QD_FLAG_EDGE_MESSAGES, and every
+                        // pair of an off-chip decoder (flooding min-sum on the grid: with the exactness certificate and the coarse-grid redo pass)
     BP_SCATTER_WIDE,    // flooding min-sum on the LLR grid, several checks per lane (bp_scatter_wide.hip); recheck + coarse grid: gather kernel
     BP_SCATTER,         // ... one check per lane (bp_scatter.hip); recheck + coarse grid: gather kernel
     BP_GATHER_GRID,     // ... the gather kernel (bp_kernels.hip) on the fine grid, then on the coarse grid
@@ -179,6 +190,7 @@ struct qd_decoder {
     uint16_t *order_ws = nullptr;
     uint64_t *q_spill = nullptr, *q_spill_fast = nullptr, *mt_ws = nullptr;
     uint64_t *q_spill_sr = nullptr;
+    uint64_t *q_spill_off = nullptr;   // [post_blocks][qd_osd_offchip_ws_words] spilled Q planes of qd_osd0_offchip_kernel
     int32_t *hard_list = nullptr, *hard_list2 = nullptr;
     int osd_blocks_fast = 0;
     int post_blocks = 0;        // workgroups of the post-processor's own kernel: qd_osd0_sr_kernel (osd_sr.hip), qd_osdcs_kernel or qd_lsd0_kernel
@@ -195,6 +207,9 @@ struct qd_decoder {
     int grid_k = -1, grid_kc = -1, grid_floor = 0;   // grid_floor: the fine grid is the 2^-10 floor, not the rule's: any number of shots may need the redo pass
     BpGraphDev bp_fine{}, bp_coarse{};         // copies of g->bp with their own bit_rec
     const float *llr0_q = nullptr;             // fault-order LLRs for the one-message-per-edge kernel (fine grid)
+    const float *llr0_qc = nullptr;            // ... on the coarse grid (edge_cert)
+    bool off_chip = false;                     // the graph is off-chip, or QD_FLAG_OFF_CHIP: edge kernel, qd_osd0_offchip_kernel
+    bool edge_cert = false;                    // off_chip and on the LLR grid: the edge kernel certifies its shots and the tripped ones are decoded again
     int32_t *redo_list = nullptr;
     int redo_cap = 0;
     const int32_t *prior_g = nullptr;          // [n_pad] fine-grid channel LLRs of the bit slots in grid units (scatter kernels)
@@ -370,7 +385,7 @@ static void scatter_walk(int m, const int32_t *row_ptr, const int32_t *col_idx, 
     }
 }
 
-extern "C" int qd_version(void) { return 106; }      // 106: qd_circuit_create takes Y_ERROR / PAULI_CHANNEL_1 / PAULI_CHANNEL_2 programs (no new export); 105: qd_decoder_fast_start; 104: qd_circuit_* and qd_sample_circuit; 103: qd_decoder_post_head_start; 102: qd_graph_info fills 10 entries again, qd_graph_info_ex(g, info, n) the rest; 101: qd_decoder_postproc_kernel
+extern "C" int qd_version(void) { return 107; }      // 107: off-chip windows decode (qd_graph_create used to refuse them), QD_FLAG_OFF_CHIP, QD_POST_OSD0_OFFCHIP (no new export); 106: qd_circuit_create takes Y_ERROR / PAULI_CHANNEL_1 / PAULI_CHANNEL_2 programs (no new export); 105: qd_decoder_fast_start; 104: qd_circuit_* and qd_sample_circuit; 103: qd_decoder_post_head_start; 102: qd_graph_info fills 10 entries again, qd_graph_info_ex(g, info, n) the rest; 101: qd_decoder_postproc_kernel
 extern "C" const char *qd_last_error(void) { return g_err; }
 extern "C" int qd_device_count(void)
 {
@@ -424,7 +439,6 @@ static int host_graph(int32_t m, int32_t n, const int32_t *row_ptr, const int32_
     h.min_rdeg = *std::min_element(rdeg.begin(), rdeg.end());
     h.m_pad = pad64(m); h.n_pad = pad64(n); h.max_rdeg_pad = (max_rdeg + 3) & ~3;
     h.row_ptr = row_ptr; h.col_idx = col_idx; h.priors = priors;
-    if ((h.m_pad + 1) * 16 > 65535) return fail(QD_ECAPACITY, "m = %d detectors per window: check-state offsets exceed 16 bits", m);
     if (h.n_pad + 1 > 65535) return fail(QD_ECAPACITY, "n = %d faults per window: fault slots exceed 16 bits", n);
     // CSC with the edge's position inside its row
     h.cp.assign(n + 1, 0); h.ri.resize(nnz); h.pos.resize(nnz);
@@ -491,8 +505,17 @@ static int build_bp(qd_graph *g, HostGraph &h, bool walk_for_atomics)
     bp.off_out = off; off += align16(bp.out_words * 4);
     bp.off_misc = off; off += 256;
     bp.lds_bytes = off;
-    if (bp.lds_bytes > QD_LDS_BYTES)
-        return fail(QD_ECAPACITY, "window needs %d bytes of LDS for BP state; the CU has %d", bp.lds_bytes, QD_LDS_BYTES);
+    // the state does not fit the CU, or a fault record cannot address a check's state with 16 bits: an off-chip window -- the slot orders alone
+    if (bp.lds_bytes > QD_LDS_BYTES || (m_pad + 1) * 16 > 65535) {
+        g->off_chip = true;
+        bp.off_chk = bp.off_cneg = bp.off_llr = bp.off_out = bp.off_misc = bp.lds_bytes = 0;
+        bp.threads = 0;
+        std::vector<uint32_t> bit_orig_u(n_pad, 0), slot_of(bit_slot_of.begin(), bit_slot_of.end());
+        for (int s = 0; s < n; ++s) bit_orig_u[s] = (uint32_t)bit_orig[s];
+        g->h_bit_orig = bit_orig_u;
+        if (g->mem.upload(bit_orig_u, &bp.bit_orig) | g->mem.upload(slot_of, &bp.bit_slot_of)) return fail(QD_EHIP, "device allocation/upload failed");
+        return QD_OK;
+    }
     bp.threads = bp_block_threads(m, n);
 
     std::vector<uint8_t> &chk_deg = h.chk_deg;
@@ -963,6 +986,7 @@ static int build_osd(qd_graph *g, const HostGraph &h)
     }
     // the full kernel sorts all n columns in LDS; windows too large for that rely on the register kernel alone
     if (od.lds_bytes == 0 && od.f_lds_bytes == 0) od.threads = 0;
+    g->x_lds = qd_osd_offchip_layout(m, n, max_cdeg, g->x_off, &g->x_off_sort, &g->x_off_order, &g->x_kw, &g->x_threads, &g->x_per_cu);
     return QD_OK;
 }
 
@@ -980,7 +1004,7 @@ extern "C" int qd_graph_create(int32_t m, int32_t n, const int32_t *row_ptr, con
     const int form = scatter_form(h);
     if (int rc = build_bp(g.get(), h, form != 0)) return rc;
     if (int rc = build_gen(g.get(), h)) return rc;
-    if (int rc = build_scatter(g.get(), h, form, env)) return rc;
+    if (int rc = build_scatter(g.get(), h, g->off_chip ? 0 : form, env)) return rc;
     if (int rc = build_osd(g.get(), h)) return rc;
     g->h_cp = h.cp; g->h_ri = h.ri; g->h_llr0 = h.llr0;
     *out = g.release();
@@ -1050,9 +1074,12 @@ extern "C" int qd_decoder_create(const qd_graph *g, const qd_params *p, qd_decod
     *out = nullptr;
     if (p->bp_method != QD_BP_MINIMUM_SUM && p->bp_method != QD_BP_PRODUCT_SUM) return fail(QD_EINVAL, "unknown bp_method %d", p->bp_method);
     if (p->schedule != QD_SCHEDULE_PARALLEL && p->schedule != QD_SCHEDULE_SERIAL) return fail(QD_EINVAL, "unknown schedule %d", p->schedule);
-    if (p->reserved & ~(QD_FLAG_EDGE_MESSAGES | QD_FLAG_RAW_LLR)) return fail(QD_EINVAL, "unknown flag bits 0x%x", p->reserved);
+    if (p->reserved & ~(QD_FLAG_EDGE_MESSAGES | QD_FLAG_RAW_LLR | QD_FLAG_OFF_CHIP)) return fail(QD_EINVAL, "unknown flag bits 0x%x", p->reserved);
     const bool lsd = p->osd_method == QD_LSD_0 || p->osd_method == QD_LSD_E || p->osd_method == QD_LSD_CS;
     if (lsd && p->osd_order < 0) return fail(QD_EINVAL, "negative lsd_order");
+    const bool off_chip = g->off_chip || (p->reserved & QD_FLAG_OFF_CHIP);
+    if (off_chip && lsd)
+        return fail(QD_EUNSUPPORTED, "BP-LSD is not implemented for the off-chip window %d x %d%s", g->m, g->n, g->off_chip ? "" : " (QD_FLAG_OFF_CHIP)");
     if (p->osd_method == QD_LSD_CS && p->osd_order > 64)
         return fail(QD_EUNSUPPORTED, "lsd_cs: lsd_order %d > 64 is not implemented on the device path", p->osd_order);
     if (p->osd_method == QD_LSD_E && p->osd_order > 15)
@@ -1063,6 +1090,9 @@ extern "C" int qd_decoder_create(const qd_graph *g, const qd_params *p, qd_decod
     if (p->osd_method != QD_OSD_OFF && !osd0) {
         if (p->osd_method != QD_OSD_CS && p->osd_method != QD_OSD_E) return fail(QD_EINVAL, "unknown osd_method %d", p->osd_method);
         if (p->osd_order < 0) return fail(QD_EINVAL, "negative osd_order");
+        if (off_chip)
+            return fail(QD_EUNSUPPORTED, "osd_cs / osd_e of order %d are not implemented for the off-chip window %d x %d%s (order 0 is)", p->osd_order, g->m,
+                        g->n, g->off_chip ? "" : " (QD_FLAG_OFF_CHIP)");
         if (g->osd.w_lds_bytes == 0)
             return fail(QD_EUNSUPPORTED, "osd_cs / osd_e need the register OSD kernel, which this window (%d detectors) does not fit", g->m);
         if (p->osd_method == QD_OSD_CS && p->osd_order > 64)
@@ -1070,12 +1100,14 @@ extern "C" int qd_decoder_create(const qd_graph *g, const qd_params *p, qd_decod
         if (p->osd_method == QD_OSD_E && p->osd_order > 15)
             return fail(QD_EUNSUPPORTED, "osd_e: osd_order %d > 15 is not implemented on the device path", p->osd_order);
     }
-    if (p->osd_method != QD_OSD_OFF && !lsd && g->osd.lds_bytes == 0 && g->osd.f_lds_bytes == 0)
+    if (p->osd_method != QD_OSD_OFF && off_chip && g->x_lds == 0)
+        return fail(QD_ECAPACITY, "off-chip window %d x %d: the row state of the OSD-0 kernel (17 bytes per detector) does not fit the CU's LDS", g->m, g->n);
+    if (p->osd_method != QD_OSD_OFF && !lsd && !off_chip && g->osd.lds_bytes == 0 && g->osd.f_lds_bytes == 0)
         return fail(QD_ECAPACITY, "window %d x %d does not fit either OSD kernel's LDS layout", g->m, g->n);
     if (p->max_iter < 0 || p->ms_scaling_factor < 0) return fail(QD_EINVAL, "negative max_iter / ms_scaling_factor");
     const Switches env = read_switches();
     qd_decoder *d = new qd_decoder();
-    d->g = g; d->prm = *p;
+    d->g = g; d->prm = *p; d->off_chip = off_chip;
     d->lsd_w = (lsd && p->osd_order > 0) ? (p->osd_method == QD_LSD_CS ? 1 : (p->osd_method == QD_LSD_E ? 2 : 0)) : 0;
     d->osd_w = osd0 || p->osd_method == QD_OSD_OFF ? 0 : (p->osd_method == QD_OSD_CS ? 1 : 2);
     if (d->osd_w) host_rank(const_cast<qd_graph *>(g));     // the sweep needs the complete factorisation: rank pivots
@@ -1083,6 +1115,7 @@ extern "C" int qd_decoder_create(const qd_graph *g, const qd_params *p, qd_decod
     if (d->prm.max_iter > QD_STATUS_ITER_MASK) d->prm.max_iter = QD_STATUS_ITER_MASK;
     // ---- the post-processor
     if (p->osd_method == QD_OSD_OFF) d->post = QD_POST_NONE;
+    else if (off_chip) d->post = QD_POST_OSD0_OFFCHIP;
     else if (lsd) d->post = QD_POST_LSD;
     else if (d->osd_w) {
         // higher-order OSD: the panel kernel (osd_cs.hip) wherever its layout takes the window, else the row form (osd_kernels.hip)
@@ -1093,9 +1126,9 @@ extern "C" int qd_decoder_create(const qd_graph *g, const qd_params *p, qd_decod
         d->post = g->osd.s_lds_bytes > 0 ? QD_POST_OSD0_SR : QD_POST_OSD0_REG;
     // ---- the BP kernel: one message per edge for every method / schedule but flooding min-sum (and for that one with QD_FLAG_EDGE_MESSAGES),
     // the gather kernel for it off the LLR grid, the gather or a scatter kernel on the grid (below)
-    const bool edge = p->bp_method != QD_BP_MINIMUM_SUM || p->schedule != QD_SCHEDULE_PARALLEL || (p->reserved & QD_FLAG_EDGE_MESSAGES);
+    const bool edge = off_chip || p->bp_method != QD_BP_MINIMUM_SUM || p->schedule != QD_SCHEDULE_PARALLEL || (p->reserved & QD_FLAG_EDGE_MESSAGES);
     if (edge)
-        d->bp = (p->bp_method == QD_BP_PRODUCT_SUM && p->schedule == QD_SCHEDULE_PARALLEL && qd_bp_ps_lds_bytes(g->gen, g->max_rdeg) > 0) ? BP_LDS_EDGE : BP_HBM_EDGE;
+        d->bp = (!off_chip && p->bp_method == QD_BP_PRODUCT_SUM && p->schedule == QD_SCHEDULE_PARALLEL && qd_bp_ps_lds_bytes(g->gen, g->max_rdeg) > 0) ? BP_LDS_EDGE : BP_HBM_EDGE;
     if (d->bp == BP_HBM_EDGE && p->schedule == QD_SCHEDULE_SERIAL) {
         // the serial schedule in several launches with the survivors packed in between (GenStage), at the bounds that leave two iterations or more
         int prev = 0;
@@ -1122,7 +1155,7 @@ extern "C" int qd_decoder_create(const qd_graph *g, const qd_params *p, qd_decod
         // (+ 0.0f: a prior that rounds to zero from below must be +0, not -0 -- the kernel's sign test reads the bit pattern)
         auto on_grid = [&](double l, int k) { return (float)std::ldexp(std::nearbyint(std::ldexp(l, k)), -k) + 0.0f; };
         int rc = 0;
-        for (int pass = 0; pass < 2; ++pass) {
+        for (int pass = 0; pass < 2 && !off_chip; ++pass) {
             const int k = pass == 0 ? d->grid_k : d->grid_kc;
             std::vector<uint32_t> rec = g->h_bit_rec;
             for (int s = 0; s < g->n; ++s) {
@@ -1134,6 +1167,11 @@ extern "C" int qd_decoder_create(const qd_graph *g, const qd_params *p, qd_decod
         std::vector<float> lq(g->n);
         for (int j = 0; j < g->n; ++j) lq[j] = on_grid(g->h_llr0[j], d->grid_k);
         rc |= d->mem.upload(lq, &d->llr0_q);
+        if (off_chip) {
+            for (int j = 0; j < g->n; ++j) lq[j] = on_grid(g->h_llr0[j], d->grid_kc);
+            rc |= d->mem.upload(lq, &d->llr0_qc);
+            d->edge_cert = true;
+        }
         if (!edge) d->bp = BP_GATHER_GRID;
         if (!edge && g->sc.ok && !env.no_scatter) {
             // scatter kernel: fine-grid priors of the bit slots as integers (grid units) and the second-minimum bound that
@@ -1183,7 +1221,7 @@ static void free_ws(qd_decoder *d)
     auto dev = [](auto *&p) { if (p) (void)hipFree(p); p = nullptr; };
     auto host = [](auto *&p) { if (p) (void)hipHostFree(p); p = nullptr; };
     auto event = [](hipEvent_t &e) { if (e) (void)hipEventDestroy(e); e = nullptr; };
-    dev(d->llr_ws); dev(d->fail_list); dev(d->ctr_base); dev(d->order_ws); dev(d->q_spill); dev(d->q_spill_fast); dev(d->q_spill_sr);
+    dev(d->llr_ws); dev(d->fail_list); dev(d->ctr_base); dev(d->order_ws); dev(d->q_spill); dev(d->q_spill_fast); dev(d->q_spill_sr); dev(d->q_spill_off);
     dev(d->mt_ws); dev(d->cs_ws); dev(d->hard_list); dev(d->hard_list2); dev(d->redo_list); dev(d->recheck_list); dev(d->lsd_ws);
     dev(d->gws.b2c); dev(d->gws.c2b); dev(d->gws.th); dev(d->gws.pre); dev(d->gws.llr); dev(d->gws.syn); dev(d->gws.slot);
     dev(d->gsp.msg2); dev(d->gsp.syn2); dev(d->gsp.lists[0]); dev(d->gsp.lists[1]); dev(d->gsp.counts);
@@ -1224,8 +1262,20 @@ extern "C" int qd_decoder_reserve(qd_decoder *d, int64_t max_batch)
             d->recheck_cap = (int)max_batch;
             HIP_TRY(hipMalloc((void **)&d->recheck_list, sizeof(int32_t) * (size_t)d->recheck_cap));
         }
+    } else if (d->edge_cert) {
+        d->redo_cap = (int)(d->grid_floor ? max_batch : std::min<int64_t>(max_batch, 4096));
+        HIP_TRY(hipMalloc((void **)&d->redo_list, sizeof(int32_t) * (size_t)d->redo_cap));
     }
-    if (d->post != QD_POST_NONE) {
+    if (d->post == QD_POST_OSD0_OFFCHIP) {
+        int ncu = 256;
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, g->device) == hipSuccess && prop.multiProcessorCount > 0) ncu = prop.multiProcessorCount;
+        d->post_blocks = ncu * std::max(1, g->x_per_cu);
+        const size_t words = qd_osd_offchip_ws_words(g->m, g->x_kw);
+        if (words > 0) HIP_TRY(hipMalloc((void **)&d->q_spill_off, sizeof(uint64_t) * (size_t)d->post_blocks * words));
+        HIP_TRY(hipMalloc((void **)&d->llr_ws, sizeof(float) * (size_t)max_batch * g->bp.n_pad));
+        HIP_TRY(hipMalloc((void **)&d->fail_list, sizeof(int32_t) * (size_t)max_batch));
+    } else if (d->post != QD_POST_NONE) {
         int ncu = 256;
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, g->device) == hipSuccess && prop.multiProcessorCount > 0) ncu = prop.multiProcessorCount;
@@ -1393,11 +1443,30 @@ static int launch_bp(qd_decoder *d, const DecodeArgs &a, int64_t B, hipStream_t 
     switch (d->bp) {
     case BP_LDS_EDGE: HIP_TRY(qd_launch_bp_ps_lds(gg, g->bp, a, B, s)); break;
     case BP_GATHER_RAW: HIP_TRY(qd_launch_bp(g->bp, a, B, s)); break;
-    case BP_HBM_EDGE:
+    case BP_HBM_EDGE: {
+        // edge_cert (off-chip decoder on the LLR grid): the first pass parks the shots whose exactness bound tripped, the redo pass decodes them
+        // on the coarse grid -- the gather kernel's rule (BP_GATHER_GRID below), chunk by chunk of the message workspace
+        int32_t *redo_count = d->fail_count + 40;
+        DecodeArgs a1 = a;
+        if (d->edge_cert) {
+            a1.s_limit = std::ldexp(1.0f, 23 - d->grid_k);
+            a1.redo_list = d->redo_list; a1.redo_count = redo_count; a1.redo_cap = d->redo_cap;
+        }
         for (int64_t b0 = 0; b0 < B; b0 += d->gws.S)
-            HIP_TRY(qd_launch_bp_general(gg, g->bp, a, d->gws, d->prm.bp_method, d->prm.schedule, b0,
+            HIP_TRY(qd_launch_bp_general(gg, g->bp, a1, d->gws, d->prm.bp_method, d->prm.schedule, b0,
                                          (int)std::min<int64_t>(d->gws.S, B - b0), s, d->gsp.nbounds > 0 ? &d->gsp : nullptr));
+        if (d->edge_cert) {
+            DecodeArgs a2 = a;
+            a2.s_limit = std::ldexp(1.0f, 23 - d->grid_kc);
+            a2.shot_list = d->redo_list; a2.shot_count = redo_count; a2.status_or = QD_STATUS_COARSE_GRID;
+            gg.llr0 = d->llr0_qc;
+            const int64_t parked_max = std::min<int64_t>(B, d->redo_cap);
+            for (int64_t c0 = 0; c0 < parked_max; c0 += d->gws.S)
+                HIP_TRY(qd_launch_bp_general(gg, g->bp, a2, d->gws, d->prm.bp_method, d->prm.schedule, c0,
+                                             (int)std::min<int64_t>(d->gws.S, parked_max - c0), s, nullptr));
+        }
         break;
+    }
     case BP_SCATTER_WIDE:
     case BP_SCATTER:
     case BP_GATHER_GRID: {
@@ -1439,6 +1508,9 @@ static int launch_post(const qd_decoder *d, const DecodeArgs &a, int64_t B, hipS
     const int blocks = (int)std::min<int64_t>(B, d->post_blocks);
     const int fast = (int)std::min<int64_t>(B, d->osd_blocks_fast), full = (int)std::min<int64_t>(B, d->osd_blocks);
     switch (d->post) {
+    case QD_POST_OSD0_OFFCHIP:
+        HIP_TRY(qd_launch_osd0_offchip(g->osd, g->bp, a, g->x_off, g->x_off_sort, g->x_off_order, g->x_kw, g->x_threads, g->x_lds, d->q_spill_off, blocks, s));
+        break;
     case QD_POST_LSD:
         HIP_TRY(qd_launch_lsd0(g->gen, g->bp, a, d->lsd_ws, d->post_blocks, blocks, d->lsd_w, d->prm.osd_order, g->osd.wfix, s));
         break;

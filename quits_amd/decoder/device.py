@@ -64,15 +64,17 @@ class BatchDecoder:
     """qd_decoder: BP(+OSD-0) over a batch of shots for one window."""
 
     def __init__(self, graph: WindowGraph, bp_method="minimum_sum", schedule="parallel", max_iter=0,
-                 osd_method="osd_0", osd_order=0, ms_scaling_factor=1.0, edge_messages=False, raw_llr=False):
+                 osd_method="osd_0", osd_order=0, ms_scaling_factor=1.0, edge_messages=False, raw_llr=False, off_chip=False):
         """bp_method 'minimum_sum' + schedule 'parallel' runs in the compressed LDS kernel; every other pair -- and that one
         too when `edge_messages` is set -- in the one-message-per-edge kernel (csrc/bp_general.hip).  `raw_llr` keeps the
-        channel LLRs off the binary grid (QD_FLAG_RAW_LLR: round-1 float arithmetic, validation only)."""
+        channel LLRs off the binary grid (QD_FLAG_RAW_LLR: round-1 float arithmetic, validation only).  `off_chip` decodes a window
+        that fits the CU the way an off-chip window is decoded (QD_FLAG_OFF_CHIP: edge kernel with the exactness certificate,
+        qd_osd0_offchip_kernel; validation only) -- a window that does not fit takes that path by itself."""
         self.graph = graph
         L = graph._L
         try:
             prm = _lib.QdParams(_lib.QD_BP[_norm(bp_method)], _lib.QD_SCHEDULE[_norm(schedule)], int(max_iter),
-                                _lib.QD_OSD[_norm(osd_method)], int(osd_order), (1 if edge_messages else 0) | (2 if raw_llr else 0),
+                                _lib.QD_OSD[_norm(osd_method)], int(osd_order), (1 if edge_messages else 0) | (2 if raw_llr else 0) | (4 if off_chip else 0),
                                 float(ms_scaling_factor))
         except KeyError as exc:
             raise ValueError("unknown decoder option %s" % exc) from exc
@@ -90,7 +92,7 @@ class BatchDecoder:
         arr = (C.c_int32 * 4)()
         _lib.check(self._L.qd_decoder_info(self._h, arr))
         post = {0: "none", 1: "qd_osd0_sr_kernel", 2: "qd_osd0_reg_kernel", 3: "qd_osd0_reg_kernel<row form>", 4: "qd_osdcs_kernel",
-                5: "qd_lsd0_kernel"}.get(int(self._L.qd_decoder_postproc_kernel(self._h)), "?")
+                5: "qd_lsd0_kernel", 6: "qd_osd0_offchip_kernel"}.get(int(self._L.qd_decoder_postproc_kernel(self._h)), "?")
         fast = hasattr(self._L, "qd_decoder_fast_start") and int(self._L.qd_decoder_fast_start(self._h)) == 1
         return {"llr_grid_bits": int(arr[0]), "llr_coarse_bits": int(arr[1]), "edge_kernel": bool(arr[2]),
                 "scatter_kernel": bool(arr[3]), "scatter_wide_kernel": int(arr[3]) == 2, "bp_fast_start": fast, "post_kernel": post}
