@@ -121,7 +121,8 @@ void qd_graph_destroy(qd_graph *g);
 int qd_graph_info(const qd_graph *g, int32_t *info);
 /* The same with the caller saying how many int32 entries `info` has room for; entries 10, 11 = modelled LDS cycles of one pass of
  * the scatter kernels' walk over the accumulators (bank conflicts included) and the same without any conflict (0, 0: the window
- * does not run there); entries beyond the ones this version knows are set to 0. */
+ * does not run there); entries 12, 13 = lanes per workgroup and checks per lane of qd_bp_scatter_wide_kernel's instantiation for this
+ * window (0, 0: the window does not take that kernel); entries beyond the ones this version knows are set to 0. */
 int qd_graph_info_ex(const qd_graph *g, int32_t *info, int32_t n_entries);
 
 /* ---- decoder: replaces BpOsdDecoder.__init__'s parameter half. */

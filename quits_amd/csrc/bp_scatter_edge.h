@@ -36,11 +36,18 @@ typedef __attribute__((address_space(3))) int32_t qs_lds_i32;
 #define QS_HP1(A_) hp ^= (uint32_t)(A_);
 #define QS_HPA(A_) hpa = (uint32_t)(A_);
 #define QS_HPB(A_) hp = __builtin_amdgcn_bitop3_b32(hp, hpa, (uint32_t)(A_), 0x96);
+// MAG_: what this check sent on the edge last time, as a magnitude: min2 on its old argmin edge, min1 elsewhere.  QS_MAG_CMP asks every edge
+// (one v_cmp + v_cndmask each); QS_MAG_MASK(q_) (bp_scatter_wide_walk.inc) picks by lane masks kept in scalar registers: `gsel_` = the lanes whose
+// old argmin lies in this group of four edges (one v_cmp per group), `lq[q_]` = the lanes whose old argmin is edge q_ of its group (one v_cmp per
+// check and pass); the AND runs on the scalar unit and the select takes the scalar pair as it is.
+#define QS_MAG_CMP(k_) (((uint32_t)(k_) == kold) ? s2 : s1)
+#define QS_MAG_MASK(q_) (__builtin_amdgcn_inverse_ballot_w64(gsel_ & lq[q_]) ? s2 : s1)
 #define QS_EDGE(off, k_, sb, TAILFIX) QS_EDGE_H(off, k_, sb, TAILFIX, QS_HP1)
-#define QS_EDGE_H(off, k_, sb, TAILFIX, HP)                                                                  \
+#define QS_EDGE_H(off, k_, sb, TAILFIX, HP) QS_EDGE_M(off, k_, sb, TAILFIX, HP, QS_MAG_CMP(k_))
+#define QS_EDGE_M(off, k_, sb, TAILFIX, HP, MAG_)                                                            \
     {                                                                                                        \
         const int A_ = QS_ACC(off);                                                                          \
-        const float mag_ = ((uint32_t)(k_) == kold) ? s2 : s1;                                               \
+        const float mag_ = MAG_;                                                                             \
         const float prev_ = __uint_as_float(QS_SIGN31(sb) | __float_as_uint(mag_));                          \
         float d_ = (float)A_ - prev_;                                                                        \
         TAILFIX(d_, k_)                                                                                      \

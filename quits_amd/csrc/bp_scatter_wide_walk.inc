@@ -1,7 +1,11 @@
 // bp_scatter_wide_walk.inc -- the edge walk of one gather pass of one check (bp_scatter_wide.hip), as program text: included by
-// qd_bp_scatter_wide_kernel for every pass and by qd_bp_first_pass_kernel, which runs pass 0 once per decoder -- the same QS_EDGE_H / QS_EDGE
-// steps, trip counts, tail rules and argmin rule, so the table cannot drift from what the loop would have found.
+// qd_bp_scatter_wide_kernel for every pass and by qd_bp_first_pass_kernel, which runs pass 0 once per decoder -- the same QS_EDGE_M
+// steps (bp_scatter_edge.h, with QS_MAG_MASK), trip counts, tail rules and argmin rule, so the table cannot drift from what the loop would have found.
 // In scope at the point of inclusion: j, dws, cs, S1, S2, KOLD, dcs, O, pf, a1, a2, kst, adj_row, QS_ADJ, QS_ABL_ADJC, QS_ACC.  Leaves hp, par, neg[].
+// "Is this the edge my last minimum came from" (min2 goes back on that edge, min1 on the others) is asked through lane masks in scalar registers, not per edge
+// on the vector ALU: lq[q] once per check and pass, gsel_ once per group of four edges (the group index is wave-uniform in all four loop forms), their AND
+// on the scalar unit, one v_cndmask per edge that takes the scalar pair -- 8-edge block of <512,8,2,2>: 101 -> 95 vector instructions (profiles/bp_argmin_masks_ab.txt).
+// The masks are ballots, so lanes that are off (act[j], a partial last wavefront) contribute 0 and read nothing.
                 // (the round's loop bounds are re-derived from one scalar every pass: hoisted out of the iteration loop they, and everything computed
                 //  from them for CPL rounds x NSW words, outgrow the scalar registers and come back through v_readlane)
                 int dwj = dws[j];
@@ -10,7 +14,11 @@
                 const int adj_voff = cs[j] * 16;
                 QS_ABL_ADJC
                 const float s1 = S1[j], s2 = S2[j];
-                const uint32_t kold = KOLD[j];
+                // the old argmin edge as lane masks (QS_MAG_MASK): position kold = 4 khi + klo; "none" (0xFFFFFFFF) has a khi no group reaches
+                const uint32_t khi = KOLD[j] >> 2, klo = KOLD[j] & 3u;
+                const unsigned long long lq[4] = {__builtin_amdgcn_ballot_w64(klo == 0u), __builtin_amdgcn_ballot_w64(klo == 1u),
+                                                  __builtin_amdgcn_ballot_w64(klo == 2u), __builtin_amdgcn_ballot_w64(klo == 3u)};
+#define QS_GSEL(k_) const unsigned long long gsel_ = __builtin_amdgcn_ballot_w64(khi == (uint32_t)((k_) >> 2));
                 const int dc = dcs[j];
                 uint32_t hp = 0u, hpa = 0u, par = 0u;
                 uint32_t neg[NSW];
@@ -33,14 +41,16 @@
                                 eb = QS_ADJ(row0 + (kk >> 2) + 1);            // (the table has spare group rows)
                                 {
                                     const int sb = kend - 1 - kk, k = k0 + kk;
-                                    QS_EDGE_H(nx.x, k, sb, QS_NOFIX, QS_HPA) QS_EDGE_H(nx.y, k + 1, sb - 1, QS_NOFIX, QS_HPB)
-                                    QS_EDGE_H(nx.z, k + 2, sb - 2, QS_NOFIX, QS_HPA) QS_EDGE_H(nx.w, k + 3, sb - 3, QS_NOFIX, QS_HPB)
+                                    QS_GSEL(k)
+                                    QS_EDGE_M(nx.x, k, sb, QS_NOFIX, QS_HPA, QS_MAG_MASK(0)) QS_EDGE_M(nx.y, k + 1, sb - 1, QS_NOFIX, QS_HPB, QS_MAG_MASK(1))
+                                    QS_EDGE_M(nx.z, k + 2, sb - 2, QS_NOFIX, QS_HPA, QS_MAG_MASK(2)) QS_EDGE_M(nx.w, k + 3, sb - 3, QS_NOFIX, QS_HPB, QS_MAG_MASK(3))
                                 }
                                 nx = QS_ADJ(row0 + (kk >> 2) + 2);
                                 {
                                     const int sb = kend - 5 - kk, k = k0 + kk + 4;
-                                    QS_EDGE_H(eb.x, k, sb, QS_NOFIX, QS_HPA) QS_EDGE_H(eb.y, k + 1, sb - 1, QS_NOFIX, QS_HPB)
-                                    QS_EDGE_H(eb.z, k + 2, sb - 2, QS_NOFIX, QS_HPA) QS_EDGE_H(eb.w, k + 3, sb - 3, QS_NOFIX, QS_HPB)
+                                    QS_GSEL(k)
+                                    QS_EDGE_M(eb.x, k, sb, QS_NOFIX, QS_HPA, QS_MAG_MASK(0)) QS_EDGE_M(eb.y, k + 1, sb - 1, QS_NOFIX, QS_HPB, QS_MAG_MASK(1))
+                                    QS_EDGE_M(eb.z, k + 2, sb - 2, QS_NOFIX, QS_HPA, QS_MAG_MASK(2)) QS_EDGE_M(eb.w, k + 3, sb - 3, QS_NOFIX, QS_HPB, QS_MAG_MASK(3))
                                 }
                             }
                         }
@@ -49,26 +59,29 @@
                             const uint4 e4 = nx;
                             nx = QS_ADJ(row0 + (kk >> 2) + 1);
                             const int sb = kend - 1 - kk, k = k0 + kk;
-                            QS_EDGE_H(e4.x, k, sb, QS_NOFIX, QS_HPA)
-                            QS_EDGE_H(e4.y, k + 1, sb - 1, QS_NOFIX, QS_HPB)
-                            QS_EDGE_H(e4.z, k + 2, sb - 2, QS_NOFIX, QS_HPA)
-                            QS_EDGE_H(e4.w, k + 3, sb - 3, QS_NOFIX, QS_HPB)
+                            QS_GSEL(k)
+                            QS_EDGE_M(e4.x, k, sb, QS_NOFIX, QS_HPA, QS_MAG_MASK(0))
+                            QS_EDGE_M(e4.y, k + 1, sb - 1, QS_NOFIX, QS_HPB, QS_MAG_MASK(1))
+                            QS_EDGE_M(e4.z, k + 2, sb - 2, QS_NOFIX, QS_HPA, QS_MAG_MASK(2))
+                            QS_EDGE_M(e4.w, k + 3, sb - 3, QS_NOFIX, QS_HPB, QS_MAG_MASK(3))
                         }
                         // an edge below the smallest degree of the wavefront is real on every lane (no fix), one at or beyond the largest is
                         // nobody's; only in between does a lane have to ask (wave-uniform tests; k < wmax: a group starts below the largest degree)
 #define QS_TAIL_EDGE(off, q_)                                                                                     \
-                            if (k + (q_) < wmin) QS_EDGE(off, k + (q_), sb - (q_), QS_NOFIX)                      \
-                            else if (k + (q_) < wmax) QS_EDGE(off, k + (q_), sb - (q_), QS_TAILFIX)               \
+                            if (k + (q_) < wmin) QS_EDGE_M(off, k + (q_), sb - (q_), QS_NOFIX, QS_HP1, QS_MAG_MASK(q_))            \
+                            else if (k + (q_) < wmax) QS_EDGE_M(off, k + (q_), sb - (q_), QS_TAILFIX, QS_HP1, QS_MAG_MASK(q_))     \
                             else { neww <<= 1; ltw <<= 1; }
 #pragma unroll 1
                         for (; kk + 4 < kend; kk += 4) {
                             const uint4 e4 = nx;
                             nx = QS_ADJ(row0 + (kk >> 2) + 1);
                             const int sb = kend - 1 - kk, k = k0 + kk;
+                            QS_GSEL(k)
                             QS_TAIL_EDGE(e4.x, 0) QS_TAIL_EDGE(e4.y, 1) QS_TAIL_EDGE(e4.z, 2) QS_TAIL_EDGE(e4.w, 3)
                         }
                         if (kk < kend) {              // the word's last group (for rows of 33..36 faults the second word's only one): nothing to request behind it, no copy
                             const int sb = kend - 1 - kk, k = k0 + kk;
+                            QS_GSEL(k)
                             QS_TAIL_EDGE(nx.x, 0) QS_TAIL_EDGE(nx.y, 1) QS_TAIL_EDGE(nx.z, 2) QS_TAIL_EDGE(nx.w, 3)
                         }
 #undef QS_TAIL_EDGE
@@ -77,3 +90,4 @@
                         if (ltw) kst = (uint32_t)(k0 + kend - 1 - (int)__builtin_ctz(ltw));   // a later word's improvement overrides an earlier one's
                     }
                 }
+#undef QS_GSEL
