@@ -71,11 +71,10 @@ __device__ __forceinline__ uint32_t qd_lanes_or(uint32_t v, uint32_t (*red)[64],
 //    CERT: flooding min-sum on the LLR grid with the exactness certificate of bp_kernels.hip (off-chip windows, QD_FLAG_OFF_CHIP): the bit pass
 //          keeps S_j = |llr0_j| + sum |c2b| per fault and a shot with some S_j >= a.s_limit is parked on a.redo_list instead of returning a result;
 //          the redo pass (a.shot_list: column c of the launch holds shot a.shot_list[shot0 + c], the coarse-grid LLRs in llr0) decodes it again
-#ifndef QD_GEN_WPE
-#define QD_GEN_WPE 1          // wavefronts per SIMD the serial instantiations for column weight <= 8 are budgeted for (1: no bound)
-#endif
+// (no register budget: six wavefronts per SIMD for the serial instantiations of column weight <= 8 -- 80 registers -- gave 1.38-1.41 M shots/s
+//  against 1.44 M at five workgroups per CU, with or without a weight-6 instantiation: profiles/r05_k1g_register_budget_ab.txt)
 template <int METHOD, int SCHED, int G, int D, bool LP, bool CERT = false>
-__global__ void __launch_bounds__(64 * G, (SCHED == QD_SCHEDULE_SERIAL && D <= 8) ? QD_GEN_WPE : 1) qd_bp_edge_kernel(GenGraphDev g, const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
+__global__ void __launch_bounds__(64 * G, 1) qd_bp_edge_kernel(GenGraphDev g, const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
                                                             const int32_t *__restrict__ cp, const int32_t *__restrict__ ri,
                                                             const int32_t *__restrict__ c2r, const float *__restrict__ llr0,
                                                             const uint32_t *__restrict__ srec,
@@ -356,11 +355,7 @@ __global__ void __launch_bounds__(64 * G, (SCHED == QD_SCHEDULE_SERIAL && D <= 8
                                                        ((uint32_t)syn[(size_t)(rw & 0x7FFFFFu) * S] << 31));
                             else P[k] = pls[(rw >> 24) * 64 + lane];
                         } else P[k] = rpre[(size_t)cur[2 + k] * S];
-#if defined(QD_GEN_ABL_NOX)      /* timing experiment only (wrong results): the suffix does not come from memory -- what a perfect prefetch of it could return */
-                        X[k] = __uint_as_float(0x3f000000u | (cur[2 + D + k] & 0xFFu));
-#else
-                        X[k] = suf[(size_t)cur[2 + D + k] * S];
-#endif
+                        X[k] = suf[(size_t)cur[2 + D + k] * S];      // (a perfect prefetch of the suffixes could return 13 % of the chain: profiles/r06_k1g_staged_ab.txt)
                     }
 #pragma unroll
                 for (int k = 0; k < D; ++k)
@@ -767,9 +762,6 @@ static hipError_t launch_k(const GenGraphDev &g, int max_cdeg, const DecodeArgs 
 {
     switch (qd_gen_unroll(max_cdeg)) {
     case 4: return launch_kd<METHOD, SCHED, G, 4, CERT>(g, a, w, shot0, nshots, st, s);
-#if QD_GEN_D6
-    case 6: return launch_kd<METHOD, SCHED, G, 6, CERT>(g, a, w, shot0, nshots, st, s);
-#endif
     case 8: return launch_kd<METHOD, SCHED, G, 8, CERT>(g, a, w, shot0, nshots, st, s);
     default: return launch_kd<METHOD, SCHED, G, QD_MAX_COL_DEG, CERT>(g, a, w, shot0, nshots, st, s);
     }

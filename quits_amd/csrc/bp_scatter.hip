@@ -96,7 +96,6 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_kernel(BpGraphDev g, Scat
         bool us = false;
         float a1 = FLT_MAX, a2 = FLT_MAX;
         uint32_t kst = 0u, q0 = 0u, q1 = 0u;
-#ifndef QS_ABL_NOGATHER
         if (active) {
             uint32_t neg0 = 0u, neg1 = 0u, hp = 0u, hpa = 0u;
             for (int k0 = 0; k0 < trip; k0 += 32) {
@@ -156,7 +155,6 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_kernel(BpGraphDev g, Scat
             mx2 = fmaxf(mx2, a2);
             us = ((synd ^ (hp >> 31)) & 1u) != 0u;
         }
-#endif
         {
             const unsigned long long bal = __ballot(us);
             if ((tid & 63) == 0) misc[32 + (tid >> 6)] = (bal != 0ull);
@@ -175,7 +173,6 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_kernel(BpGraphDev g, Scat
         // ---- scatter pass, in place (every gather of this iteration is done): each edge's accumulator moves by (new message) -
         // (message sent last time), so L(t+1) = prior + sum of the new messages without a second buffer and without a reset
         __builtin_amdgcn_s_setprio(QS_PRIO);
-#ifndef QS_ABL_NOSCAT
         if (active) {
             const int n1i = (int)a1, s1i = (int)s1;
             const int pdif = n1i - s1i, pxq = pdif ^ (n1i + s1i);
@@ -234,7 +231,6 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_kernel(BpGraphDev g, Scat
                 (void)__hip_atomic_fetch_add(QS_LDS(fixo_off), sg_ ? dlt : -dlt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
         }
-#endif
         s1 = a1; s2 = a2; kold = kst; o0 = q0; o1 = q1;
         __builtin_amdgcn_s_setprio(0);
         __syncthreads();

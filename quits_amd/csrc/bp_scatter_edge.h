@@ -17,9 +17,7 @@ __device__ __forceinline__ uint4 qs_as_uint4(qs_u32x4 v) { return make_uint4(v.x
 typedef __attribute__((address_space(3))) int32_t qs_lds_i32;
 #define QS_LDS(off) ((qs_lds_i32 *)(uintptr_t)(uint32_t)(off))
 #define QS_BIG 1.0e30f
-#ifndef QS_PRIO
 #define QS_PRIO 1         // wavefront priority during the scatter pass (short, bound by the LDS): 53.4 -> 52.8 ms at the headline
-#endif
 
 // Gather pass, one edge.  off = LDS byte offset of the fault's accumulator (L - 1) in the buffer being read; k_ = position of the
 // edge in the check's walk (wave-uniform), compared with the argmin label of the last pass; sb = bit of `sgnw` that holds the sign of the message this check sent
@@ -31,7 +29,7 @@ typedef __attribute__((address_space(3))) int32_t qs_lds_i32;
 // immediates instead of one scalar each measured slower: 42.6 -> 43.1 ms, profiles/r05_k1sw_micro_ab.txt.)
 // QS_ACC(off): the accumulator itself -- an LDS read in the kernels; the first-pass table (bp_scatter_wide.hip) redefines it to read the priors from
 // global memory.
-#define QS_ACC(off) (*QS_LDS(QS_ADDR(off)))
+#define QS_ACC(off) (*QS_LDS(off))
 #define QS_SIGN31(sb) (((sgnw >> (sb)) & 1u) << 31)
 #define QS_HP1(A_) hp ^= (uint32_t)(A_);
 #define QS_HPA(A_) hpa = (uint32_t)(A_);
@@ -64,25 +62,8 @@ typedef __attribute__((address_space(3))) int32_t qs_lds_i32;
 // nor a minimum
 #define QS_TAILFIX(x_, k_) x_ = ((int)(k_) < dc) ? x_ : QS_BIG;
 
-#if defined(QS_ABL_NOCONF)      /* timing experiment only (wrong results): every lane's accumulator address moved to bank (lane mod 32) of its 128-byte row */
-#define QS_ADDR(off) ((((uint32_t)(off)) & ~0x7Cu) | ((threadIdx.x & 31u) << 2))
-#elif defined(QS_ABL_ADDRCTL)   /* ... its control: the same extra instruction per access, addresses unchanged */
-__device__ __forceinline__ uint32_t qs_opaque(uint32_t x) { asm volatile("" : "+s"(x)); return x; }
-#define QS_ADDR(off) ((((uint32_t)(off)) & qs_opaque(0xFFFFFFFFu)) | (threadIdx.x & qs_opaque(0u)))
-#else
-#define QS_ADDR(off) (off)
-#endif
-#if defined(QS_ABL_STORE)       /* timing experiments only (wrong results): a plain store instead of the atomic add ... */
-#define QS_ADD(off, v_) *QS_LDS(off) = v_;
-#elif defined(QS_ABL_CONSTV)    /* ... the atomic add of a constant (the value's arithmetic is dead code) */
-#define QS_ADD(off, v_) (void)__hip_atomic_fetch_add(QS_LDS(off), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#elif defined(QS_ABL_READ)      /* ... a plain LDS read per edge instead of the atomic add (what a gather-form bit pass would issue at least) */
-#define QS_ADD(off, v_) { const int r_ = *QS_LDS(off) ^ (v_); asm volatile("" ::"v"(r_)); }
-#elif defined(QS_ABL_NOADD)     /* ... no LDS operation at all in the scatter pass (its vector arithmetic stays) */
-#define QS_ADD(off, v_) asm volatile("" ::"v"(v_));
-#else
-#define QS_ADD(off, v_) (void)__hip_atomic_fetch_add(QS_LDS(QS_ADDR(off)), v_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#endif
+// the scatter pass's one LDS operation per edge (a plain read, a plain store, an add of a constant or nothing in its place: profiles/r05_k1sw_ablation_bounds.txt)
+#define QS_ADD(off, v_) (void)__hip_atomic_fetch_add(QS_LDS(off), v_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 // Scatter pass, one edge: (new message) - (message sent in the last iteration) = sn a - so b with a, b = min1 of the two passes
 // (the argmin edges are corrected after the loop) and sn, so = +-1 the outgoing signs: sn (a - b) where the signs agree, sn (a + b)
 // where they differ.  `own` holds the new signs, `xw` = new ^ sent, edge i of the group at bit 31 - i; pdif = a - b, pxq = (a - b) ^ (a + b).

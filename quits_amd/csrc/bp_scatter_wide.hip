@@ -28,31 +28,9 @@
 // Wavefront priorities.  A wavefront raises its priority for its last gather round (0 -> 2; the scatter pass runs at QS_PRIO = 1 as
 // in bp_scatter.hip): the wavefronts closest to the barrier go first, so a workgroup's stragglers are fewer.  Headline BP stage 44.1 ->
 // 43.2 ms per 65 536 shots; the other way round (first round high) 43.7, scatter pass at 0 / 2 / 3 no change, alternate wavefronts
-// high no change (profiles/r03x_wavefront_priority_ab.txt).
-// Scatter pass: the sign / difference bit of an edge is picked with a scalar bit position (v_bfe_i32 with an SGPR offset) instead of shifting
-// the two words by 4 per group: half a vector instruction per edge moves to the scalar unit.  BP stage 42.35 -> 42.24 ms per 65 536 headline
-// shots (profiles/r05_k1sw_micro_ab.txt); 0 = the shifting form.
-#ifndef QSW_SCAT_SGPR_POS
-#define QSW_SCAT_SGPR_POS 1
-#endif
-#ifndef QSW_GPRIO
-#define QSW_GPRIO 1
-#endif
-// QSW_PRIO_BASE: added to every priority this kernel sets (gather rounds 0 / 1 / 2, scatter pass QS_PRIO, 0 in between): above 0 the wavefronts of a
-// kernel running beside this one at the default priority (the pipelined driver's post-processing) only issue when these do not
-// QSW_FAST_START / QSW_THIN_LAST: the two halves of the fast start (table of gather pass 0; hard-decision parity alone in the last pass), 0 = that half
-// as the generic loop does it (step-by-step A/B, profiles/bp_fast_start_ab.txt)
-#ifndef QSW_FAST_START
-#define QSW_FAST_START 1
-#endif
-#ifndef QSW_THIN_LAST
-#define QSW_THIN_LAST 1
-#endif
-#ifndef QSW_PRIO_BASE
-#define QSW_PRIO_BASE 0
-#endif
-
-__device__ __forceinline__ uint4 qs_reuse4(uint4 &v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w)); return v; }   // (QS_ABL_NOADJ: opaque, so that the reads it feeds stay in the loops)
+// high no change (profiles/r03x_wavefront_priority_ab.txt).  Between the passes the kernel runs at priority 0: every priority raised by one, so that
+// a kernel beside this one (the pipelined driver's post-processing) only issues when this one does not, was no faster (profiles/r06_bp_stream_bubble.txt).
+#define QSW_GATHER_PRIO(j_) if ((j_) == 0) __builtin_amdgcn_s_setprio(0); else if ((j_) == CPL - 1) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(1);
 
 template <int T, int MW, int CPL, int NSW>
 __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g, ScatGraphDev sg, DecodeArgs a, ScatArgs x)
@@ -129,28 +107,19 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
     const uint32_t cur = (uint32_t)sg.offA;
     const __amdgpu_buffer_rsrc_t adj_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)sg.adjA, 0, (g.max_rdeg_pad / 4 + 2) * m_pad * 16, 0x00020000);
     const int adj_row = m_pad * 16;
-#define QS_ADJ_LOAD(row_) qs_as_uint4(__builtin_amdgcn_raw_buffer_load_b128(adj_rsrc, adj_voff, (row_) * adj_row, 0))
-#ifdef QS_ABL_NOADJ      /* timing experiment only (wrong results): one group of offsets per check and pass, reused for every step -- no adjacency traffic in the loops */
-#define QS_ADJ(row_) qs_reuse4(adjc)
-#define QS_ABL_ADJC uint4 adjc = QS_ADJ_LOAD(0);
-#else
-#define QS_ADJ(row_) QS_ADJ_LOAD(row_)
-#define QS_ABL_ADJC
-#endif
+#define QS_ADJ(row_) qs_as_uint4(__builtin_amdgcn_raw_buffer_load_b128(adj_rsrc, adj_voff, (row_) * adj_row, 0))
     // The first group of offsets of a pass (round 0, word 0) is requested BEFORE the barrier the pass starts behind: every wavefront of the workgroup
-    // would otherwise begin the pass by waiting for the same L2 round trip at the same time (QSW_PREFETCH=0: not).
-#ifndef QSW_PREFETCH
-#define QSW_PREFETCH 1
-#endif
+    // would otherwise begin the pass by waiting for the same L2 round trip at the same time.
 #define QS_ADJ_FIRST qs_as_uint4(__builtin_amdgcn_raw_buffer_load_b128(adj_rsrc, cs[0] * 16, 0, 0))
     uint4 pf = QS_ADJ_FIRST;
     // ---- fast start.  Gather pass 0 reads the priors alone (nothing has been sent: S1 = S2 = 0, O = 0, KOLD none), so the minima, the argmin and
     // the incoming signs it finds are constants of the decoder: they come from the table qd_bp_first_pass_kernel made with the same walk.  Only `flip`
     // depends on the shot, through the check's own syndrome bit; the pass's convergence vote is never read (t >= 1 below).  The kernel then enters
     // the loop at scatter pass 0, behind the barriers of the set-up above.
+    // (The table and the thin last pass behind the loop, each measured alone against the generic loop: profiles/bp_fast_start_ab.txt.)
     const bool fast = x.first_pass != nullptr && a.max_iter >= 1;
     bool have = false;                                  // A1 / A2 / KST / Q already hold what the gather pass of this iteration would find
-    if (QSW_FAST_START && fast) {
+    if (fast) {
 #pragma unroll
         for (int j = 0; j < CPL; ++j)
             if (act[j]) {
@@ -185,14 +154,12 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
       if (!have) {
         // ---- gather pass t+1 over L(t); the parity of the hard decisions it meets is the convergence test of iteration t
         bool us = false;
-        if (QSW_THIN_LAST && fast && t == a.max_iter) break;      // the last pass runs behind the loop, in its thin form
+        if (fast && t == a.max_iter) break;      // the last pass runs behind the loop, in its thin form
 #pragma unroll
         for (int j = 0; j < CPL; ++j) {
             float a1 = FLT_MAX, a2 = FLT_MAX;
             uint32_t kst = 0u;
-#if QSW_GPRIO       /* the later gather rounds of a wavefront run at a higher priority (see QSW_GPRIO above) */
-            if (j == 0) __builtin_amdgcn_s_setprio(QSW_PRIO_BASE); else if (j == CPL - 1) __builtin_amdgcn_s_setprio((QSW_PRIO_BASE + 2) & 3); else __builtin_amdgcn_s_setprio((QSW_PRIO_BASE + 1) & 3);
-#endif
+            QSW_GATHER_PRIO(j)          // the later gather rounds of a wavefront run at a higher priority
             if (act[j]) {
 #include "bp_scatter_wide_walk.inc"
                 // outgoing sign on edge k = syndrome ^ (parity of all incoming signs) ^ incoming sign k
@@ -204,20 +171,16 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
             }
             A1[j] = a1; A2[j] = a2; KST[j] = kst;
         }
-#if QSW_GPRIO
-        __builtin_amdgcn_s_setprio(QSW_PRIO_BASE);
-#endif
-        if (QSW_PREFETCH) pf = QS_ADJ_FIRST;              // for the scatter pass behind the barrier
+        __builtin_amdgcn_s_setprio(0);
+        pf = QS_ADJ_FIRST;              // for the scatter pass behind the barrier
         int anyun;
         QSW_VOTE(us, anyun)
-#ifndef QS_ABL_FORCE_ITERS       /* timing experiments only: every shot runs max_iter iterations, whatever the (wrong) arithmetic of an ablation build does */
         if (t >= 1 && !anyun) { converged = 1; break; }
-#endif
         if (t == a.max_iter) break;
       }
         have = false;
         // ---- scatter pass, in place: each edge's accumulator moves by (new message) - (message sent last time)
-        __builtin_amdgcn_s_setprio((QSW_PRIO_BASE + QS_PRIO) & 3);
+        __builtin_amdgcn_s_setprio(QS_PRIO);
 #pragma unroll
         for (int j = 0; j < CPL; ++j) {
 #ifdef QSW_STATS
@@ -239,26 +202,21 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
                 asm volatile("" : "+s"(dwj));
                 const int trip = dwj & 0xFF, wmax = (dwj >> 8) & 0xFF, wmin = (dwj >> 16) & 0xFF, wmin4 = wmin & ~3;
                 const int adj_voff = cs[j] * 16;
-                QS_ABL_ADJC
                 const int dc = dcs[j];
                 const int n1i = (int)A1[j], s1i = (int)S1[j];
                 const int pdif = n1i - s1i, pxq = pdif ^ (n1i + s1i);
                 const uint32_t kst = KST[j];
                 const uint32_t fixn_off = __builtin_amdgcn_raw_buffer_load_b32(adj_rsrc, (int)((kst >> 2) * (uint32_t)adj_row + (kst & 3u) * 4u) + adj_voff, 0, 0);
                 const int ng = trip >> 2;
-#if QSW_SCAT_SGPR_POS
+                // The sign / difference bit of an edge is picked with a scalar bit position (v_bfe_i32 with an SGPR offset) instead of shifting the two
+                // words by 4 per group: half a vector instruction per edge moves to the scalar unit.  BP stage 42.35 -> 42.24 ms per 65 536 headline
+                // shots against the shifting form (profiles/r05_k1sw_micro_ab.txt).
 #define QS_GROUP_POS(gi_) const int b0_ = kendw - 1 - 4 * ((gi_) - 8 * w);      /* (the words are used as they are: edge k of the word at bit kendw - 1 - k) */
-#define QS_GROUP_STEP
-#else
-#define QS_GROUP_POS(gi_) constexpr int b0_ = 31;
-#define QS_GROUP_STEP own <<= 4; xw <<= 4;
-#endif
                 // a group every lane of the wavefront has in full ...
 #define QS_GROUP_PLAIN(e4, gi_)                                                                                                      \
                 {                                                                                                                    \
                     QS_GROUP_POS(gi_)                                                                                                \
                     QS_SCAT(e4.x, 0, b0_, QS_NOFIX) QS_SCAT(e4.y, 0, b0_ - 1, QS_NOFIX) QS_SCAT(e4.z, 0, b0_ - 2, QS_NOFIX) QS_SCAT(e4.w, 0, b0_ - 3, QS_NOFIX) \
-                    QS_GROUP_STEP                                                                                                    \
                 }
                 // ... and one that reaches beyond the smallest degree: lanes past their degree add 0 to a trash slot
 #define QS_SCAT_TAIL(off, q_)                                                                                                        \
@@ -269,20 +227,15 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
                     const int k = (gi_) * 4;                                                                                         \
                     QS_GROUP_POS(gi_)                                                                                                \
                     QS_SCAT_TAIL(e4.x, 0) QS_SCAT_TAIL(e4.y, 1) QS_SCAT_TAIL(e4.z, 2) QS_SCAT_TAIL(e4.w, 3)                          \
-                    QS_GROUP_STEP                                                                                                    \
                 }
 #pragma unroll
                 for (int w = 0; w < NSW; ++w) {
                     if (32 * w < trip) {
                         const int kendw = min(trip - 32 * w, 32);
-#if QSW_SCAT_SGPR_POS
                         const uint32_t own = Q[j][w], xw = Q[j][w] ^ O[j][w];
-#else
-                        uint32_t own = Q[j][w] << (32 - kendw), xw = (Q[j][w] ^ O[j][w]) << (32 - kendw);
-#endif
                         const int g1 = min(ng, 8 * w + 8);                    // groups of this word: [8 w, g1)
                         const int gp = min(g1, max(wmin4 >> 2, 8 * w));       // ... of which [8 w, gp) are plain (as in the gather pass: three loops, no test per group)
-                        uint4 ea = (QSW_PREFETCH && j == 0 && w == 0) ? pf : QS_ADJ(8 * w), eb;
+                        uint4 ea = (j == 0 && w == 0) ? pf : QS_ADJ(8 * w), eb;
                         int gi = 8 * w;
 #pragma unroll 1
                         for (; gi + 2 <= gp; gi += 2) {                       // two groups per trip on two register sets
@@ -310,7 +263,6 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
 #undef QS_GROUP_TAIL
 #undef QS_SCAT_TAIL
 #undef QS_GROUP_POS
-#undef QS_GROUP_STEP
                 // the argmin edges carry min2, not min1: the new one gains +-(min2 - min1), the old one gives its own back
                 {
                     const int kw = (int)(kst >> 5), kendw = min(trip - 32 * kw, 32);
@@ -330,12 +282,12 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
 #pragma unroll
             for (int w = 0; w < NSW; ++w) O[j][w] = Q[j][w];
         }
-        __builtin_amdgcn_s_setprio(QSW_PRIO_BASE);
-        if (QSW_PREFETCH) pf = QS_ADJ_FIRST;              // for the next gather pass
+        __builtin_amdgcn_s_setprio(0);
+        pf = QS_ADJ_FIRST;              // for the next gather pass
         __syncthreads();
         ++t;
     }
-    if (QSW_THIN_LAST && fast && !converged) {
+    if (fast && !converged) {
         // ---- the gather pass at t = max_iter (the loop left before it).  No scatter pass follows, so its minima, signs and argmin would be thrown
         // away; what is left is the parity of the hard decisions, the convergence test of the last iteration.  Steps beyond a check's degree read a
         // trash slot, which holds 0: they cannot set bit 31.  The pass's second minima do not enter mx2 either: they are magnitudes of messages of
@@ -343,18 +295,15 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
         bool us = false;
 #pragma unroll
         for (int j = 0; j < CPL; ++j) {
-#if QSW_GPRIO
-            if (j == 0) __builtin_amdgcn_s_setprio(QSW_PRIO_BASE); else if (j == CPL - 1) __builtin_amdgcn_s_setprio((QSW_PRIO_BASE + 2) & 3); else __builtin_amdgcn_s_setprio((QSW_PRIO_BASE + 1) & 3);
-#endif
+            QSW_GATHER_PRIO(j)
             if (act[j]) {
                 int dwj = dws[j];
                 asm volatile("" : "+s"(dwj));
                 const int ng = (dwj & 0xFF) >> 2;
                 const int adj_voff = cs[j] * 16;
-                QS_ABL_ADJC
                 uint32_t hp = 0u, hpa = 0u;
 #define QS_HP_GROUP(e4) { QS_HPA(QS_ACC(e4.x)) QS_HPB(QS_ACC(e4.y)) QS_HPA(QS_ACC(e4.z)) QS_HPB(QS_ACC(e4.w)) }
-                uint4 nx = (QSW_PREFETCH && j == 0) ? pf : QS_ADJ(0);
+                uint4 nx = (j == 0) ? pf : QS_ADJ(0);
                 int gi = 0;
 #pragma unroll 1
                 for (; gi + 2 <= ng; gi += 2) {               // two groups per trip on two register sets, as in the full pass
@@ -368,20 +317,15 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
                 us = us || (((synd[j] ^ (hp >> 31)) & 1u) != 0u);
             }
         }
-#if QSW_GPRIO
-        __builtin_amdgcn_s_setprio(QSW_PRIO_BASE);
-#endif
+        __builtin_amdgcn_s_setprio(0);
         int anyun;
         QSW_VOTE(us, anyun)
-#ifndef QS_ABL_FORCE_ITERS
         if (!anyun) converged = 1;                  // (t = max_iter >= 1)
-#endif
     }
 #undef QSW_VOTE
 #undef QS_ADJ
 #undef QS_ADJ_FIRST
-#undef QS_ADJ_LOAD
-#undef QS_ABL_ADJC
+#undef QSW_GATHER_PRIO
     // L(t) - 1 is in the buffer: the scatter pass of the last iteration did not run
 
     // ---- did the bound hold?
@@ -420,7 +364,6 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
 #undef QS_ACC
 #define QS_ACC(off) (prior_g[((uint32_t)(off) - (uint32_t)sg.offA) >> 2])
 #define QS_ADJ(row_) qs_as_uint4(__builtin_amdgcn_raw_buffer_load_b128(adj_rsrc, adj_voff, (row_) * adj_row, 0))
-#define QS_ABL_ADJC
 template <int NSW>
 __global__ void __launch_bounds__(64) qd_bp_first_pass_kernel(BpGraphDev g, ScatGraphDev sg, const int32_t *prior_g, uint32_t *rec)
 {
@@ -449,7 +392,6 @@ __global__ void __launch_bounds__(64) qd_bp_first_pass_kernel(BpGraphDev g, Scat
     out[0] = r0; out[1] = r1;
 }
 #undef QS_ADJ
-#undef QS_ABL_ADJC
 #undef QS_ACC
 
 // rec: [m_pad][8] words

@@ -1,7 +1,7 @@
 // bp_scatter_wide_walk.inc -- the edge walk of one gather pass of one check (bp_scatter_wide.hip), as program text: included by
 // qd_bp_scatter_wide_kernel for every pass and by qd_bp_first_pass_kernel, which runs pass 0 once per decoder -- the same QS_EDGE_M
 // steps (bp_scatter_edge.h, with QS_MAG_MASK), trip counts, tail rules and argmin rule, so the table cannot drift from what the loop would have found.
-// In scope at the point of inclusion: j, dws, cs, S1, S2, KOLD, dcs, O, pf, a1, a2, kst, adj_row, QS_ADJ, QS_ABL_ADJC, QS_ACC.  Leaves hp, par, neg[].
+// In scope at the point of inclusion: j, dws, cs, S1, S2, KOLD, dcs, O, pf, a1, a2, kst, adj_row, QS_ADJ, QS_ACC.  Leaves hp, par, neg[].
 // "Is this the edge my last minimum came from" (min2 goes back on that edge, min1 on the others) is asked through lane masks in scalar registers, not per edge
 // on the vector ALU: lq[q] once per check and pass, gsel_ once per group of four edges (the group index is wave-uniform in all four loop forms), their AND
 // on the scalar unit, one v_cndmask per edge that takes the scalar pair -- 8-edge block of <512,8,2,2>: 101 -> 95 vector instructions (profiles/bp_argmin_masks_ab.txt).
@@ -12,7 +12,6 @@
                 asm volatile("" : "+s"(dwj));
                 const int trip = dwj & 0xFF, wmax = (dwj >> 8) & 0xFF, wmin = (dwj >> 16) & 0xFF, wmin4 = wmin & ~3;
                 const int adj_voff = cs[j] * 16;
-                QS_ABL_ADJC
                 const float s1 = S1[j], s2 = S2[j];
                 // the old argmin edge as lane masks (QS_MAG_MASK): position kold = 4 khi + klo; "none" (0xFFFFFFFF) has a khi no group reaches
                 const uint32_t khi = KOLD[j] >> 2, klo = KOLD[j] & 3u;
@@ -32,7 +31,7 @@
                         const int kend = min(trip - k0, 32);                  // multiple of 4
                         const int kplain = min(max(wmin4 - k0, 0), kend);     // groups every lane of the wavefront has in full
                         const int row0 = k0 >> 2;
-                        uint4 nx = (QSW_PREFETCH && j == 0 && w == 0) ? pf : QS_ADJ(row0);
+                        uint4 nx = (j == 0 && w == 0) ? pf : QS_ADJ(row0);
                         int kk = 0;
                         {
                             uint4 eb;                                         // two groups per trip on two register sets (bp_scatter.hip)

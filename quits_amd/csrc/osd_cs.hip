@@ -28,9 +28,7 @@
 
 #include <cstdlib>
 
-#ifndef QD_CS_NSAMP_PER_BUCKET
 #define QD_CS_NSAMP_PER_BUCKET 8
-#endif
 #define QD_CS_MAX_BUCKETS 64
 
 // sub-phase timers of a -DQD_OSD_TIMING build: -DQD_CS_SUB=1 (default) panel phase, 2 the sort, 3 the sweep (tools/osdcs_timing.py)
@@ -38,9 +36,7 @@
 #define QD_CS_SUB 1
 #endif
 // priority of wavefront 0 from the head of phase [B] to the batch's last barrier (1 and 2 measured no different: profiles/r06_osdcs_steps.txt)
-#ifndef QD_CS_B_PRIO
 #define QD_CS_B_PRIO 3
-#endif
 #ifdef QD_OSD_TIMING
 #define QD_SUBT(mode, slot) if constexpr (QD_CS_SUB == mode) { const unsigned long long n2_ = wall_clock64(); acc_[slot] += n2_ - sub_; sub_ = n2_; }
 #define QD_SUBT0(mode) if constexpr (QD_CS_SUB == mode) { sub_ = wall_clock64(); }

@@ -461,10 +461,7 @@ __device__ __noinline__ void qd_osd_sweep_pick(const OsdRegArgs &a, unsigned cha
 // the batch stays in Q planes 0..QD_PANEL_PLANES-1.  Returns the new pivot count; *done_out = syndrome explained.
 #define QD_PANEL_SLOTS 4
 #define QD_PANEL_PLANES 2   // (3 measured slower: late batches hold few pivots, the fixed cost of compaction + call exceeds a handful of barrier rounds)
-#ifndef QD_OSD_PANEL_INLINE
-#define QD_OSD_PANEL_INLINE __forceinline__
-#endif
-__device__ QD_OSD_PANEL_INLINE int qd_osd_panel_wave0(const OsdLds &S, const uint16_t *list, int nL, int npiv0, uint32_t outside_resid,
+__device__ __forceinline__ int qd_osd_panel_wave0(const OsdLds &S, const uint16_t *list, int nL, int npiv0, uint32_t outside_resid,
                                                int m_pad, int *done_out)
 {
     const int lane = threadIdx.x & 63;
@@ -555,13 +552,11 @@ __device__ QD_OSD_PANEL_INLINE int qd_osd_panel_wave0(const OsdLds &S, const uin
     return npiv;
 }
 
+// Register budget.  Full-rank instantiation: one workgroup per CU, so twice the registers.  Else 512 threads: two workgroups per CU, 128 registers.  (Rounds 2-5: three per CU
+// at 85 registers and 88-144 bytes of scratch per lane -- the faster trade while this was THE OSD-0 kernel; since round 4 it only takes the shots qd_osd0_sr_kernel
+// hands over and the windows that kernel does not fit, and a fall-back does not get to spill: ScratchSize 0, tests/test_api.py)
 template <int T, int RPT, bool WFULL>
-#ifndef QD_OSD0_WPS
-#define QD_OSD0_WPS (T == 512 ? 4 : T / 128)   // 512 threads: two workgroups per CU, 128 registers.  (Rounds 2-5: three per CU at 85 registers and 88-144 bytes of
-                                               // scratch per lane -- the faster trade while this was THE OSD-0 kernel; since round 4 it only takes the shots qd_osd0_sr_kernel
-                                               // hands over and the windows that kernel does not fit, and a fall-back does not get to spill: ScratchSize 0, tests/test_api.py)
-#endif
-__global__ void __launch_bounds__(T, (WFULL ? T / 256 : QD_OSD0_WPS)) qd_osd0_reg_kernel(OsdRegArgs a)   // full-rank instantiation: one workgroup per CU, so twice the registers
+__global__ void __launch_bounds__(T, (WFULL ? T / 256 : (T == 512 ? 4 : T / 128))) qd_osd0_reg_kernel(OsdRegArgs a)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     const int tid = threadIdx.x;
@@ -667,7 +662,8 @@ __global__ void __launch_bounds__(T, (WFULL ? T / 256 : QD_OSD0_WPS)) qd_osd0_re
                 if (tid == 0) red[64] = 0u;
                 if (tid < 64) S.bcols[tid] = (base + tid < cnt) ? (uint32_t)order[base + tid] : 0xFFFFFFFFu;
                 __syncthreads();
-                if constexpr (want_full && QD_OSD_FULL_PAIRS) {
+                if constexpr (want_full) {
+                // full-rank elimination: loop over the (column, pivot) incidences (the row-wise form below, Q rows being dense by then, measured 30 % slower)
                 for (int x = tid; x < 64 * a.max_cdeg; x += T) {
                     const int c = x / a.max_cdeg, q = x - c * a.max_cdeg;
                     const uint32_t col = S.bcols[c];

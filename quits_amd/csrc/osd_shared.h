@@ -52,20 +52,11 @@ __device__ __forceinline__ void qd_bitonic_u64(uint64_t *buf, int P, int tid)
 // and the first QD_OSD_KWR Q planes in registers; LDS holds a write-through mirror that other threads read when one of
 // those rows becomes the pivot row.  Q planes beyond the LDS budget spill to HBM (rare: > 64 * f_kw pivots).
 #define QD_OSD_TIER 1024
-#ifndef QD_OSD_FULL_PAIRS
-#define QD_OSD_FULL_PAIRS 1   // full-rank elimination: loop over the (column, pivot) incidences (the row-wise form, Q rows being dense by then, measured 30 % slower)
-#endif
-#ifndef QD_OSD_TIER_FIRST
 #define QD_OSD_TIER_FIRST 256
-#endif
 #define QD_OSD_KWR 6
-#ifndef QD_OSD_KWR0
 #define QD_OSD_KWR0 2
-#endif
-#ifndef QD_OSD_KPT
-#define QD_OSD_KPT 1      // (20, i.e. every key of the headline window held in registers, was the round-1 choice: see qd_osd_draw_tier)
-#endif
-//      QD_OSD_KPT        // monotone keys a thread keeps in registers while a tier is drawn (windows with n <= KPT * T; else re-read)
+#define QD_OSD_KPT 1      // monotone keys a thread keeps in registers while a tier is drawn (windows with n <= KPT * T; else re-read).
+                          // (20, i.e. every key of the headline window held in registers, was the round-1 choice: see qd_osd_draw_tier)
 
 // Sum of v over the workgroup; one barrier; `buf` = 2 x 64 words alternating with `phase` (entries beyond the wave count must be zero).
 template <int T>
@@ -116,13 +107,10 @@ struct TierState {
 
 // Draws the next tier: the <= QD_OSD_TIER not yet consumed columns with the smallest (key, fault index), sorted, as fault
 // indices in order[0..cnt).  State: every column with (key, index) < (lo_key, lo_idx) has been consumed.
-#ifndef QD_OSD_TIER_INLINE
-#define QD_OSD_TIER_INLINE __forceinline__
-#endif
 // KPT = monotone keys a thread keeps in registers while the tier is drawn (used when n <= KPT * T; otherwise, and always with
 // KPT = 1 on windows of more than T faults, every radix level and the gather re-read the posteriors, which sit in L2).
 template <int T, int KPT = QD_OSD_KPT, class ARGS = OsdRegArgs, int SCAN = 0>     // ARGS: anything with n and bit_orig; SCAN: 16-byte loads in flight per pass over the posteriors (0: one float at a time)
-__device__ QD_OSD_TIER_INLINE int qd_osd_draw_tier(const ARGS &a, const float *llr, uint64_t *sortbuf, uint16_t *order,
+__device__ __forceinline__ int qd_osd_draw_tier(const ARGS &a, const float *llr, uint64_t *sortbuf, uint16_t *order,
                                              uint32_t *red, uint32_t *sumbuf, TierState &ts)
 {
     const int tid = threadIdx.x;

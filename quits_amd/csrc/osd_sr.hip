@@ -39,9 +39,7 @@
 #include "osd_shared.h"
 #include <algorithm>
 
-#ifndef QD_SR_TIER_GUESS
-#define QD_SR_TIER_GUESS 1       // 0: every first tier through the radix selection (A/B)
-#endif
+#define QD_SR_KWR 4              // Q planes (64 pivots each) the kernel keeps in registers (8 planes at three wavefronts per SIMD: profiles/r06_k2s_planes_ab.txt)
 struct OsdSrArgs {
     int m, n, m_pad, n_pad, mw, out_words, upd_rows, ell_log2;
     int o_tb, o_rowpiv, o_prow, o_pcol, o_ppos, o_nz, o_cand, o_stq, o_stsp, o_bcols, o_red, o_out, o_order;
@@ -60,12 +58,12 @@ struct OsdSrArgs {
 };
 
 template <int T, int RPT, int KWR>
-__global__ void __launch_bounds__(T, QD_SR_WPS_OF(RPT)) qd_osd0_sr_kernel(OsdSrArgs a)
+__global__ void __launch_bounds__(T, qd_sr_wps(RPT)) qd_osd0_sr_kernel(OsdSrArgs a)
 {
     extern __shared__ __align__(16) unsigned char smem[];
-#if QD_SR_PRIO
-    __builtin_amdgcn_s_setprio(QD_SR_PRIO);              // (see QD_SR_PRIO in qd_internal.h)
-#endif
+    // (Wavefront priority 0.  In the pipelined driver the kernel runs beside the BP kernel of the other lane, whose workgroups fill every wavefront slot: an
+    //  OSD workgroup takes the place of one BP workgroup on its CU for as long as it lives, and at equal priority it lives 2-5 times longer than alone.
+    //  At priority 3 / 2 it should leave its slots sooner: within the noise, profiles/r06_bp_stream_bubble.txt.)
     const int tid = threadIdx.x, lane = tid & 63;
     constexpr int NW = T / 64;
     static_assert(NW <= 16 && T >= 256, "key / flag records hold 16 wavefronts; the tier drawing wants >= 256 threads");
@@ -131,7 +129,7 @@ __global__ void __launch_bounds__(T, QD_SR_WPS_OF(RPT)) qd_osd0_sr_kernel(OsdSrA
             ++ntier;
             const int cnt = qd_osd_draw_tier<T, QD_OSD_KPT, OsdSrArgs, 6>(a, llr, sortbuf, order, red, sumbuf, ts);
             lo_key = ts.lo_key; lo_idx = ts.lo_idx; sphase = ts.sphase;
-            if (first_tier && QD_SR_TIER_GUESS) {
+            if (first_tier) {      // (against every first tier through the radix selection: profiles/r05_osd0_tier_guess.txt)
                 // aim the next shot's first tier at 55..85 % of its size: fuller, and a shot with a few more unreliable columns overflows it (one pass
                 // wasted, then the radix selection); emptier, and more shots need a second tier
                 const uint32_t lim1 = (uint32_t)a.tier_first, step = 1u << 20;      // an eighth of a binade of the monotone key
@@ -377,7 +375,8 @@ __global__ void __launch_bounds__(T, QD_SR_WPS_OF(RPT)) qd_osd0_sr_kernel(OsdSrA
 int qd_osd_sr_layout(int m, int m_pad, int n, int out_words, int *off13, int *threads, int *rpt)
 {
     if (m > 2048 || n > 49152) return 0;              // rows per thread <= 4 at 512 threads; ppos holds 10 bits of batch number
-    const int T = m <= 256 ? 256 : (m <= 4 * QD_SR_TSMALL ? QD_SR_TSMALL : 512);     // windows of <= 256 checks: one row per thread on four wavefronts
+    const int T = m <= 256 ? 256 : 512;               // windows of <= 256 checks: one row per thread on four wavefronts (256 threads x 4 rows up to 1024
+                                                      // detectors against 512 x 2: profiles/r06_osd0_shape_pipelined_ab.txt)
     *threads = T; *rpt = (m + T - 1) / T;
     auto al = [](int x) { return (x + 15) & ~15; };
     int o = 0;
@@ -388,7 +387,7 @@ int qd_osd_sr_layout(int m, int m_pad, int n, int out_words, int *off13, int *th
     off13[4] = o; o += al(m_pad * 2);                 // ppos
     off13[5] = o; o += al(((m + 63) / 64) * 8);       // nz
     off13[6] = o; o += 3 * 80 * 4;                    // cand
-    off13[7] = o; o += (QD_SR_KWR_MAX + 1) * 64 * 8;  // stq
+    off13[7] = o; o += (QD_SR_KWR + 1) * 64 * 8;      // stq
     off13[8] = o; o += 64 * 4;                        // stsp
     off13[9] = o; o += 64 * 4;                        // bcols
     off13[10] = o; o += 1024;                         // red
@@ -401,8 +400,8 @@ int qd_osd_sr_layout(int m, int m_pad, int n, int out_words, int *off13, int *th
 size_t qd_osd_sr_ws_words(int m_pad, int mw, int threads, int rpt)
 {
     (void)threads;
-    const int kwr = QD_SR_KWR_OF(rpt);
-    return (size_t)(mw > kwr ? mw - kwr : 0) * m_pad + 64;
+    (void)rpt;
+    return (size_t)(mw > QD_SR_KWR ? mw - QD_SR_KWR : 0) * m_pad + 64;
 }
 
 hipError_t qd_launch_osd0_sr(const OsdGraphDev &g, const BpGraphDev &bg, const DecodeArgs &a, int blocks, hipStream_t s)
@@ -422,7 +421,7 @@ hipError_t qd_launch_osd0_sr(const OsdGraphDev &g, const BpGraphDev &bg, const D
     const int lds = g.s_lds_bytes;
 #define QD_SR_CASE(TT, RR)                                                                                                        \
     {                                                                                                                             \
-        auto k = qd_osd0_sr_kernel<TT, RR, QD_SR_KWR_OF(RR)>;                                                                            \
+        auto k = qd_osd0_sr_kernel<TT, RR, QD_SR_KWR>;                                                                     \
         hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);                     \
         if (e != hipSuccess) return e;                                                                                            \
         hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(TT), lds, s, r);                                                       \

@@ -981,7 +981,7 @@ static int build_osd(qd_graph *g, const HostGraph &h)
         const int lds = qd_osd_sr_layout(m, m_pad, n, out_words, od.s_off, &od.s_threads, &od.s_rpt);
         if (lds > 0 && lds <= QD_LDS_BYTES) {
             od.s_lds_bytes = lds;
-            od.s_per_cu = std::max(1, std::min(QD_LDS_BYTES / lds, QD_SR_WPS_OF(od.s_rpt) * 256 / od.s_threads));   // the kernel's register budget (wavefronts per SIMD)
+            od.s_per_cu = std::max(1, std::min(QD_LDS_BYTES / lds, qd_sr_wps(od.s_rpt) * 256 / od.s_threads));   // the kernel's register budget (wavefronts per SIMD)
         }
     }
     // the full kernel sorts all n columns in LDS; windows too large for that rely on the register kernel alone

@@ -7,24 +7,9 @@
 #define QD_MAX_COL_DEG 16      // bit-side sign copy is a uint16 per fault
 #define QD_MAX_ROW_DEG 255     // edge position inside a check is a byte
 #define QD_LDS_BYTES (160 * 1024)
-#ifndef QD_SR_KWR
-#define QD_SR_KWR 4            // Q planes (64 pivots each) qd_osd0_sr_kernel keeps in registers (variant builds: -DQD_SR_KWR=8 -DQD_SR_WPS12=3)
-#endif
-#ifndef QD_SR_WPS12
-#define QD_SR_WPS12 4          // wavefronts per SIMD the register budget of its one- and two-rows-per-thread shapes is cut for
-#endif
-#ifndef QD_SR_KWR_OF
-#define QD_SR_KWR_OF(rpt) QD_SR_KWR
-#endif
-#ifndef QD_SR_WPS_OF
-#define QD_SR_WPS_OF(rpt) ((rpt) <= 2 ? QD_SR_WPS12 : 2)   // wavefronts per SIMD its register budget is cut for: 128 / 256 registers -- no instantiation may
-                                                 // spill vector registers (scalar registers it cannot keep live in lanes of vector registers)
-#endif
-#ifndef QD_SR_TSMALL
-#define QD_SR_TSMALL 512       // its workgroup size for windows of <= 1024 detectors
-#endif
-//      QD_SR_KWR_OF(rpt)       // Q planes (64 pivots each) the many-pivots-per-round OSD-0 kernel keeps in registers at rpt rows per thread (osd_sr.hip)
-#define QD_SR_KWR_MAX (QD_SR_KWR > 4 ? QD_SR_KWR : 4)
+// wavefronts per SIMD the register budget of qd_osd0_sr_kernel (osd_sr.hip) is cut for at rpt rows per thread: 128 / 256 registers -- no instantiation may
+// spill vector registers (scalar registers it cannot keep live in lanes of vector registers)
+constexpr int qd_sr_wps(int rpt) { return rpt <= 2 ? 4 : 2; }
 
 // One window's Tanner graph as the BP kernel wants it.
 //   check slots: checks sorted by degree (descending); bit slots: faults sorted by degree (descending), so that a
@@ -91,13 +76,9 @@ struct ScatArgs {
 
 // The general (one message per edge) BP kernel's view: plain CSR + CSC in fault / detector order, prior LLRs in float.
 // column-weight bound the per-edge kernel's serial schedule unrolls for (register arrays of that length, record width)
-#ifndef QD_GEN_D6
-#define QD_GEN_D6 0           // 1: a weight-6 instantiation between 4 and 8 (A/B, profiles/r05_k1g_*)
-#endif
-static inline int qd_gen_unroll(int max_cdeg) { return max_cdeg <= 4 ? 4 : ((QD_GEN_D6 && max_cdeg <= 6) ? 6 : (max_cdeg <= 8 ? 8 : QD_MAX_COL_DEG)); }
-#ifndef QD_GEN_GS
+// (a weight-6 instantiation between 4 and 8 was no faster: profiles/r05_k1g_register_budget_ab.txt)
+static inline int qd_gen_unroll(int max_cdeg) { return max_cdeg <= 4 ? 4 : (max_cdeg <= 8 ? 8 : QD_MAX_COL_DEG); }
 #define QD_GEN_GS 4           // wavefronts per 64 shots in the serial schedule (faults of one dependency level in parallel)
-#endif
 struct GenGraphDev {
     int m, n, nnz, out_words;
     const int32_t *rp, *ci;     // [m + 1], [nnz]   CSR, columns ascending in a row
@@ -140,11 +121,6 @@ struct GenWs {
 // prefixes and posteriors are rebuilt by every sweep), so the survivors' columns of those two planes are copied to consecutive columns of `next`
 // and the next launch runs on full wavefronts (bp.hpp's shot loop has no such problem: one shot, one thread; here a lane that has converged
 // idles until the slowest of its 64 shots is done -- 31 % of the lanes of the reference-settings windows, profiles/r05_k1g_load_curve.txt).
-// Wavefront priority of qd_osd0_sr_kernel.  In the pipelined driver it runs beside the BP kernel of the other lane, whose workgroups fill every wavefront
-// slot: an OSD workgroup takes the place of one BP workgroup on its CU for as long as it lives, and at equal priority it lives 2-5 times longer than alone.
-#ifndef QD_SR_PRIO
-#define QD_SR_PRIO 0
-#endif
 // hipEventQuery without side effects: "not ready" is an answer, not an error -- it must not be what a later hipGetLastError() behind a kernel launch reports
 static inline bool qd_event_done(hipEvent_t e)
 {

@@ -239,6 +239,32 @@ def test_serial_edge_kernel_keeps_five_workgroups_per_cu(tmp_path):
     assert all(v <= 96 and sc == 0 for _, v, sc in serial), serial
 
 
+def test_kernel_sources_fork_only_on_the_instrumentation_switches():
+    """The kernels hold the code that ships: a preprocessor conditional under quits_amd/csrc tests an instrumentation build's switch (the
+    phase timers, the scatter statistics), qd_math.h's include guard or its host / device test -- nothing else."""
+    allowed = {"QD_BP_TIMING", "QD_OSD_TIMING", "QD_CS_SUB", "QD_LSD_TIMING", "QSW_STATS", "QD_MATH_H", "__HIPCC__"}
+    cs = os.path.join(ROOT, "quits_amd", "csrc")
+    found = []
+    for name in sorted(os.listdir(cs)):
+        path = os.path.join(cs, name)
+        if not os.path.isfile(path):
+            continue
+        lines = open(path, errors="replace").read().split("\n")
+        for no, line in enumerate(lines, 1):
+            m = re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b(.*)", line)
+            if not m:
+                continue
+            cond, nxt = m.group(2), no
+            while cond.endswith("\\") and nxt < len(lines):           # a continued condition counts at its first line
+                cond, nxt = cond[:-1] + " " + lines[nxt], nxt + 1
+            cond = re.sub(r"//.*|/\*.*?\*/", "", cond)
+            found += [(name, no, ident) for ident in re.findall(r"[A-Za-z_]\w*", cond) if ident != "defined"]
+    assert found, "no conditional found: the scan is broken"
+    bad = [f for f in found if f[2] not in allowed]
+    assert not bad, ("compile-time switches beyond the instrumentation builds: " + ", ".join("%s:%d tests %s" % b for b in bad) +
+                     " -- an experiment is built as a variant library on a branch and recorded under profiles/, not forked in the tree")
+
+
 def test_lane_groups_of_the_pipelined_driver():
     """Chunks are dealt to the driver's lanes in as few groups as possible, as even as they come, in order."""
     from quits_amd.decoder.sliding_window import lane_groups

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""profiles/pmc_traffic.json entries from one evidence set (tools/r04_evidence.sh <tag> -> gpurun_out/):
+"""profiles/pmc_traffic.json entries from one evidence set (the round-4 evidence script, now at the parent of the commit that removed the round-numbered scripts):
   python tools/derive_pmc.py <tag> <profiles-prefix>      e.g.  python tools/derive_pmc.py r04 r04
 HBM bytes per launch = FETCH_SIZE x 2 (gfx950 correction of MI355X_MICROARCH.md) + WRITE_SIZE, separate rocprofv3 --pmc passes, largest
 dispatch of the kernel; SQ ratios from the single-launch counter passes (tools/pmc_bp_kernel.sh, tools/pmc_osd_kernel.sh)."""

@@ -21,7 +21,7 @@ def main():
             cur = {"name": m.group(1)}
             rows.append(cur)
             continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[bytes/(?:lane|block)\])?: (\d+)", ln)
+        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]+\])?: (\d+)", ln)
         if m and cur is not None:
             cur[m.group(1).strip()] = int(m.group(2))
     dem = subprocess.run(["c++filt"] + [r["name"] for r in rows], capture_output=True, text=True).stdout.splitlines()
