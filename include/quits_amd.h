@@ -96,7 +96,7 @@ typedef struct qd_params {
     double ms_scaling_factor;   /* not exposed by the reference wrapper -> ldpc default 1.0; 0 = 1-2^-it */
 } qd_params;
 
-int qd_version(void);                 /* 107 (107: off-chip windows decode, QD_FLAG_OFF_CHIP, QD_POST_OSD0_OFFCHIP, no new export; 106: qd_circuit_create accepts the biased-noise opcodes Y_ERROR / PAULI_CHANNEL_1 / PAULI_CHANNEL_2, no new export; 105: qd_decoder_fast_start; 104: qd_circuit_* + qd_sample_circuit; 103: qd_decoder_post_head_start; 101: qd_graph_info wrote 12 entries; 102: 10 again + qd_graph_info_ex) */
+int qd_version(void);                 /* 108 (108: qd_shot_flags_fold, qd_tally_batch, qd_sample_circuit_shots, qd_sample_dem_shots; 107: off-chip windows decode, QD_FLAG_OFF_CHIP, QD_POST_OSD0_OFFCHIP, no new export; 106: qd_circuit_create accepts the biased-noise opcodes Y_ERROR / PAULI_CHANNEL_1 / PAULI_CHANNEL_2, no new export; 105: qd_decoder_fast_start; 104: qd_circuit_* + qd_sample_circuit; 103: qd_decoder_post_head_start; 101: qd_graph_info wrote 12 entries; 102: 10 again + qd_graph_info_ex) */
 const char *qd_last_error(void);
 /* Number of visible HIP devices (0 if none): lets a host fail loudly before building anything. */
 int qd_device_count(void);
@@ -236,12 +236,44 @@ int qd_unpack_bits(const uint32_t *d_bits, int64_t stride_words, int32_t nbits, 
 int qd_count_mismatch(const uint8_t *d_pred, const uint8_t *d_obs, int32_t k, int64_t B, int64_t *d_count,
                       void *stream);
 
+/* ---- a memory experiment's bookkeeping, on the device.  The reference compares on the host (tests/test_sliding_window.py:83:
+ *      `pL = np.sum((logical_pred != observable_flips).any(axis=1)) / num_trials`) and has nothing to say about which observable
+ *      failed or how the failing shots were decoded; quits_amd.simulation.get_circuit_mem_pL runs sampler -> decoder -> these two. */
+
+/* Flag byte per shot: what happened to it in ANY window of a sliding-window decode. */
+#define QD_SHOT_POST 1          /* some window's output came from the post-processor (QD_STATUS_OSD)   */
+#define QD_SHOT_INCONSISTENT 2  /* ... QD_STATUS_INCONSISTENT                                          */
+#define QD_SHOT_INEXACT 4       /* ... QD_STATUS_INEXACT                                               */
+#define QD_SHOT_COARSE 8        /* ... QD_STATUS_COARSE_GRID: the shot left the fine LLR grid          */
+/* d_flags[b] |= the QD_SHOT_* bits of d_status[b], b < B: call once per window with that window's status words (qd_decode_batch) on a
+ * zeroed d_flags.  Stands in for `(status & QD_STATUS_OSD) != 0` and its kin computed by the host per window and ORed over the windows;
+ * no reference counterpart (ldpc's decoders report `converge` per decode call and the reference drops it, sliding_window.py:171). */
+int qd_shot_flags_fold(const int32_t *d_status, int64_t B, uint8_t *d_flags, void *stream);
+
+/* Tallies of a decoded batch, accumulated into d_counts (int64 [QD_TALLY_HEAD + k] on the device, zeroed by the caller before the first call):
+ *   [0] shots, [1] failing shots -- prediction != observable flips on the low bit of any of the k bytes, exactly what qd_count_mismatch counts
+ *   (the `pL` numerator of tests/test_sliding_window.py:83);  [2 + 2j], [3 + 2j], j = 0 .. 3: shots / failing shots with bit j of d_flags[b]
+ *   set (QD_SHOT_POST, _INCONSISTENT, _INEXACT, _COARSE; all zero when d_flags is NULL);  [QD_TALLY_HEAD + i]: shots whose observable i is
+ *   mispredicted (`(logical_pred != observable_flips).sum(axis=0)`).
+ * d_pred, d_obs: B rows of k bytes with row strides pred_stride, obs_stride >= k (column slices of wider arrays are fine), 1 <= k <= QD_TALLY_MAX_K.
+ * d_fail_mask, if not NULL: ceil(B / 64) words, WRITTEN (not accumulated): bit l of word w = shot 64 w + l failed; bits past B are zero.
+ * One launch; the number of global atomics does not depend on B. */
+#define QD_TALLY_HEAD 10
+#define QD_TALLY_MAX_K 4096
+int qd_tally_batch(const uint8_t *d_pred, int64_t pred_stride, const uint8_t *d_obs, int64_t obs_stride, int32_t k, int64_t B,
+                   const uint8_t *d_flags, int64_t *d_counts, uint64_t *d_fail_mask, void *stream);
+
 /* ---- synthetic input: stands in for stim's detector sampler (simulation.py:23-27), absent here.
  *      e_j ~ Bernoulli(priors_j) (Philox4x32-10, key = seed, counter = (shot0 + b, j / 4)), s = H e, o = L e.
  *      Ht / Lt are the TRANSPOSES as CSR (row j = fault j -> detectors / observables it flips).
  *      d_det: B x det_stride bytes (first m columns written), d_obs: B x obs_stride bytes. */
 int qd_sample_dem(const qd_spmat *Ht, const qd_spmat *Lt, const double *priors, uint64_t seed, int64_t shot0,
                   int64_t B, uint8_t *d_det, int64_t det_stride, uint8_t *d_obs, int64_t obs_stride, void *stream);
+/* The same for the shots d_shots[0 .. B - 1] (int64 on the device, >= 0, any order, repeats allowed, not bounded by 2^32): row b is what
+ * qd_sample_dem(..., shot0 = d_shots[b], B = 1, ...) writes.  Stands in for sampling a range again and indexing it
+ * (`sampler.sample(shots)[0][indices]`, simulation.py:23-27 -- Stim can only draw a whole range again); B <= 2^31 - 1. */
+int qd_sample_dem_shots(const qd_spmat *Ht, const qd_spmat *Lt, const double *priors, uint64_t seed, const int64_t *d_shots, int64_t B,
+                        uint8_t *d_det, int64_t det_stride, uint8_t *d_obs, int64_t obs_stride, void *stream);
 
 /* ---- circuit-level input: a Pauli-frame simulation of the circuit itself (what stim's compile_detector_sampler().sample(...,
  *      separate_observables=True) returns, simulation.py:8-28), without gauge randomisation: exact when every detector and observable
@@ -262,6 +294,12 @@ int qd_circuit_info(const qd_circuit *c, int64_t *info);
  * consecutive shot0 compose.  d_det: B x det_stride bytes (first ndet columns written), d_obs: B x obs_stride bytes.  Asynchronous. */
 int qd_sample_circuit(const qd_circuit *c, uint64_t seed, int64_t shot0, int64_t B, uint8_t *d_det, int64_t det_stride,
                       uint8_t *d_obs, int64_t obs_stride, void *stream);
+/* The same for the shots d_shots[0 .. B - 1] (int64 on the device, >= 0, any order, repeats allowed, not bounded by 2^32): row b is what
+ * qd_sample_circuit(..., shot0 = d_shots[b], B = 1, ...) writes -- the stream depends on (seed, shot, site) only, so a shot is regenerated
+ * from its index.  Stands in for `compile_detector_sampler(seed).sample(shots)[indices]` (simulation.py:8-28), which has to draw every
+ * shot up to the largest index again.  Asynchronous. */
+int qd_sample_circuit_shots(const qd_circuit *c, uint64_t seed, const int64_t *d_shots, int64_t B, uint8_t *d_det, int64_t det_stride,
+                            uint8_t *d_obs, int64_t obs_stride, void *stream);
 
 #ifdef __cplusplus
 }

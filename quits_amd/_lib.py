@@ -23,6 +23,9 @@ STATUS_CONVERGED = 1 << 16
 STATUS_OSD = 1 << 17
 STATUS_INCONSISTENT = 1 << 18
 STATUS_ZERO = 1 << 19
+SHOT_POST, SHOT_INCONSISTENT, SHOT_INEXACT, SHOT_COARSE = 1, 2, 4, 8     # QD_SHOT_*: the flag byte qd_shot_flags_fold keeps per shot
+SHOT_FLAG_NAMES = ("post", "inconsistent", "inexact", "coarse")         # ... bit j <-> name j
+TALLY_HEAD = 10                                                         # QD_TALLY_HEAD
 
 
 class QdParams(C.Structure):
@@ -45,6 +48,7 @@ EXPORTS = [
     "qd_decoder_set_profiling", "qd_decoder_profile", "qd_decoder_post_head_start", "qd_decoder_debug_counters", "qd_spmat_create", "qd_spmat_destroy", "qd_gf2_spmv_batch",
     "qd_unpack_bits", "qd_count_mismatch", "qd_sample_dem",
     "qd_circuit_create", "qd_circuit_destroy", "qd_circuit_info", "qd_sample_circuit",
+    "qd_shot_flags_fold", "qd_tally_batch", "qd_sample_circuit_shots", "qd_sample_dem_shots",
 ]
 
 
@@ -109,6 +113,11 @@ def load():
     L.qd_circuit_destroy.restype = None
     L.qd_circuit_info.argtypes = [vp, vp]
     L.qd_sample_circuit.argtypes = [vp, u64, i64, i64, vp, i64, vp, i64, vp]
+    if hasattr(L, "qd_tally_batch"):                # (library version 108; an older library named by QUITS_AMD_LIB samples and decodes as before)
+        L.qd_shot_flags_fold.argtypes = [vp, i64, vp, vp]
+        L.qd_tally_batch.argtypes = [vp, i64, vp, i64, i32, i64, vp, vp, vp, vp]
+        L.qd_sample_circuit_shots.argtypes = [vp, u64, vp, i64, vp, i64, vp, i64, vp]
+        L.qd_sample_dem_shots.argtypes = [vp, vp, vp, u64, vp, i64, vp, i64, vp, i64, vp]
     _lib = L
     return L
 
@@ -116,6 +125,13 @@ def load():
 def check(rc):
     if rc != 0:
         raise QdError(rc, load().qd_last_error().decode(errors="replace"))
+
+
+def require_experiment(L):
+    """The entry points of library version 108 (tallies, flag fold, list sampling): a clear error from an older library."""
+    if not hasattr(L, "qd_tally_batch"):
+        raise RuntimeError("quits_amd: %s is version %d; the device-resident memory experiment needs >= 108 -- rebuild it" % (LIB_PATH, L.qd_version()))
+    return L
 
 
 def require_gpu():

@@ -88,7 +88,8 @@ __device__ __forceinline__ void qd_frame_noise(const int32_t *__restrict__ ins, 
 // admits only the opcodes below, and an arm that set pc = prog_len made the compiler wrap every ds_xor_b64 of the noise sites in a
 // wave reduction (v_mbcnt / s_bcnt1 / s_mul per XOR), 7 % on BB144 r12.
 template <bool CHANNELS>
-__global__ void __launch_bounds__(QD_WAVE) qd_frame_sample_kernel(FrameDev c, uint32_t k0, uint32_t k1, int64_t shot0, int64_t B,
+__global__ void __launch_bounds__(QD_WAVE) qd_frame_sample_kernel(FrameDev c, uint32_t k0, uint32_t k1, int64_t shot0,
+                                                                   const int64_t *__restrict__ shot_list, int64_t B,
                                                                    uint8_t *__restrict__ det, int64_t det_stride,
                                                                    uint8_t *__restrict__ obs, int64_t obs_stride)
 {
@@ -97,7 +98,8 @@ __global__ void __launch_bounds__(QD_WAVE) qd_frame_sample_kernel(FrameDev c, ui
     const int lane = threadIdx.x;
     const int64_t b0 = (int64_t)blockIdx.x * QD_WAVE;
     const int rows = (int)min<int64_t>(QD_WAVE, B - b0);
-    const uint64_t shot = (uint64_t)(shot0 + b0 + lane);
+    // row b0 + l is shot shot0 + b0 + l, or shot_list[b0 + l] (qd_sample_circuit_shots: any order, repeats allowed); a lane past the batch draws for a shot nobody reads
+    const uint64_t shot = (uint64_t)(shot_list && lane < rows ? shot_list[b0 + lane] : shot0 + b0 + lane);
     const uint32_t s_lo = (uint32_t)shot, s_hi = (uint32_t)(shot >> 32);
     for (int i = lane; i < 2 * c.nq + c.ring + c.nobs; i += QD_WAVE) fsm[i] = 0ull;
     __syncthreads();
@@ -206,16 +208,16 @@ __global__ void __launch_bounds__(QD_WAVE) qd_frame_sample_kernel(FrameDev c, ui
     }
 }
 
-hipError_t qd_launch_frame_sample(const FrameDev &c, uint64_t seed, int64_t shot0, int64_t B, uint8_t *det, int64_t det_stride,
-                                  uint8_t *obs, int64_t obs_stride, hipStream_t s)
+hipError_t qd_launch_frame_sample(const FrameDev &c, uint64_t seed, int64_t shot0, const int64_t *shot_list, int64_t B, uint8_t *det,
+                                  int64_t det_stride, uint8_t *obs, int64_t obs_stride, hipStream_t s)
 {
     if (B <= 0) return hipSuccess;
     const dim3 grid((unsigned)((B + QD_WAVE - 1) / QD_WAVE));
     if (c.channels)
         hipLaunchKernelGGL(qd_frame_sample_kernel<true>, grid, dim3(QD_WAVE), (size_t)c.lds_bytes, s, c, (uint32_t)seed,
-                           (uint32_t)(seed >> 32), shot0, B, det, det_stride, obs, obs_stride);
+                           (uint32_t)(seed >> 32), shot0, shot_list, B, det, det_stride, obs, obs_stride);
     else
         hipLaunchKernelGGL(qd_frame_sample_kernel<false>, grid, dim3(QD_WAVE), (size_t)c.lds_bytes, s, c, (uint32_t)seed,
-                           (uint32_t)(seed >> 32), shot0, B, det, det_stride, obs, obs_stride);
+                           (uint32_t)(seed >> 32), shot0, shot_list, B, det, det_stride, obs, obs_stride);
     return hipGetLastError();
 }

@@ -85,8 +85,8 @@ __global__ void qd_count_mismatch_kernel(const uint8_t *__restrict__ pred, const
 // oq_sample_dem (oracle/qd_oracle.c): Philox4x32-10, key = seed, counter = (shot lo, shot hi, j / 4, 0); word j & 3
 // fires fault j iff it is < floor(p_j * 2^32) (qd_philox4x32_10: qd_internal.h).  One workgroup per shot, detector/observable bits accumulated in LDS.
 __global__ void qd_sample_dem_kernel(SpmatDev Ht, SpmatDev Lt, const uint32_t *__restrict__ thr, uint32_t k0,
-                                     uint32_t k1, int64_t shot0, int m, int nobs, uint8_t *det, int64_t det_stride,
-                                     uint8_t *obs, int64_t obs_stride)
+                                     uint32_t k1, int64_t shot0, const int64_t *__restrict__ shot_list, int m, int nobs, uint8_t *det,
+                                     int64_t det_stride, uint8_t *obs, int64_t obs_stride)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     uint32_t *dbits = reinterpret_cast<uint32_t *>(smem);
@@ -94,7 +94,7 @@ __global__ void qd_sample_dem_kernel(SpmatDev Ht, SpmatDev Lt, const uint32_t *_
     uint32_t *obits = dbits + dwords;
     const int tid = threadIdx.x, T = blockDim.x;
     const int64_t b = blockIdx.x;
-    const uint64_t shot = (uint64_t)(shot0 + b);
+    const uint64_t shot = (uint64_t)(shot_list ? shot_list[b] : shot0 + b);     // (qd_sample_dem_shots: row b is shot shot_list[b])
     for (int w = tid; w < dwords + owords; w += T) dbits[w] = 0u;
     __syncthreads();
     const int n = Ht.nrows;
@@ -194,12 +194,12 @@ hipError_t qd_launch_count(const uint8_t *pred, const uint8_t *obs, int k, int64
 }
 
 hipError_t qd_launch_sample(const SpmatDev &Ht, const SpmatDev &Lt, const uint32_t *thr, uint64_t seed, int64_t shot0,
-                            int64_t B, int m, int nobs, uint8_t *det, int64_t det_stride, uint8_t *obs,
+                            const int64_t *shot_list, int64_t B, int m, int nobs, uint8_t *det, int64_t det_stride, uint8_t *obs,
                             int64_t obs_stride, hipStream_t s)
 {
     if (B == 0) return hipSuccess;
     const size_t lds = sizeof(uint32_t) * (size_t)(((m + 31) >> 5) + ((nobs + 31) >> 5));
     hipLaunchKernelGGL(qd_sample_dem_kernel, dim3((unsigned)B), dim3(256), lds, s, Ht, Lt, thr, (uint32_t)seed,
-                       (uint32_t)(seed >> 32), shot0, m, nobs, det, det_stride, obs, obs_stride);
+                       (uint32_t)(seed >> 32), shot0, shot_list, m, nobs, det, det_stride, obs, obs_stride);
     return hipGetLastError();
 }

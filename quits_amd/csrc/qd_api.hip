@@ -50,8 +50,12 @@ hipError_t qd_launch_unpack(const uint32_t *bits, int64_t stride_words, int nbit
                             int64_t out_stride, hipStream_t s);
 hipError_t qd_launch_count(const uint8_t *pred, const uint8_t *obs, int k, int64_t B, int64_t *count, hipStream_t s);
 hipError_t qd_launch_sample(const SpmatDev &Ht, const SpmatDev &Lt, const uint32_t *thr, uint64_t seed, int64_t shot0,
-                            int64_t B, int m, int nobs, uint8_t *det, int64_t det_stride, uint8_t *obs,
+                            const int64_t *shot_list, int64_t B, int m, int nobs, uint8_t *det, int64_t det_stride, uint8_t *obs,
                             int64_t obs_stride, hipStream_t s);
+// experiment.hip: the flag byte per shot and the tallies of a memory experiment
+hipError_t qd_launch_shot_flags(const int32_t *status, int64_t B, uint8_t *flags, hipStream_t s);
+hipError_t qd_launch_tally(const uint8_t *pred, int64_t pred_stride, const uint8_t *obs, int64_t obs_stride, int k, int64_t B,
+                           const uint8_t *flags, int64_t *counts, uint64_t *fail_mask, hipStream_t s);
 
 static thread_local char g_err[512] = "";
 
@@ -385,7 +389,7 @@ static void scatter_walk(int m, const int32_t *row_ptr, const int32_t *col_idx, 
     }
 }
 
-extern "C" int qd_version(void) { return 107; }      // 107: off-chip windows decode (qd_graph_create used to refuse them), QD_FLAG_OFF_CHIP, QD_POST_OSD0_OFFCHIP (no new export); 106: qd_circuit_create takes Y_ERROR / PAULI_CHANNEL_1 / PAULI_CHANNEL_2 programs (no new export); 105: qd_decoder_fast_start; 104: qd_circuit_* and qd_sample_circuit; 103: qd_decoder_post_head_start; 102: qd_graph_info fills 10 entries again, qd_graph_info_ex(g, info, n) the rest; 101: qd_decoder_postproc_kernel
+extern "C" int qd_version(void) { return 108; }      // 108: qd_shot_flags_fold, qd_tally_batch, qd_sample_circuit_shots, qd_sample_dem_shots (the device-resident memory experiment); 107: off-chip windows decode (qd_graph_create used to refuse them), QD_FLAG_OFF_CHIP, QD_POST_OSD0_OFFCHIP (no new export); 106: qd_circuit_create takes Y_ERROR / PAULI_CHANNEL_1 / PAULI_CHANNEL_2 programs (no new export); 105: qd_decoder_fast_start; 104: qd_circuit_* and qd_sample_circuit; 103: qd_decoder_post_head_start; 102: qd_graph_info fills 10 entries again, qd_graph_info_ex(g, info, n) the rest; 101: qd_decoder_postproc_kernel
 extern "C" const char *qd_last_error(void) { return g_err; }
 extern "C" int qd_device_count(void)
 {
@@ -1746,9 +1750,9 @@ extern "C" int qd_count_mismatch(const uint8_t *d_pred, const uint8_t *d_obs, in
     return QD_OK;
 }
 
-extern "C" int qd_sample_dem(const qd_spmat *Ht, const qd_spmat *Lt, const double *priors, uint64_t seed, int64_t shot0,
-                             int64_t B, uint8_t *d_det, int64_t det_stride, uint8_t *d_obs, int64_t obs_stride,
-                             void *stream)
+// qd_sample_dem (d_shots == nullptr: shots shot0 .. shot0 + B - 1) and qd_sample_dem_shots (row b = shot d_shots[b])
+static int sample_dem_impl(const qd_spmat *Ht, const qd_spmat *Lt, const double *priors, uint64_t seed, int64_t shot0, const int64_t *d_shots,
+                           int64_t B, uint8_t *d_det, int64_t det_stride, uint8_t *d_obs, int64_t obs_stride, void *stream)
 {
     if (!Ht || !Lt || !priors || !d_det || !d_obs) return fail(QD_EINVAL, "null argument");
     if (Ht->d.nrows != Lt->d.nrows) return fail(QD_EINVAL, "Ht and Lt must both have one row per fault");
@@ -1765,17 +1769,33 @@ extern "C" int qd_sample_dem(const qd_spmat *Ht, const qd_spmat *Lt, const doubl
     uint32_t *d_thr = nullptr;
     HIP_TRY(hipMalloc((void **)&d_thr, sizeof(uint32_t) * (size_t)std::max(n, 4)));
     hipError_t e = hipMemcpy(d_thr, thr.data(), sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = qd_launch_sample(Ht->d, Lt->d, d_thr, seed, shot0, B, m, nobs, d_det, det_stride, d_obs, obs_stride, s);
+    if (e == hipSuccess) e = qd_launch_sample(Ht->d, Lt->d, d_thr, seed, shot0, d_shots, B, m, nobs, d_det, det_stride, d_obs, obs_stride, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     (void)hipFree(d_thr);
     if (e != hipSuccess) return fail(QD_EHIP, "sampler: %s", hipGetErrorString(e));
     return QD_OK;
 }
 
+extern "C" int qd_sample_dem(const qd_spmat *Ht, const qd_spmat *Lt, const double *priors, uint64_t seed, int64_t shot0,
+                             int64_t B, uint8_t *d_det, int64_t det_stride, uint8_t *d_obs, int64_t obs_stride,
+                             void *stream)
+{
+    return sample_dem_impl(Ht, Lt, priors, seed, shot0, nullptr, B, d_det, det_stride, d_obs, obs_stride, stream);
+}
+
+extern "C" int qd_sample_dem_shots(const qd_spmat *Ht, const qd_spmat *Lt, const double *priors, uint64_t seed, const int64_t *d_shots,
+                                   int64_t B, uint8_t *d_det, int64_t det_stride, uint8_t *d_obs, int64_t obs_stride, void *stream)
+{
+    if (B == 0) return QD_OK;
+    if (B < 0 || B > INT32_MAX) return fail(QD_EINVAL, "bad shot count (one workgroup per shot: at most 2^31 - 1 in one call)");
+    if (!d_shots) return fail(QD_EINVAL, "null shot list");
+    return sample_dem_impl(Ht, Lt, priors, seed, 0, d_shots, B, d_det, det_stride, d_obs, obs_stride, stream);
+}
+
 // ---- circuit-level sampler (frame_sampler.hip): the program comes from quits_amd/frame.py; everything the kernel indexes with is
 // checked here once, so the kernel trusts the program.
-hipError_t qd_launch_frame_sample(const FrameDev &c, uint64_t seed, int64_t shot0, int64_t B, uint8_t *det, int64_t det_stride,
-                                  uint8_t *obs, int64_t obs_stride, hipStream_t s);
+hipError_t qd_launch_frame_sample(const FrameDev &c, uint64_t seed, int64_t shot0, const int64_t *shot_list, int64_t B, uint8_t *det,
+                                  int64_t det_stride, uint8_t *obs, int64_t obs_stride, hipStream_t s);
 
 struct qd_circuit {
     int device = 0;
@@ -1914,6 +1934,44 @@ extern "C" int qd_sample_circuit(const qd_circuit *c, uint64_t seed, int64_t sho
     if ((c->ndet > 0 && !d_det) || (c->nobs > 0 && !d_obs)) return fail(QD_EINVAL, "null output");
     if (det_stride < c->ndet || obs_stride < c->nobs) return fail(QD_EINVAL, "output strides too small");
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(qd_launch_frame_sample(c->d, seed, shot0, B, d_det, det_stride, d_obs, obs_stride, reinterpret_cast<hipStream_t>(stream)));
+    HIP_TRY(qd_launch_frame_sample(c->d, seed, shot0, nullptr, B, d_det, det_stride, d_obs, obs_stride, reinterpret_cast<hipStream_t>(stream)));
+    return QD_OK;
+}
+
+extern "C" int qd_sample_circuit_shots(const qd_circuit *c, uint64_t seed, const int64_t *d_shots, int64_t B, uint8_t *d_det, int64_t det_stride,
+                                       uint8_t *d_obs, int64_t obs_stride, void *stream)
+{
+    if (B == 0) return QD_OK;
+    if (!c) return fail(QD_EINVAL, "null circuit");
+    if (B < 0) return fail(QD_EINVAL, "negative shot count");
+    if (B > (int64_t)QD_WAVE * INT32_MAX) return fail(QD_EINVAL, "too many shots in one call");
+    if (!d_shots) return fail(QD_EINVAL, "null shot list");
+    if ((c->ndet > 0 && !d_det) || (c->nobs > 0 && !d_obs)) return fail(QD_EINVAL, "null output");
+    if (det_stride < c->ndet || obs_stride < c->nobs) return fail(QD_EINVAL, "output strides too small");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(qd_launch_frame_sample(c->d, seed, 0, d_shots, B, d_det, det_stride, d_obs, obs_stride, reinterpret_cast<hipStream_t>(stream)));
+    return QD_OK;
+}
+
+// ---- the memory experiment's bookkeeping (experiment.hip)
+extern "C" int qd_shot_flags_fold(const int32_t *d_status, int64_t B, uint8_t *d_flags, void *stream)
+{
+    if (B == 0) return QD_OK;
+    if (B < 0) return fail(QD_EINVAL, "negative shot count");
+    if (!d_status || !d_flags) return fail(QD_EINVAL, "null status or flags");
+    if (B > 256ll * INT32_MAX) return fail(QD_EINVAL, "too many shots in one call");
+    HIP_TRY(qd_launch_shot_flags(d_status, B, d_flags, reinterpret_cast<hipStream_t>(stream)));
+    return QD_OK;
+}
+
+extern "C" int qd_tally_batch(const uint8_t *d_pred, int64_t pred_stride, const uint8_t *d_obs, int64_t obs_stride, int32_t k, int64_t B,
+                              const uint8_t *d_flags, int64_t *d_counts, uint64_t *d_fail_mask, void *stream)
+{
+    if (B == 0) return QD_OK;
+    if (B < 0) return fail(QD_EINVAL, "negative shot count");
+    if (!d_pred || !d_obs || !d_counts) return fail(QD_EINVAL, "null predictions, observables or counts");
+    if (k <= 0 || k > QD_TALLY_MAX_K) return fail(QD_EINVAL, "k = %d observables outside 1 .. %d", k, QD_TALLY_MAX_K);
+    if (pred_stride < k || obs_stride < k) return fail(QD_EINVAL, "row strides smaller than k");
+    HIP_TRY(qd_launch_tally(d_pred, pred_stride, d_obs, obs_stride, k, B, d_flags, d_counts, d_fail_mask, reinterpret_cast<hipStream_t>(stream)));
     return QD_OK;
 }

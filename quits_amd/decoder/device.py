@@ -230,6 +230,70 @@ def count_mismatch(pred, obs) -> "object":
     return cnt
 
 
+def shot_flags_fold(status, flags):
+    """flags[b] |= the QD_SHOT_* bits of one window's status words (qd_shot_flags_fold): _lib.SHOT_POST if the post-processor produced that
+    window's output, SHOT_INCONSISTENT, SHOT_INEXACT, SHOT_COARSE.  status: cuda int32 [B], flags: cuda uint8 [B], both contiguous."""
+    torch = _torch()
+    L = _lib.require_experiment(_lib.load())
+    assert status.is_cuda and status.dtype == torch.int32 and status.dim() == 1 and status.is_contiguous()
+    assert flags.is_cuda and flags.dtype == torch.uint8 and flags.shape == status.shape and flags.is_contiguous()
+    _lib.check(L.qd_shot_flags_fold(_ptr(status), status.shape[0], _ptr(flags), _stream_ptr()))
+    return flags
+
+
+class Tally:
+    """Counters of a memory experiment, on the device (qd_tally_batch): shots, failing shots, both again per flag bit, mismatches per
+    observable.  `add` accumulates and returns nothing to the host; `counts` does."""
+
+    def __init__(self, k: int, device=None):
+        torch = _torch()
+        self._L = _lib.require_experiment(_lib.require_gpu())
+        self.k = int(k)
+        self.data = torch.zeros((_lib.TALLY_HEAD + self.k,), dtype=torch.int64, device="cuda" if device is None else device)
+
+    def add(self, pred, obs, flags=None, fail_mask=None):
+        """pred, obs: cuda uint8 [B, k] (row strides >= k: column slices are fine); flags: cuda uint8 [B] or None; fail_mask: cuda int64
+        [>= ceil(B / 64)] or None -- written, not accumulated: bit l of word w is the fail bit of shot 64 w + l, zero past B."""
+        torch = _torch()
+        assert pred.is_cuda and obs.is_cuda and pred.dtype == torch.uint8 and obs.dtype == torch.uint8
+        assert pred.dim() == 2 and pred.shape == obs.shape and pred.shape[1] == self.k
+        B = pred.shape[0]
+        if B == 0:
+            return
+        assert pred.stride(1) == 1 and obs.stride(1) == 1
+        fp = mp = C.c_void_p(0)
+        if flags is not None:
+            assert flags.is_cuda and flags.dtype == torch.uint8 and flags.shape == (B,) and flags.is_contiguous()
+            fp = _ptr(flags)
+        if fail_mask is not None:
+            assert fail_mask.is_cuda and fail_mask.dtype == torch.int64 and fail_mask.dim() == 1 and fail_mask.is_contiguous()
+            assert fail_mask.shape[0] >= (B + 63) // 64
+            mp = _ptr(fail_mask)
+        _lib.check(self._L.qd_tally_batch(_ptr(pred), pred.stride(0), _ptr(obs), obs.stride(0), self.k, B, fp, _ptr(self.data), mp, _stream_ptr()))
+
+    def counts(self):
+        """numpy int64 [10 + k] (synchronises): [0] shots, [1] failing shots, [2 + 2j], [3 + 2j] shots / failing shots with flag bit j,
+        [10 + i] shots whose observable i mismatches."""
+        return self.data.cpu().numpy()
+
+
+def _shot_indices(indices):
+    """int64 cuda tensor of shot indices from a tensor or any integer sequence."""
+    torch = _torch()
+    if isinstance(indices, torch.Tensor):
+        if indices.dtype != torch.int64 or indices.dim() != 1:
+            raise ValueError("shot indices must be a one-dimensional int64 tensor")
+        idx = indices.to("cuda").contiguous()
+    else:
+        a = np.asarray(indices)
+        if a.size and a.dtype.kind not in "iu":
+            raise ValueError("shot indices must be integers")
+        idx = torch.from_numpy(np.ascontiguousarray(a.reshape(-1).astype(np.int64))).to("cuda")
+    if idx.numel() and int(idx.min()) < 0:
+        raise ValueError("shot indices must not be negative")
+    return idx
+
+
 class DemSampler:
     """Device-side detector-error-model sampler (stands in for stim's detector sampler, simulation.py:23-27)."""
 
@@ -250,6 +314,19 @@ class DemSampler:
         _lib.check(L.qd_sample_dem(self.Ht._h, self.Lt._h, self.priors.ctypes.data_as(C.c_void_p),
                                    C.c_uint64(int(seed) & (2 ** 64 - 1)), int(shot0), int(shots), _ptr(det),
                                    det.stride(0), _ptr(obs), obs.stride(0), _stream_ptr()))
+        return det, obs
+
+    def sample_shots(self, indices, seed: int):
+        """Row b = shot indices[b] of this seed's stream (qd_sample_dem_shots): what `sample(1, seed, shot0=indices[b])` returns.  `indices`: an
+        int64 cuda tensor or any integer sequence; any order, repeats allowed."""
+        torch = _torch()
+        idx = _shot_indices(indices)
+        n = idx.shape[0]
+        det = torch.empty((n, self.m), dtype=torch.uint8, device="cuda")
+        obs = torch.empty((n, self.nobs), dtype=torch.uint8, device="cuda")
+        L = _lib.require_experiment(self.Ht._L)
+        _lib.check(L.qd_sample_dem_shots(self.Ht._h, self.Lt._h, self.priors.ctypes.data_as(C.c_void_p), C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                         _ptr(idx), n, _ptr(det), det.stride(0), _ptr(obs), obs.stride(0), _stream_ptr()))
         return det, obs
 
 
@@ -293,6 +370,18 @@ class CircuitSampler:
         obs = torch.empty((shots, self.nobs), dtype=torch.uint8, device="cuda")
         _lib.check(self._L.qd_sample_circuit(self._h, C.c_uint64(int(seed) & (2 ** 64 - 1)), int(shot0), int(shots), _ptr(det),
                                              det.stride(0), _ptr(obs), obs.stride(0), _stream_ptr()))
+        return det, obs
+
+    def sample_shots(self, indices, seed: int):
+        """Row b = shot indices[b] of this seed's stream (qd_sample_circuit_shots): what `sample(1, seed, shot0=indices[b])` returns.
+        `indices`: an int64 cuda tensor or any integer sequence; any order, repeats allowed."""
+        torch = _torch()
+        idx = _shot_indices(indices)
+        n = idx.shape[0]
+        det = torch.empty((n, self.m), dtype=torch.uint8, device="cuda")
+        obs = torch.empty((n, self.nobs), dtype=torch.uint8, device="cuda")
+        _lib.check(_lib.require_experiment(self._L).qd_sample_circuit_shots(self._h, C.c_uint64(int(seed) & (2 ** 64 - 1)), _ptr(idx), n, _ptr(det),
+                                                                            det.stride(0), _ptr(obs), obs.stride(0), _stream_ptr()))
         return det, obs
 
     def __del__(self):

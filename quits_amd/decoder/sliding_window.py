@@ -220,13 +220,24 @@ class DeviceWindowPlan:
         shots go through two pinned staging buffers and a copy stream, so that the host-side copy and the PCIe transfer of one
         piece run beside the decoding of the previous one, and the predictions come back through a pinned buffer.  Tensors that
         already live on the GPU skip the staging."""
+        with self.in_use():
+            return self._decode_host_locked(zcheck_samples)
+
+    def in_use(self):
+        """Context manager around a run of `decode` calls that owns the plan: checks the current device, takes the plan's lock and marks
+        the workspaces live, so that the plan cache does not release them under the run (decode_host, simulation.get_circuit_mem_pL)."""
+        import contextlib
         import torch
         if self.device >= 0 and torch.cuda.current_device() != self.device:
             raise RuntimeError("this plan was built on cuda:%d but the current device is cuda:%d (plans are per device; the plan "
                                "cache keys on the current device)" % (self.device, torch.cuda.current_device()))
-        with self._lock:
-            self._ws_live = True                 # (a concurrent cache lookup may have released them since this plan was handed out)
-            return self._decode_host_locked(zcheck_samples)
+
+        @contextlib.contextmanager
+        def held():
+            with self._lock:
+                self._ws_live = True             # (a concurrent cache lookup may have released them since this plan was handed out)
+                yield self
+        return held()
 
     def _decode_host_locked(self, zcheck_samples):
         import torch

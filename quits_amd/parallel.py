@@ -55,6 +55,18 @@ def reduce_counts(dist, n_errors: int, n_shots: int, device="cpu") -> Tuple[int,
     return int(t[0].item()), int(t[1].item())
 
 
+def reduce_vector(dist, values, device="cpu"):
+    """All-reduce SUM of a vector of int64 counters in one collective (numpy in, numpy out); identity without a process group."""
+    import numpy as np
+    values = np.asarray(values, dtype=np.int64)
+    if dist is None:
+        return values
+    import torch
+    t = torch.from_numpy(values.copy()).to(_collective_device(dist, device))
+    dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    return t.cpu().numpy()
+
+
 def reduce_max(dist, value: float, device="cpu") -> float:
     if dist is None:
         return float(value)

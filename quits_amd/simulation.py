@@ -3,6 +3,10 @@
   get_codecap_pL       <- simulation.py:31-61   code-capacity logical error rate of a decoder plug-in
   get_stim_mem_result  <- simulation.py:8-28    detector / observable samples of a memory circuit
   get_circuit_mem_result                        the same samples from the circuit itself on the device (Pauli-frame simulation)
+  get_circuit_mem_pL                            a whole memory experiment on the device: sampler -> sliding-window BP-OSD -> tallies; what
+                                                the reference's users write around the two calls above (tests/test_sliding_window.py:72-83),
+                                                without a host array per shot
+  replay_shots                                  the samples of given shot indices again (both samplers are counter-based)
 
 `get_codecap_pL` keeps the reference's signature and its random stream (`np.random.seed(seed)` followed by one
 `np.random.binomial(1, p, n)` per trial), so a given seed produces the same noise vectors as the reference.  With a plug-in
@@ -10,6 +14,9 @@ that decodes batches (`quits_amd.decoder.BpOsdDecoder`: it has `decode_batch`) a
 one call; any other plug-in class runs the reference's per-trial loop on the host.
 """
 from __future__ import annotations
+
+import dataclasses
+import math
 
 import numpy as np
 
@@ -87,3 +94,224 @@ def get_codecap_pL(code, p, num_trials, decoder, dict, basis='Z', seed=-1, tqdm_
         if (Lm @ residual_error % 2).any():
             num_errors += 1
     return num_errors / num_trials
+
+
+# ---- a memory experiment on the device ------------------------------------------------------------------------------------------
+def _batch_step(batch):
+    """`batch` rounded up to a multiple of 64, a word of the fail mask."""
+    return (int(batch) + 63) // 64 * 64
+
+
+def experiment_batches(num_trials, batch, rank=0, world=1):
+    """[(shot0, n), ...]: the batches `get_circuit_mem_pL` issues, in order, for `rank` of `world`: the rank's contiguous slice of
+    [0, num_trials) (parallel.shard_range) cut into pieces of `batch` shots, `batch` rounded up to a multiple of 64 (a word of the
+    fail mask), the last piece taking what is left.  Shot indices are global."""
+    from .parallel import shard_range
+    if num_trials < 0 or batch < 1:
+        raise ValueError("num_trials must be >= 0 and batch >= 1")
+    lo, hi = shard_range(int(num_trials), int(rank), int(world))
+    step = _batch_step(batch)
+    return [(s, min(step, hi - s)) for s in range(lo, hi, step)]
+
+
+def shots_before_stop(batches, failing_shots, max_errors):
+    """The early-stop rule of `get_circuit_mem_pL`, as arithmetic: how many of `batches` (experiment_batches) are issued when the sorted
+    global indices of the failing shots are `failing_shots`.  Batch i >= 2 is issued only if fewer than `max_errors` of the shots of batches
+    0 .. i - 2 failed: the driver reads the count two batches behind, so that the read never waits for the batch in flight.  Returns the
+    number of batches issued."""
+    f = np.sort(np.asarray(failing_shots, dtype=np.int64))
+    for i in range(2, len(batches)):
+        end = batches[i - 2][0] + batches[i - 2][1]
+        first = batches[0][0]
+        if int(np.searchsorted(f, end, side="left") - np.searchsorted(f, first, side="left")) >= max_errors:
+            return i
+    return len(batches)
+
+
+@dataclasses.dataclass
+class MemExperimentResult:
+    """What `get_circuit_mem_pL` returns.  shots, errors: decoded shots and those with a wrong prediction on any observable; pL = errors /
+    shots with its binomial standard deviation sigma; per_observable_errors[i]: shots whose observable i was mispredicted; flagged[name] =
+    (shots, errors) among the shots some window of which was post-processed ('post'), had a syndrome outside the window matrix's column
+    space ('inconsistent'), may have seen float rounding ('inexact'), was decoded again on the coarse LLR grid ('coarse');
+    failing_shots: ascending global indices of the first `keep_failures` failing shots (of this rank), failures_truncated if there were more."""
+    shots: int
+    errors: int
+    pL: float
+    sigma: float
+    per_observable_errors: np.ndarray
+    flagged: dict
+    failing_shots: np.ndarray
+    failures_truncated: bool
+    seed: int
+    sampler: str
+    batch: int
+    seconds: float
+    shots_per_s: float
+
+    @classmethod
+    def from_counts(cls, counts, failing_shots=(), failures_truncated=False, seed=0, sampler="circuit", batch=0, seconds=0.0):
+        """From the counter vector of decoder.device.Tally ([0] shots, [1] errors, [2 + 2j], [3 + 2j] per flag, [10 + i] per observable)."""
+        from ._lib import SHOT_FLAG_NAMES, TALLY_HEAD
+        c = np.asarray(counts, dtype=np.int64)
+        shots, errors = int(c[0]), int(c[1])
+        pL = errors / shots if shots else float("nan")
+        sigma = math.sqrt(pL * (1.0 - pL) / shots) if shots else float("nan")
+        flagged = {name: (int(c[2 + 2 * j]), int(c[3 + 2 * j])) for j, name in enumerate(SHOT_FLAG_NAMES)}
+        return cls(shots, errors, pL, sigma, c[TALLY_HEAD:].copy(), flagged, np.asarray(failing_shots, dtype=np.int64), bool(failures_truncated),
+                   int(seed), str(sampler), int(batch), float(seconds), shots / seconds if seconds > 0 else 0.0)
+
+
+def _as_circuit(circuit):
+    from .dem import Circuit
+    return circuit if isinstance(circuit, Circuit) else Circuit(str(circuit))
+
+
+def _make_sampler(circ, sampler):
+    from .decoder.device import CircuitSampler, DemSampler
+    if sampler == "circuit":
+        return CircuitSampler(circ)
+    if sampler == "dem":
+        from .decoder.base import detector_error_model_to_matrix
+        H, L, priors = detector_error_model_to_matrix(circ.detector_error_model())
+        return DemSampler(H, L, priors)
+    raise ValueError("sampler must be 'circuit' or 'dem'")
+
+
+def _mask_to_indices(words, shot0, limit):
+    """Ascending global indices of the set bits of a fail mask (uint64 words, bit l of word w = shot shot0 + 64 w + l): at most `limit`, and
+    whether there were more.  Only the non-zero words are unpacked."""
+    nz = np.flatnonzero(words)
+    bits = np.unpackbits(words[nz].astype("<u8").view(np.uint8).reshape(-1, 8), axis=1, bitorder="little").astype(bool)
+    idx = (np.int64(shot0) + nz.astype(np.int64)[:, None] * 64 + np.arange(64, dtype=np.int64)[None, :])[bits]
+    return idx[:limit], idx.shape[0] > limit
+
+
+def get_circuit_mem_pL(circuit, hz, lz, W, F, num_trials, max_iter=2, osd_order=0, bp_method='product_sum', schedule='serial',
+                       osd_method='osd_cs', *, seed=0, sampler='circuit', batch=None, max_errors=None, keep_failures=4096,
+                       shard=None, distributed=False):
+    """A logical-memory experiment of `num_trials` shots, entirely on the device: every batch is sampled (shots shot0 .. shot0 + n - 1 of the
+    stream of `seed`), decoded by the sliding-window BP-OSD decoder and tallied there; the host receives the counters and the failing
+    shots' indices at the end.  The decoder keywords are `sliding_window_bposd_circuit_mem`'s (same names, order, defaults; same cached
+    plan), the number of rounds follows from the circuit's detector count as it does there from the sample width.
+
+    sampler: 'circuit' (decoder.device.CircuitSampler: the circuit itself, what `get_circuit_mem_result` draws) or 'dem'
+        (DemSampler on the circuit's detector error model, what `get_stim_mem_result` draws for circuit text).  A 'dem' batch is not
+        asynchronous: every qd_sample_dem call uploads its threshold table (an allocation, a blocking copy, a stream synchronisation),
+        so the host waits for each batch's sampling and the batches do not overlap; 'circuit' queues everything.
+    batch: shots per batch, rounded up to a multiple of 64; default: as many of the plan's chunks as the two-stream driver has lanes
+        (at least two, so that it runs).  The result does not depend on it, except through `max_errors`.
+    max_errors: stop early.  Batches are issued in order; before batch i >= 2 is issued, the number of failing shots of batches
+        0 .. i - 2 is read (it is two batches old, so the read does not wait for the batch in flight), and if it is >= max_errors no
+        further batch is issued.  Every issued batch is counted, so `shots` and `errors` are a function of (num_trials, batch,
+        max_errors, shard) and the seed alone -- not of timing.  `shots_before_stop` states the rule as arithmetic.
+    keep_failures: how many failing shots' global indices to return (the smallest); 0 keeps no fail mask at all.
+    shard: (rank, world): run this rank's contiguous slice of the shots (parallel.shard_range); indices stay global.
+    distributed: take (rank, world) from RANK / WORLD_SIZE (parallel.init_distributed) and sum the counters over the ranks in one
+        all-reduce; failing_shots stay this rank's.  With max_errors each rank stops on ceil(max_errors / world) of its own.
+
+    Returns a MemExperimentResult.  `replay_shots(circuit, result.failing_shots, seed, sampler)` regenerates the failing shots."""
+    import time
+    import warnings
+    from . import _lib
+    from .decoder.base import window_count
+    from .decoder.bposd import BpOsdDecoder
+    from .decoder.sliding_window import build_circuit_plan, cached_plan, plan_key
+    if F == 0:
+        raise ValueError("Input parameter F cannot be zero.")
+    if sampler not in ("circuit", "dem"):
+        raise ValueError("sampler must be 'circuit' or 'dem'")
+    _lib.require_experiment(_lib.require_gpu())           # no GPU or no library: RuntimeError, there is no CPU fallback
+    import torch
+    from .decoder.device import Tally, shot_flags_fold
+    from .parallel import env_rank_world, init_distributed, reduce_vector
+    dist = None
+    rank, world = (0, 1) if shard is None else (int(shard[0]), int(shard[1]))
+    if distributed:
+        env_rank, env_world, local = env_rank_world()
+        if env_world > 1:
+            torch.cuda.set_device(local % torch.cuda.device_count())    # one process per GPU; the plan, the samplers and RCCL follow the current device
+        dist = init_distributed()
+        if shard is None:
+            rank, world = env_rank, env_world
+    circ = _as_circuit(circuit)
+    smp = _make_sampler(circ, sampler)
+    nz = hz.shape[0]
+    num_rounds = smp.m // nz - 2
+    if window_count(num_rounds, W, F)[2]:
+        warnings.warn("Window size larger than the syndrome extraction rounds: Doing whole history correction")
+    opts = {'bp_method': bp_method, 'max_iter': max_iter, 'schedule': schedule, 'osd_method': osd_method, 'osd_order': osd_order}
+    plan = cached_plan(plan_key("circuit", circ, hz, None, W, F, num_rounds, BpOsdDecoder, BpOsdDecoder, opts, opts),
+                       lambda: build_circuit_plan(circ, hz, W, F, num_rounds, dict(opts), dict(opts), BpOsdDecoder, BpOsdDecoder))
+    k = plan.nobs
+    if smp.nobs != k or np.asarray(lz.shape)[0] != k:
+        raise ValueError("the circuit has %d observables, lz %d rows, the window plan commits %d" % (smp.nobs, lz.shape[0], k))
+    if batch is None:
+        batch = max(2, int(plan.lanes) if plan.pipeline else 2) * int(plan.chunk)
+    batches = experiment_batches(num_trials, batch, rank, world)
+    step = _batch_step(batch)
+    limit = None if max_errors is None else -(-int(max_errors) // world)
+    first = batches[0][0] if batches else 0
+    nwin = len(plan.windows)
+    with plan.in_use():
+        tally = Tally(k)
+        mask = torch.zeros((sum((n + 63) // 64 for _, n in batches),), dtype=torch.int64, device="cuda") if keep_failures else None
+        seen = torch.zeros((3,), dtype=torch.int64).pin_memory()       # failing shots so far, as of the last three batches
+        done = []
+        issued = 0
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i, (shot0, n) in enumerate(batches):
+            if i >= 2:
+                # at most two batches are in flight; the count behind this event is two batches old and has long arrived
+                done[i - 2].synchronize()
+                if limit is not None and int(seen[(i - 2) % 3]) >= limit:
+                    break
+            det, obs = smp.sample(n, seed, shot0)
+            stats = []
+            pred = plan.decode(det, stats)
+            # `stats` holds (window, status words) pairs.  Both drivers append a window's pairs in shot order: the single-stream one chunk by
+            # chunk, each pair a tensor of its own; the two-stream one as views st_all[k, c0:c0 + B] of one tensor, c0 ascending within a
+            # window.  So the pairs of window k, laid end to end, are the batch's shots 0 .. n - 1.  Checked: the lengths add up to n, and a
+            # pair that is a view into the storage of its window's first pair starts where the pairs before it end.
+            flags = torch.zeros((n,), dtype=torch.uint8, device="cuda")
+            at = [0] * nwin
+            origin = [None] * nwin
+            for kw, st in stats:
+                where = (st.untyped_storage().data_ptr(), st.storage_offset())
+                if origin[kw] is None:
+                    origin[kw] = where
+                elif where[0] == origin[kw][0] and where[1] != origin[kw][1] + at[kw]:
+                    raise RuntimeError("the decoder's status words of window %d are not in shot order (offset %d after %d shots)"
+                                       % (kw, where[1] - origin[kw][1], at[kw]))
+                shot_flags_fold(st, flags[at[kw]:at[kw] + st.shape[0]])
+                at[kw] += st.shape[0]
+            if any(a != n for a in at):
+                raise RuntimeError("the decoder reported status words for %s shots per window, the batch has %d" % (at, n))
+            w0 = (shot0 - first) // 64
+            tally.add(pred, obs, flags, None if mask is None else mask[w0:w0 + (n + 63) // 64])
+            seen[i % 3:i % 3 + 1].copy_(tally.data[1:2], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            done.append(ev)
+            issued += 1
+        torch.cuda.synchronize()
+        seconds = time.perf_counter() - t0
+        counts = tally.counts()
+        failing, truncated = np.zeros((0,), np.int64), False
+        if mask is not None and issued:
+            nwords = (batches[issued - 1][0] + batches[issued - 1][1] - first + 63) // 64
+            failing, truncated = _mask_to_indices(mask[:nwords].cpu().numpy().view(np.uint64), first, int(keep_failures))
+    if dist is not None:
+        counts = reduce_vector(dist, counts, device="cuda")
+    return MemExperimentResult.from_counts(counts, failing, truncated, seed, sampler, step, seconds)
+
+
+def replay_shots(circuit, shot_indices, seed, sampler='circuit'):
+    """The samples of the given shots of `seed`'s stream again: numpy bool (det [n, ndet], obs [n, nobs]) like `get_circuit_mem_result`,
+    row i being shot shot_indices[i] -- e.g. `result.failing_shots` of `get_circuit_mem_pL`, to decode them with other settings.  Both
+    samplers draw shot s from (seed, s, site) alone, so nothing but the index is needed."""
+    from . import _lib
+    _lib.require_experiment(_lib.require_gpu())
+    det, obs = _make_sampler(_as_circuit(circuit), sampler).sample_shots(shot_indices, int(seed))
+    return det.cpu().numpy().astype(bool), obs.cpu().numpy().astype(bool)

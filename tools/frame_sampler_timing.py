@@ -2,7 +2,7 @@
 """Time the circuit-level frame sampler against the DEM sampler and the headline decode on the same shots.
 
     python tools/frame_sampler_timing.py [--shots 1048576] [--reps 5] [--out profiles/frame_sampler_timing.json]
-    python tools/frame_sampler_timing.py --channels [--parent-lib OLD/libquits_amd.so] [--out profiles/frame_sampler_channels_timing.json]
+    python tools/frame_sampler_timing.py --channels [--parent-lib OLD/libquits_amd.so [--rounds 4]] [--out profiles/frame_sampler_channels_timing.json]
 
 Circuit bb144_custom_r12_p0.003.  After one warm-up of each, device events time `reps` calls of CircuitSampler.sample and
 DemSampler.sample (2^20 shots each) and one headline decode (minimum_sum, parallel, max_iter=50, OSD-0, the whole history as one
@@ -11,8 +11,9 @@ window) of the circuit-sampled shots; the median call is reported.  Prints one J
 --channels times the biased-noise path instead: the same circuit with every DEPOLARIZE1(p) rewritten as PAULI_CHANNEL_1(p/3, p/3, p/3)
 and every DEPOLARIZE2(p) as the uniform 15-entry PAULI_CHANNEL_2 -- the same distribution through the threshold tables -- next to the
 unchanged text, `shots` shots each, median and min - max of `reps` calls after a warm-up.  With --parent-lib the unchanged text is timed
-with that library too (an older build of libquits_amd.so, which need not know the channel opcodes).  Every measurement runs in a child
-process of its own (QUITS_AMD_LIB names the library), one after the other; this process does not touch the GPU."""
+with that library too (an older build of libquits_amd.so, which need not know the channel opcodes): --rounds rounds, in each the parent
+library and then this one, `reps` calls each, a library's calls pooled over the rounds.  Every measurement runs in a child process of its
+own (QUITS_AMD_LIB names the library), one after the other; this process does not touch the GPU."""
 import argparse
 import json
 import os
@@ -81,14 +82,27 @@ def channels(a):
     row = dict(circuit="bb144_custom_r12_p0.003", shots=a.shots, reps=a.reps,
                rewrite="DEPOLARIZE1(p) -> PAULI_CHANNEL_1(p/3 x 3), DEPOLARIZE2(p) -> PAULI_CHANNEL_2(p/15 x 15)")
     if a.parent_lib:
-        row["parent_library"] = child(a.parent_lib)
-    row["this_library"] = child(None)
+        # A B A B ...: one child per library and round, the two libraries alternating, so that drift over the session falls on both alike;
+        # a library's calls of all rounds are pooled
+        runs = {"parent_library": [], "this_library": []}
+        for _ in range(max(1, a.rounds)):
+            runs["parent_library"].append(child(a.parent_lib))
+            runs["this_library"].append(child(None))
+        for side, lst in runs.items():
+            row[side] = dict(lst[0])
+            for key in ("depolarize", "pauli_channel"):
+                if key in lst[0]:
+                    row[side][key] = dict(_stats([x for r in lst for x in r[key]["all_ms"]]), info=lst[0][key]["info"],
+                                          round_medians_ms=[r[key]["median_ms"] for r in lst])
+        row["order"] = "alternating, parent library first, %d rounds of %d calls per library" % (max(1, a.rounds), a.reps)
+    else:
+        row["this_library"] = child(None)
     new = row["this_library"]
     row["pauli_channel_over_depolarize"] = round(new["pauli_channel"]["median_ms"] / new["depolarize"]["median_ms"], 4)
     if a.parent_lib:
         old = row["parent_library"]["depolarize"]
         row["depolarize_over_parent"] = round(new["depolarize"]["median_ms"] / old["median_ms"], 4)
-        row["depolarize_within_parent_range"] = bool(new["depolarize"]["median_ms"] <= old["max_ms"])
+        row["depolarize_within_parent_range"] = bool(old["min_ms"] <= new["depolarize"]["median_ms"] <= old["max_ms"])
     line = json.dumps(row)
     print(line, flush=True)
     if a.out:
@@ -104,6 +118,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--channels", action="store_true", help="time the PAULI_CHANNEL_1/2 rewrite next to the unchanged circuit")
     ap.add_argument("--parent-lib", default=None, help="with --channels: an older libquits_amd.so to time the unchanged circuit with")
+    ap.add_argument("--rounds", type=int, default=4, help="with --parent-lib: rounds of (parent library, this library), alternating")
     ap.add_argument("--sampler-only", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.sampler_only:
