@@ -33,6 +33,7 @@
 // The serial product-sum schedule keeps tanh(b2c/2) of every edge INSTEAD of the message (bp.hpp re-evaluates it once per
 // use, row weight times per sweep; a pure function of an unchanged argument, so the cached value is the same number).
 #include "qd_internal.h"
+#include "qd_host.h"
 #include "qd_math.h"
 #include "../../include/quits_amd.h"
 

@@ -16,6 +16,7 @@
 //     one check pass + one bit pass + two barriers.
 //   * No atomics on floats, fixed summation order (ascending detector index) -> bit-reproducible.
 #include "qd_internal.h"
+#include "qd_host.h"
 #include "../../include/quits_amd.h"
 #include <float.h>
 
@@ -51,7 +52,7 @@ __device__ __forceinline__ float qd_min_abs(float a, float b)
 //   sb   = bit of `sgnw` that holds the sign of the previous check->bit message on this edge
 // Branch-free: the second minimum is the median of (min1, min2, |b|); the new sign bits are shifted in from bit 0.
 // (b <= 0) is taken as the sign bit of (bits(b) - 1): exact for every float except -0.0, which cannot occur here: a prior that
-// rounds to zero is uploaded as +0 (qd_api.hip, on_grid), sums and differences of values that are not -0 only yield -0 from
+// rounds to zero is uploaded as +0 (qd_decoder.hip, on_grid), sums and differences of values that are not -0 only yield -0 from
 // (-0) - (+0), and a message's sign is ORed onto a magnitude only where it is read, never stored as a float.
 #define QD_CHECK_EDGE(off, sb) QD_CHECK_EDGE_L(off, sb, (*(const __attribute__((address_space(3))) float *)(uintptr_t)(uint32_t)(off)))
 #define QD_CHECK_EDGE_L(off, sb, Lval)                                                                       \

@@ -28,6 +28,7 @@
 // by qd_bp_minsum_kernel (recheck pass), which then decides about the coarse grid as before.  A certified shot is exact in both
 // kernels, hence identical.
 #include "qd_internal.h"
+#include "qd_host.h"
 #include "../../include/quits_amd.h"
 #include <float.h>
 

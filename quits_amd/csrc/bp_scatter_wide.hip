@@ -22,6 +22,7 @@
 // One iteration = [gather pass of check 0 .. CPL-1] barrier [converged? | scatter pass of check 0 .. CPL-1] barrier, in place as in
 // bp_scatter.hip (every gather of the iteration precedes every add).
 #include "qd_internal.h"
+#include "qd_host.h"
 #include "../../include/quits_amd.h"
 #include "bp_scatter_edge.h"
 

@@ -4,6 +4,7 @@
 // and for what a user would compute from the status words with torch; nothing of a batch but these counters has to leave the device.
 #include "../../include/quits_amd.h"
 #include "qd_internal.h"
+#include "qd_host.h"
 
 #define QD_TALLY_THREADS 256
 #define QD_TALLY_MAX_BLOCKS 1024        // the grid is bounded: every workgroup strides over the shots and flushes its sums once

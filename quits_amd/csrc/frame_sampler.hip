@@ -14,6 +14,7 @@
 //   OBSERVABLE_INCLUDE   : XOR into the observable's LDS word; written out as bytes at the end.
 // One wavefront per workgroup, so __syncthreads() between steps only orders the LDS traffic of the wave.
 #include "qd_internal.h"
+#include "qd_host.h"
 
 // The noise sites of one instruction.  thr: the threshold below which a site fires (for a Pauli channel its last cumulative
 // threshold T_K).  tab: T_1 .. T_K of a Pauli channel (K = 3 / 15), unused otherwise; the address is the same in every lane and the

@@ -1,5 +1,6 @@
 // gf2_kernels.hip -- the byte/bit plumbing around the decoder: window hand-off, unpacking, counting, sampling.
 #include "qd_internal.h"
+#include "qd_host.h"
 
 // out[b][r] (^)= parity(row r of A AND e_b).  Replaces `window_observable_set[k] @ e % 2` and
 // `window_update[k] @ e % 2` (quits/decoder/sliding_window.py:172,174,183).  CPU restatement: the L/U loops of

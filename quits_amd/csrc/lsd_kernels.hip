@@ -24,6 +24,7 @@
 // accesses): keeping two of them in LDS (39 KB per shot, four shots per CU) measured 38.4 ms per 65536 headline shots, none
 // 32.6 ms -- a growth step is a chain of dependent instructions, and what hides it is more shots per SIMD.
 #include "qd_internal.h"
+#include "qd_host.h"
 #include "../../include/quits_amd.h"
 
 #define QL_NONE 0xFFFFu

@@ -25,6 +25,7 @@
 //   * One kernel body, every loop that touches the Q columns unrolled over compile-time bounds: ScratchSize 0 in every instantiation
 //     (tests/test_api.py compiles this file and asserts it).
 #include "osd_shared.h"
+#include "qd_host.h"
 
 #include <cstdlib>
 

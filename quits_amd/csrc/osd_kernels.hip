@@ -30,6 +30,7 @@
 // (The full kernel's elimination, qd_osd_eliminate, lives in osd_shared.h: qd_osd0_offchip_kernel, osd_offchip.hip, runs it tier by tier
 //  on the windows neither kernel here takes.)
 #include "osd_shared.h"
+#include "qd_host.h"
 #include <cstdlib>
 #include <algorithm>
 

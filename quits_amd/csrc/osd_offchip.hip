@@ -1,4 +1,4 @@
-// osd_offchip.hip -- OSD-0 for off-chip windows: windows whose BP state does not fit the CU (build_bp, qd_api.hip) and whose
+// osd_offchip.hip -- OSD-0 for off-chip windows: windows whose BP state does not fit the CU (build_bp, graph_layout.hip) and whose
 // column order fits neither OSD kernel of osd_kernels.hip -- qd_osd0_reg_kernel stops at four rows per thread (2048 detectors),
 // qd_osd0_full_kernel sorts every column in LDS (about 16 384 faults).  QLP [[1020,136]] at W = 5 / F = 3: 2250 x 31 500.
 //
@@ -13,6 +13,7 @@
 // Every loop is bounded: a tier that is not the last consumes at least one column (at most n tiers), the elimination takes at most
 // rank pivots.  Workspaces (Q spill planes) are private to the workgroup.
 #include "osd_shared.h"
+#include "qd_host.h"
 #include "../../include/quits_amd.h"
 #include <algorithm>
 

@@ -37,6 +37,7 @@
 // 66.4 ms, 128 registers 4.40 / 72 ms (profiles/r04_osd_sr_register_budget_ab.txt); tests/test_api.py holds every instantiation
 // to ScratchSize 0.
 #include "osd_shared.h"
+#include "qd_host.h"
 #include <algorithm>
 
 #define QD_SR_KWR 4              // Q planes (64 pivots each) the kernel keeps in registers (8 planes at three wavefronts per SIMD: profiles/r06_k2s_planes_ab.txt)

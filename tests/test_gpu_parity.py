@@ -1176,7 +1176,7 @@ def test_scatter_kernel_and_gather_kernel_agree(gpu, monkeypatch, name, shots, m
 @pytest.mark.parametrize("fixture,window", [("bb144_custom_r12_p0.003", None), ("bb144_custom_r12_p0.003", (3, 1, 1)), ("bb72_custom_r6_p0.003", None)])
 def test_scatter_accumulator_banks_and_walk_do_not_change_results(gpu, monkeypatch, fixture, window):
     """The scatter kernels keep their accumulators in a slot order of their own: a bank per fault balanced over the groups of 32 checks
-    (scatter_banks) and a walk per check found by matching (scatter_walk; qd_api.hip).  Neither may change a bit: the same shots through
+    (scatter_banks) and a walk per check found by matching (scatter_walk; graph_layout.hip).  Neither may change a bit: the same shots through
     the round-3 layout (QD_SCATTER_BANKS_BY_SLOT=1: degree-sorted bit slots), through the greedy walk (QD_SCATTER_WALK_GREEDY=1) and through the
     default give identical decisions, status words and posteriors-driven OSD-0 outputs; and the default's modelled LDS cycles per pass are within
     15 % of the conflict-free count."""
