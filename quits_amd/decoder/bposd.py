@@ -60,7 +60,7 @@ class BpOsdDecoder:
         """syndromes: [B, m] numpy/torch (any integer/bool dtype)  ->  numpy uint8 [B, n]."""
         import torch
         from .device import unpack_bits
-        from .sliding_window import _to_device_samples
+        from .pipeline import _to_device_samples
         if not isinstance(syndromes, torch.Tensor):
             syndromes = np.asarray(syndromes)
             if syndromes.ndim != 2 or syndromes.shape[1] != self.m:

@@ -216,7 +216,7 @@ def get_circuit_mem_pL(circuit, hz, lz, W, F, num_trials, max_iter=2, osd_order=
     from . import _lib
     from .decoder.base import window_count
     from .decoder.bposd import BpOsdDecoder
-    from .decoder.sliding_window import build_circuit_plan, cached_plan, plan_key
+    from .decoder.plan import cached_circuit_plan
     if F == 0:
         raise ValueError("Input parameter F cannot be zero.")
     if sampler not in ("circuit", "dem"):
@@ -241,8 +241,7 @@ def get_circuit_mem_pL(circuit, hz, lz, W, F, num_trials, max_iter=2, osd_order=
     if window_count(num_rounds, W, F)[2]:
         warnings.warn("Window size larger than the syndrome extraction rounds: Doing whole history correction")
     opts = {'bp_method': bp_method, 'max_iter': max_iter, 'schedule': schedule, 'osd_method': osd_method, 'osd_order': osd_order}
-    plan = cached_plan(plan_key("circuit", circ, hz, None, W, F, num_rounds, BpOsdDecoder, BpOsdDecoder, opts, opts),
-                       lambda: build_circuit_plan(circ, hz, W, F, num_rounds, dict(opts), dict(opts), BpOsdDecoder, BpOsdDecoder))
+    plan = cached_circuit_plan(circ, hz, W, F, num_rounds, BpOsdDecoder, BpOsdDecoder, opts, opts)
     k = plan.nobs
     if smp.nobs != k or np.asarray(lz.shape)[0] != k:
         raise ValueError("the circuit has %d observables, lz %d rows, the window plan commits %d" % (smp.nobs, lz.shape[0], k))

@@ -103,7 +103,7 @@ def test_bplsd_options_outside_the_device_path_fail_loudly():
 def test_device_options_follow_the_decoder_class():
     """the post-processor is chosen by the plug-in CLASS, not by which keys the dict happens to hold."""
     from quits_amd.decoder import BpLsdDecoder, BpOsdDecoder
-    from quits_amd.decoder.sliding_window import _kwargs_for_device
+    from quits_amd.decoder.plan import _kwargs_for_device
     base = {"bp_method": "product_sum", "max_iter": 3, "schedule": "serial", "channel_probs": None}
     kw = _kwargs_for_device(base, BpLsdDecoder)                      # no lsd_* keys: still LSD (ldpc's defaults lsd_0 / order 0)
     assert kw["osd_method"] == "lsd_0" and kw["osd_order"] == 0
@@ -295,12 +295,13 @@ def test_plan_cache_is_process_wide_locked_and_keyed_on_the_device(monkeypatch):
     last, and leaves alone a plan another thread holds."""
     import threading
     from quits_amd.decoder import BpOsdDecoder
+    from quits_amd.decoder import plan_cache
     from quits_amd.decoder import sliding_window as sw
     hz = np.eye(3, dtype=int)
     d = {"bp_method": "minimum_sum", "max_iter": 5}
     k0 = sw.plan_key("circuit", "H 0\nM 0\n", hz, None, 3, 1, 6, BpOsdDecoder, BpOsdDecoder, d, d)
-    assert ("device", sw._current_device()) in k0
-    monkeypatch.setattr(sw, "_current_device", lambda: 5)
+    assert ("device", plan_cache._current_device()) in k0
+    monkeypatch.setattr(plan_cache, "_current_device", lambda: 5)
     k5 = sw.plan_key("circuit", "H 0\nM 0\n", hz, None, 3, 1, 6, BpOsdDecoder, BpOsdDecoder, d, d)
     assert k5 != k0 and ("device", 5) in k5
 
@@ -357,10 +358,69 @@ def test_plan_cache_is_process_wide_locked_and_keyed_on_the_device(monkeypatch):
 
 
 def test_env_switches_parse_loosely(monkeypatch):
-    """QD_NO_PIPELINE=true / yes still switch the pipelined driver off; a malformed QD_HOST_PIECE_SHOTS falls back."""
-    from quits_amd.decoder import sliding_window as sw
+    """QD_NO_PIPELINE=true / yes still switch the pipelined driver off."""
+    from quits_amd.decoder.plan import driver_env
     for v, want in (("1", True), ("true", True), ("yes", True), ("0", False), ("", False), ("off", False)):
         monkeypatch.setenv("QD_NO_PIPELINE", v)
-        assert sw._env_flag("QD_NO_PIPELINE") is want, v
-    monkeypatch.setenv("QD_HOST_PIECE_SHOTS", "a lot")
-    assert sw._env_int("QD_HOST_PIECE_SHOTS", 123) == 123
+        assert driver_env().no_pipeline is want, v
+
+
+def test_the_driver_reads_the_environment_in_two_functions():
+    """A plan is steered by the environment it was built under: under quits_amd/decoder only plan.driver_env (called once, by
+    DeviceWindowPlan.__init__) and the plan cache's capacity function (per lookup) mention os.environ / os.getenv."""
+    import ast
+    import glob
+    readers, calls = [], []
+    for path in sorted(glob.glob(os.path.join(ROOT, "quits_amd", "decoder", "*.py"))):
+        mod = os.path.basename(path)
+        tree = ast.parse(open(path).read())
+
+        def visit(node, scope):
+            if isinstance(node, (ast.FunctionDef, ast.AsyncFunctionDef, ast.ClassDef)):
+                scope = scope + [node.name]
+            if isinstance(node, ast.Attribute) and isinstance(node.value, ast.Name) and node.value.id == "os" and node.attr in ("environ", "getenv"):
+                readers.append((mod, ".".join(scope)))
+            if isinstance(node, ast.Name) and node.id in ("environ", "getenv"):          # (from os import environ)
+                readers.append((mod, ".".join(scope)))
+            if isinstance(node, ast.Call) and isinstance(node.func, ast.Name) and node.func.id == "driver_env":
+                calls.append((mod, ".".join(scope)))
+            for child in ast.iter_child_nodes(node):
+                visit(child, scope)
+        visit(tree, [])
+    assert set(readers) == {("plan.py", "driver_env"), ("plan_cache.py", "_plan_cache_size")}, readers
+    assert calls == [("plan.py", "DeviceWindowPlan.__init__")], calls
+
+
+def test_retired_driver_switches_are_gone():
+    """The five A/B switches of the Python driver whose measurements were in long ago (docs/HISTORY.md lists them with their profile
+    files) occur in no Python file of the package, the tools or the tests, nor in INTEGRATION.md."""
+    retired = ["QD_" + tail for tail in ("NO_HOST_" "CHAIN", "POST_STREAM_" "PRIORITY", "PIPELINE_" "EDGE", "PIPELINE_" "LANES", "HOST_PIECE_" "SHOTS")]
+    files = [os.path.join(ROOT, "INTEGRATION.md")]
+    for top in ("quits_amd", "tools", "tests"):
+        for dp, _, names in os.walk(os.path.join(ROOT, top)):
+            files += [os.path.join(dp, f) for f in names if f.endswith(".py")]
+    assert len(files) > 40
+    found = [(os.path.relpath(f, ROOT), name) for f in files for name in retired if name in open(f, errors="replace").read()]
+    assert not found, found
+
+
+class _RecordsLimit:
+    def __init__(self):
+        self.limits = []
+
+    def set_workspace_limit(self, nbytes):
+        self.limits.append(nbytes)
+
+
+@pytest.mark.parametrize("ndec,given,want", [
+    (1, None, []),                              # one decoder, nothing given: the library's own default stays
+    (1, 2.0, [2 << 30]),                        # ... the whole budget
+    (7, None, [int(96.0 * (1 << 30) / 7)]),     # several: the 96 GB default, split
+    (7, 2.0, [int(2.0 * (1 << 30) / 7)]),
+    (400, None, [1 << 28]),                     # never below 256 MB each
+])
+def test_workspace_budget_is_split_among_the_decoders(ndec, given, want):
+    from quits_amd.decoder.plan import set_workspace_limits
+    decs = [_RecordsLimit() for _ in range(ndec)]
+    set_workspace_limits(decs, given)
+    assert [d.limits for d in decs] == [want] * ndec

@@ -321,7 +321,7 @@ def test_dem_structure_cache_does_not_replay_channels():
 
 
 def test_plan_key_carries_the_setting():
-    from quits_amd.decoder.sliding_window import _circuit_fingerprint
+    from quits_amd.decoder.plan_cache import _circuit_fingerprint
     text = cc_.biased(helpers.circuit_text("bb72_custom_r0_p0.003"))
     plain, flagged = _circuit_fingerprint(text), _circuit_fingerprint(Circuit(text, approximate_disjoint_errors=True))
     assert plain == _circuit_fingerprint(Circuit(text)) == hashlib.sha1(text.encode()).hexdigest()
@@ -377,7 +377,7 @@ def test_abi_checks_the_channel_opcodes_before_touching_a_device():
         assert rc == -1 and b"runs past the end of the thresholds" in msg, (rc, msg)
         bad[pc + 2] = nthr - K                                   # the last place it fits: not a range error any more
         rc, msg = create(bad)
-        assert b"runs past" not in msg and b"out of range" not in msg
+        assert rc == 0 or (b"runs past" not in msg and b"out of range" not in msg), (rc, msg)   # (created, on a GPU: the message is the last failure's)
     thr = cc.thresholds.copy()
     t0 = int(cc.program[p2 + 2])
     thr[t0 + 7] = thr[t0 + 6] - 1

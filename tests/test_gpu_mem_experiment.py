@@ -122,10 +122,11 @@ def test_result_does_not_depend_on_the_batch(gpu, text, cd, full, batch, rounded
 def test_two_stream_driver_gives_the_same(gpu, text, cd, full, monkeypatch):
     """A batch of three plan chunks (chunks of 1024 shots) goes through the two-stream driver, whose status words arrive as views of one
     table: same tallies, same failing shots."""
+    from quits_amd.decoder import pipeline
     from quits_amd.decoder import sliding_window as sw
     calls = []
-    impl = sw._decode_pipelined_impl
-    monkeypatch.setattr(sw, "_decode_pipelined_impl", lambda plan, det, stats, chain=None: calls.append(det.shape[0]) or impl(plan, det, stats, chain))
+    impl = pipeline.decode_pipelined
+    monkeypatch.setattr(pipeline, "decode_pipelined", lambda plan, det, stats, ready=None: calls.append(det.shape[0]) or impl(plan, det, stats, ready))
     monkeypatch.setenv("QD_CHUNK_SHOTS", "1024")
     sw.plan_cache_clear()                                  # the cached plan has the default chunk
     try:

@@ -530,7 +530,7 @@ def _circuit_dem(name, p_from=None, p_to=None):
 ])
 def test_pipelined_chunks_equal_single_stream(gpu, W, F, opts):
     """A call of two or more chunks runs the post-processing (OSD / LSD, acc ^= L e, the hand-off U e) on a second stream
-    beside the BP of the other chunk of a pair, with a second set of decoders (sliding_window.py _decode_pipelined_impl).
+    beside the BP of the other chunk of a pair, with a second set of decoders (pipeline.py decode_pipelined).
     Predictions and status words must equal the single-stream path's, shot for shot -- three chunks, the last one ragged, twice
     in a row (workspaces, buffers and streams reused), with work queued on the caller's stream before (the syndromes are
     sampled there) and after (the comparison)."""
@@ -577,6 +577,7 @@ def test_public_call_plan_cache_and_streamed_host_samples(gpu, monkeypatch):
     equal to the device-resident plan's."""
     import torch
     from quits_amd.decoder import sliding_window_bposd_circuit_mem
+    from quits_amd.decoder import plan_cache
     from quits_amd.decoder import sliding_window as sw
     from quits_amd.decoder.device import DemSampler
     from quits_amd.dem import Circuit
@@ -600,21 +601,21 @@ def test_public_call_plan_cache_and_streamed_host_samples(gpu, monkeypatch):
     info = sw.plan_cache_info()
     assert info["misses"] == 1 and info["hits"] == 5 and info["size"] == 1
     # pieces of 1024 shots through the staging buffers (3000 = 1024 + 1024 + 952)
-    plan = next(iter(sw._CACHE.values()))
-    plan.chunk, plan.host_piece, plan._stage = 1024, 1024, None
+    plan = next(iter(plan_cache._CACHE.values()))
+    plan.chunk, plan.host_piece = 1024, 1024
     assert np.array_equal(plan.decode_host(det_h.astype(np.bool_)), ref)
     assert np.array_equal(plan.decode_host(det_h[:10]), ref[:10]) and plan.decode_host(det_h[:0]).shape == (0, ref.shape[1])
     # pieces of two or more chunks: ONE chain of the two-lane pipeline across the pieces (3000 = 4 x 256 | 4 x 256 | 3 x 256 + 184;
-    # 2900 and 2400 leave a last piece of less than two chunks / less than one, chained like the others), and the same with the chain switched off
+    # 2900 and 2400 leave a last piece of less than two chunks / less than one, chained like the others), and the same piece by piece, unchained
     assert plan.pipeline
-    plan.chunk, plan.host_piece, plan._stage = 256, 1024, None
+    plan.chunk, plan.host_piece = 256, 1024
     assert np.array_equal(plan.decode_host(det_h), ref)
-    plan.chunk, plan.host_piece, plan._stage = 500, 1000, None
+    plan.chunk, plan.host_piece = 500, 1000
     assert np.array_equal(plan.decode_host(det_h[:2900]), ref[:2900])
     assert np.array_equal(plan.decode_host(det_h[:2400]), ref[:2400])
-    monkeypatch.setenv("QD_NO_HOST_CHAIN", "1")
+    plan.pipeline = False
     assert np.array_equal(plan.decode_host(det_h[:2900]), ref[:2900])
-    monkeypatch.delenv("QD_NO_HOST_CHAIN")
+    plan.pipeline = True
     assert np.array_equal(plan.decode(det).cpu().numpy().astype(np.int64), ref)          # (the plan's device-resident call after a chain)
     # another option / another window shape / another circuit: misses
     sliding_window_bposd_circuit_mem(det_h, circ, hz, lz, 3, 1, **dict(kw, max_iter=21))

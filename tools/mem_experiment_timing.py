@@ -146,14 +146,13 @@ def main():
     import torch
     from quits_amd.decoder.bposd import BpOsdDecoder
     from quits_amd.decoder.device import CircuitSampler
-    from quits_amd.decoder.sliding_window import build_circuit_plan, cached_plan, plan_key
+    from quits_amd.decoder.plan import cached_circuit_plan
     from quits_amd.dem import Circuit
     text = helpers.circuit_text(NAME)
     cd = helpers.code("bb144")
     circ = Circuit(text)
     opts = {k: KW[k] for k in ("bp_method", "max_iter", "schedule", "osd_method", "osd_order")}
-    plan = cached_plan(plan_key("circuit", circ, cd["hz"], None, W, F, 12, BpOsdDecoder, BpOsdDecoder, opts, opts),
-                       lambda: build_circuit_plan(circ, cd["hz"], W, F, 12, dict(opts), dict(opts), BpOsdDecoder, BpOsdDecoder))
+    plan = cached_circuit_plan(circ, cd["hz"], W, F, 12, BpOsdDecoder, BpOsdDecoder, opts, opts)
     assert len(plan.windows) == 1
     sampler = CircuitSampler(text)
     row = dict(circuit=NAME, decoder=KW, device=torch.cuda.get_device_name(0))
