@@ -1,6 +1,6 @@
 // bp_scatter_wide_walk.inc -- the edge walk of one gather pass of one check (bp_scatter_wide.hip), as program text: included by
 // qd_bp_scatter_wide_kernel for every pass and by qd_bp_first_pass_kernel, which runs pass 0 once per decoder -- the same QS_EDGE_M
-// steps (bp_scatter_edge.h, with QS_MAG_MASK), trip counts, tail rules and argmin rule, so the table cannot drift from what the loop would have found.
+// steps (bp_scatter_edge.h, with QS_MAG_MASK and QS_SIGN_TOP), trip counts, tail rules and argmin rule, so the table cannot drift from what the loop would have found.
 // In scope at the point of inclusion: j, dws, cs, S1, S2, KOLD, dcs, O, pf, a1, a2, kst, adj_row, QS_ADJ, QS_ACC.  Leaves hp, par, neg[].
 // "Is this the edge my last minimum came from" (min2 goes back on that edge, min1 on the others) is asked through lane masks in scalar registers, not per edge
 // on the vector ALU: lq[q] once per check and pass, gsel_ once per group of four edges (the group index is wave-uniform in all four loop forms), their AND
@@ -26,9 +26,16 @@
                     neg[w] = 0u;
                     const int k0 = 32 * w;
                     if (k0 < trip) {
-                        const uint32_t sgnw = O[j][w];
-                        uint32_t neww = 0u, ltw = 0u;
                         const int kend = min(trip - k0, 32);                  // multiple of 4
+                        // One register for the signs sent last time and the signs collected now.  The sent word O[j][w] has edge i of the word at bit
+                        // kend - 1 - i; shifted left by 32 - kend (0 for a full word: & 31) edge 0 stands at bit 31, where QS_SIGN_TOP reads it.  Every position
+                        // of the walk -- an edge's v_alignbit, a pad position's shift -- then moves the word up by one and enters its new sign at bit 0, so
+                        // the next edge's sent sign is at bit 31 when that edge asks.  After the word's kend positions the kend new signs fill bits
+                        // kend - 1 .. 0 and everything the word started with has left at the top: the sent signs, and whatever `flip` set above bit
+                        // kend - 1 of O (all ones for a check with syndrome ^ parity = 1), which the pre-shift already dropped; the 32 - kend zeros the
+                        // pre-shift brought in at the bottom are the bits above kend - 1 now.  The result is bit for bit the word that started from 0.
+                        // (Lanes past their degree collect QS_BIG's sign, 0, whatever they read as the sent sign; the first-pass table walks with O = 0.)
+                        uint32_t neww = O[j][w] << ((32 - kend) & 31), ltw = 0u;
                         const int kplain = min(max(wmin4 - k0, 0), kend);     // groups every lane of the wavefront has in full
                         const int row0 = k0 >> 2;
                         uint4 nx = (j == 0 && w == 0) ? pf : QS_ADJ(row0);
@@ -39,17 +46,17 @@
                             for (; kk + 8 <= kplain; kk += 8) {
                                 eb = QS_ADJ(row0 + (kk >> 2) + 1);            // (the table has spare group rows)
                                 {
-                                    const int sb = kend - 1 - kk, k = k0 + kk;
+                                    const int k = k0 + kk;
                                     QS_GSEL(k)
-                                    QS_EDGE_M(nx.x, k, sb, QS_NOFIX, QS_HPA, QS_MAG_MASK(0)) QS_EDGE_M(nx.y, k + 1, sb - 1, QS_NOFIX, QS_HPB, QS_MAG_MASK(1))
-                                    QS_EDGE_M(nx.z, k + 2, sb - 2, QS_NOFIX, QS_HPA, QS_MAG_MASK(2)) QS_EDGE_M(nx.w, k + 3, sb - 3, QS_NOFIX, QS_HPB, QS_MAG_MASK(3))
+                                    QS_EDGE_M(nx.x, k, QS_SIGN_TOP, QS_NOFIX, QS_HPA, QS_MAG_MASK(0)) QS_EDGE_M(nx.y, k + 1, QS_SIGN_TOP, QS_NOFIX, QS_HPB, QS_MAG_MASK(1))
+                                    QS_EDGE_M(nx.z, k + 2, QS_SIGN_TOP, QS_NOFIX, QS_HPA, QS_MAG_MASK(2)) QS_EDGE_M(nx.w, k + 3, QS_SIGN_TOP, QS_NOFIX, QS_HPB, QS_MAG_MASK(3))
                                 }
                                 nx = QS_ADJ(row0 + (kk >> 2) + 2);
                                 {
-                                    const int sb = kend - 5 - kk, k = k0 + kk + 4;
+                                    const int k = k0 + kk + 4;
                                     QS_GSEL(k)
-                                    QS_EDGE_M(eb.x, k, sb, QS_NOFIX, QS_HPA, QS_MAG_MASK(0)) QS_EDGE_M(eb.y, k + 1, sb - 1, QS_NOFIX, QS_HPB, QS_MAG_MASK(1))
-                                    QS_EDGE_M(eb.z, k + 2, sb - 2, QS_NOFIX, QS_HPA, QS_MAG_MASK(2)) QS_EDGE_M(eb.w, k + 3, sb - 3, QS_NOFIX, QS_HPB, QS_MAG_MASK(3))
+                                    QS_EDGE_M(eb.x, k, QS_SIGN_TOP, QS_NOFIX, QS_HPA, QS_MAG_MASK(0)) QS_EDGE_M(eb.y, k + 1, QS_SIGN_TOP, QS_NOFIX, QS_HPB, QS_MAG_MASK(1))
+                                    QS_EDGE_M(eb.z, k + 2, QS_SIGN_TOP, QS_NOFIX, QS_HPA, QS_MAG_MASK(2)) QS_EDGE_M(eb.w, k + 3, QS_SIGN_TOP, QS_NOFIX, QS_HPB, QS_MAG_MASK(3))
                                 }
                             }
                         }
@@ -57,29 +64,29 @@
                         for (; kk < kplain; kk += 4) {
                             const uint4 e4 = nx;
                             nx = QS_ADJ(row0 + (kk >> 2) + 1);
-                            const int sb = kend - 1 - kk, k = k0 + kk;
+                            const int k = k0 + kk;
                             QS_GSEL(k)
-                            QS_EDGE_M(e4.x, k, sb, QS_NOFIX, QS_HPA, QS_MAG_MASK(0))
-                            QS_EDGE_M(e4.y, k + 1, sb - 1, QS_NOFIX, QS_HPB, QS_MAG_MASK(1))
-                            QS_EDGE_M(e4.z, k + 2, sb - 2, QS_NOFIX, QS_HPA, QS_MAG_MASK(2))
-                            QS_EDGE_M(e4.w, k + 3, sb - 3, QS_NOFIX, QS_HPB, QS_MAG_MASK(3))
+                            QS_EDGE_M(e4.x, k, QS_SIGN_TOP, QS_NOFIX, QS_HPA, QS_MAG_MASK(0))
+                            QS_EDGE_M(e4.y, k + 1, QS_SIGN_TOP, QS_NOFIX, QS_HPB, QS_MAG_MASK(1))
+                            QS_EDGE_M(e4.z, k + 2, QS_SIGN_TOP, QS_NOFIX, QS_HPA, QS_MAG_MASK(2))
+                            QS_EDGE_M(e4.w, k + 3, QS_SIGN_TOP, QS_NOFIX, QS_HPB, QS_MAG_MASK(3))
                         }
                         // an edge below the smallest degree of the wavefront is real on every lane (no fix), one at or beyond the largest is
                         // nobody's; only in between does a lane have to ask (wave-uniform tests; k < wmax: a group starts below the largest degree)
 #define QS_TAIL_EDGE(off, q_)                                                                                     \
-                            if (k + (q_) < wmin) QS_EDGE_M(off, k + (q_), sb - (q_), QS_NOFIX, QS_HP1, QS_MAG_MASK(q_))            \
-                            else if (k + (q_) < wmax) QS_EDGE_M(off, k + (q_), sb - (q_), QS_TAILFIX, QS_HP1, QS_MAG_MASK(q_))     \
+                            if (k + (q_) < wmin) QS_EDGE_M(off, k + (q_), QS_SIGN_TOP, QS_NOFIX, QS_HP1, QS_MAG_MASK(q_))         \
+                            else if (k + (q_) < wmax) QS_EDGE_M(off, k + (q_), QS_SIGN_TOP, QS_TAILFIX, QS_HP1, QS_MAG_MASK(q_))  \
                             else { neww <<= 1; ltw <<= 1; }
 #pragma unroll 1
                         for (; kk + 4 < kend; kk += 4) {
                             const uint4 e4 = nx;
                             nx = QS_ADJ(row0 + (kk >> 2) + 1);
-                            const int sb = kend - 1 - kk, k = k0 + kk;
+                            const int k = k0 + kk;
                             QS_GSEL(k)
                             QS_TAIL_EDGE(e4.x, 0) QS_TAIL_EDGE(e4.y, 1) QS_TAIL_EDGE(e4.z, 2) QS_TAIL_EDGE(e4.w, 3)
                         }
                         if (kk < kend) {              // the word's last group (for rows of 33..36 faults the second word's only one): nothing to request behind it, no copy
-                            const int sb = kend - 1 - kk, k = k0 + kk;
+                            const int k = k0 + kk;
                             QS_GSEL(k)
                             QS_TAIL_EDGE(nx.x, 0) QS_TAIL_EDGE(nx.y, 1) QS_TAIL_EDGE(nx.z, 2) QS_TAIL_EDGE(nx.w, 3)
                         }
