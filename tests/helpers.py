@@ -72,6 +72,55 @@ def same_sparse(a, b):
     return a.shape == b.shape and np.array_equal(a.indptr, b.indptr) and np.array_equal(a.indices, b.indices)
 
 
+# ---- seeded synthetic windows with prescribed row and column weights (the GPU tests that need weights no fixture has) --------------
+def _place(rng, rows, cdeg):
+    """A 0/1 matrix with the row weights `rows` (heaviest first, dealt to shuffled row indices) and the column weights `cdeg`: every row
+    takes the columns with the most free places, random among equals (the bipartite Havel-Hakimi rule: every edge is placed and no
+    column is used twice in a row)."""
+    left = cdeg.copy()
+    H = np.zeros((len(rows), len(cdeg)), dtype=np.uint8)
+    for i, w in zip(rng.permutation(len(rows)), rows):
+        cols = np.lexsort((rng.random(len(cdeg)), -left))[:w]
+        assert left[cols].min() >= 1
+        H[i, cols] = 1
+        left[cols] -= 1
+    assert not left.any()
+    return H
+
+
+def synthetic_window(rows, cmin, cmax, seed):
+    """A seeded random parity-check matrix (csc) with the row weights `rows` (heaviest first; the rows are shuffled) and its priors.
+    Every row has exactly two faults of column weight 2 (as many such columns as rows); its other faults have weight cmin..cmax (about
+    total / ((cmin + cmax) // 2) columns of equal weight, then seeded +1 / -1 moves that keep the sum and spread the weights over the
+    whole range).  The two light faults keep min-sum's magnitudes from growing geometrically on a syndrome BP cannot meet (the all-ones
+    one): a light fault passes on its prior plus ONE message, and every message a check sends is the minimum over edges that include a
+    light fault, so the largest message grows by at most the largest prior per iteration."""
+    rows = [int(w) for w in rows]
+    rng = np.random.default_rng(seed)
+    m = len(rows)
+    assert rows == sorted(rows, reverse=True) and rows[-1] > 2 and 2 < cmin <= cmax <= m
+    light = _place(rng, [2] * m, np.full(m, 2, dtype=np.int64))
+    total = sum(rows) - 2 * m
+    n = max(total // ((cmin + cmax) // 2), max(rows) - 2)
+    cdeg = np.full(n, total // n, dtype=np.int64)
+    cdeg[:total - cdeg.sum()] += 1
+    assert cmin <= cdeg.min() and cdeg.max() <= cmax, (cdeg.min(), cdeg.max())
+    for _ in range(2 * n * (cmax - cmin + 1)):
+        a, b = rng.integers(0, n, size=2)
+        if a != b and cdeg[a] < cmax and cdeg[b] > cmin:
+            cdeg[a] += 1
+            cdeg[b] -= 1
+    assert cdeg.sum() == total and cdeg.min() >= cmin and cdeg.max() == cmax, (cdeg.min(), cdeg.max())
+    H = np.concatenate([light, _place(rng, [w - 2 for w in rows], cdeg)], axis=1)
+    H = H[:, rng.permutation(H.shape[1])]
+    assert sorted(H.sum(axis=1).tolist(), reverse=True) == rows
+    assert H.sum(axis=0).min() == 2 and H.sum(axis=0).max() == cmax
+    # three to four faults per shot, spread over three decades: with near-equal priors the all-ones syndrome of an odd row weight is met
+    # by the first iteration's hard decisions (every fault set) and nothing is left to iterate
+    pri = np.minimum(0.08, 10.0 ** rng.uniform(-2.5, 0.5, size=H.shape[1]) * 8.0 / H.shape[1])
+    return csc_matrix(H), pri
+
+
 # ---- the CPU oracle over several processes (the oracle is single-threaded C; the larger parity tests slice the shots) ----------
 def _oracle_procs():
     return max(1, min(32, len(os.sched_getaffinity(0))))

@@ -84,6 +84,12 @@ static int check(const HostGraph &h, const GraphImage &g)
         auto rec_at = [&](int s, int w) { return rec[((size_t)(w >> 2) * n_pad + s) * 4 + (w & 3)]; };
         std::vector<std::set<uint32_t>> signs(m);
         CHECK(rec.size() == (size_t)n_pad * bp.rec_words && bp.rec_words % 4 == 0 && bp.rec_words > h.max_cdeg);
+        const auto degp_w = arr<int32_t>(g, &bp.chk_degp_w);
+        CHECK((int)degp_w.size() == m_pad / 64 && bp.neg_words == (bp.max_rdeg_pad + 31) / 32);
+        for (int w0 = 0; w0 < m_pad; w0 += 64) {            // trip count of a wavefront: its largest degree (slots descend) rounded up to 4 | that degree
+            const int mx = w0 < m ? h.rdeg[chk_orig[w0]] : 0;
+            CHECK(degp_w[w0 / 64] == (((mx + 3) & ~3) | (mx << 16)));
+        }
         for (int s = 0; s < n_pad; ++s) {
             const int j = s < n ? (int)bit_orig[s] : -1, deg = s < n ? h.cdeg[j] : 0;
             const float l0 = s < n ? (float)h.llr0[j] : 1.0f;
@@ -94,6 +100,12 @@ static int check(const HostGraph &h, const GraphImage &g)
                 const int i = h.ri[h.cp[j] + q];
                 CHECK((int)(r >> 16) == bp.off_chk + chk_slot[i] * 16 && signs[i].insert(where).second);
                 CHECK(bp.sign_mode == 2 ? (int)(where >> 5) < bp.neg_words : (where < 32 || (bp.sign_mode == 1 && where >= 48 && where < 63)));
+                // the sign sits where the check pass puts it: step k of the walk lands on bit kend - 1 - (k & 31) of word k >> 5 (kend = the word's
+                // share of the wavefront's trip count), and step k of this check's walk is this fault -- in every sign word and every record slot
+                const int w = bp.sign_mode == 2 ? (int)(where >> 5) : (where < 32 ? 0 : 1), bit = bp.sign_mode == 2 ? (int)(where & 31u) : (int)(where < 32 ? where : where - 48);
+                const int kend = std::min((degp_w[chk_slot[i] / 64] & 0xFFFF) - 32 * w, 32), k = 32 * w + kend - 1 - bit;
+                CHECK(bit < kend && k >= 0 && k < h.rdeg[i] && adj[((size_t)(k >> 2) * m_pad + chk_slot[i]) * 4 + (k & 3)] == (uint32_t)bp.off_llr + (uint32_t)s * 4u);
+                CHECK(s < bp.bit_thr[q]);                   // the bit pass reads record slot q of this fault's wavefront
             }
         }
         for (int i = 0; i < m; ++i) CHECK((int)signs[i].size() == h.rdeg[i]);

@@ -56,21 +56,6 @@ SHAPES = {name: (128, 2, 2) for name in SYNTH}
 SHAPES["qlp1020_w3"] = (512, 3, 3)
 
 
-def _place(rng, rows, cdeg):
-    """A 0/1 matrix with the row weights `rows` (heaviest first, dealt to shuffled row indices) and the column weights `cdeg`: every row
-    takes the columns with the most free places, random among equals (the bipartite Havel-Hakimi rule: every edge is placed and no
-    column is used twice in a row)."""
-    left = cdeg.copy()
-    H = np.zeros((len(rows), len(cdeg)), dtype=np.uint8)
-    for i, w in zip(rng.permutation(len(rows)), rows):
-        cols = np.lexsort((rng.random(len(cdeg)), -left))[:w]
-        assert left[cols].min() >= 1
-        H[i, cols] = 1
-        left[cols] -= 1
-    assert not left.any()
-    return H
-
-
 def _synthetic(name):
     """A seeded random parity-check matrix with the row weights of SYNTH[name] and column weights 2..6, and its priors.
     Every row has exactly two faults of column weight 2 (as many such columns as rows); its other faults have weight 3..6 (4 each, then
@@ -81,7 +66,7 @@ def _synthetic(name):
     rows = SYNTH[name]
     rng = np.random.default_rng(20260 + sorted(SYNTH).index(name))
     m = len(rows)
-    light = _place(rng, [2] * m, np.full(m, 2, dtype=np.int64))
+    light = helpers._place(rng, [2] * m, np.full(m, 2, dtype=np.int64))
     total = sum(rows) - 2 * m
     n = max(total // 4, max(rows) - 2)
     cdeg = np.full(n, total // n, dtype=np.int64)
@@ -92,7 +77,7 @@ def _synthetic(name):
             cdeg[a] += 1
             cdeg[b] -= 1
     assert cdeg.sum() == total and cdeg.min() >= 3 and cdeg.max() == 6, (name, cdeg.min(), cdeg.max())
-    H = np.concatenate([light, _place(rng, [w - 2 for w in rows], cdeg)], axis=1)
+    H = np.concatenate([light, helpers._place(rng, [w - 2 for w in rows], cdeg)], axis=1)
     H = H[:, rng.permutation(H.shape[1])]
     assert sorted(H.sum(axis=1).tolist(), reverse=True) == rows
     assert H.sum(axis=0).min() == 2 and H.sum(axis=0).max() == 6

@@ -49,6 +49,13 @@ def synthetic(m, n, weights, seed, heavy_column=0, off_chip_columns=0):
     return (row_ptr, col_idx, n), rng.uniform(1e-3, 1e-2, n)
 
 
+# row weights, lightest and heaviest of the columns beside the two weight-2 faults of every row, seed (helpers.synthetic_window)
+LIMITS = {"rows_of_255": ([255] * 72, 3, 6, 30255), "column_of_weight_16": ([40] * 128, 7, 16, 30016),
+          "rows_of_255_columns_of_16": ([255] * 64 + [100] * 64, 7, 16, 30271),
+          "row_of_256": ([256] + [40] * 71, 3, 6, 31006), "column_of_weight_17": ([40] * 72, 14, 17, 31017)}
+REFUSED = {"row_of_256": "row weight 256 outside 1..255", "column_of_weight_17": "column weight 17 outside 1..16"}
+
+
 def _syn(name):
     rng = np.random.default_rng(7)
     if name == "70x300_rows_to_40":
@@ -59,6 +66,8 @@ def _syn(name):
         return synthetic(40, 120, np.concatenate([rng.integers(3, 7, 5), [1], rng.integers(3, 7, 34)]), 3)
     if name == "column_of_weight_12":
         return synthetic(64, 200, rng.integers(4, 9, 64), 4, heavy_column=12)
+    if name in LIMITS:                                   # the windows of tests/test_gpu_graph_limits.py at the limits of the ABI, and one past each
+        return helpers.synthetic_window(*LIMITS[name])
     assert name == "4100x9000_columns_of_3"
     return synthetic(4100, 9000, None, 5, off_chip_columns=3)
 
@@ -73,6 +82,9 @@ WINDOWS = {
     "600x6000_row_of_70": (lambda: _syn("600x6000_row_of_70"), {"sign_mode": 2, "sc_ok": 1, "wide_cpl": 3}),
     "row_of_one_fault": (lambda: _syn("row_of_one_fault"), {"min_rdeg": 1, "sc_ok": 0}),
     "column_of_weight_12": (lambda: _syn("column_of_weight_12"), {"frec": 0, "unroll": 16}),
+    "rows_of_255": (lambda: _syn("rows_of_255"), {"sign_mode": 2, "sc_ok": 0, "threads": 512, "off_chip": 0}),
+    "column_of_weight_16": (lambda: _syn("column_of_weight_16"), {"sign_mode": 1, "sc_ok": 1, "frec": 0, "unroll": 16, "off_chip": 0}),
+    "rows_of_255_columns_of_16": (lambda: _syn("rows_of_255_columns_of_16"), {"sign_mode": 2, "sc_ok": 0, "frec": 0, "unroll": 16, "off_chip": 0}),
     "4100x9000_columns_of_3": (lambda: _syn("4100x9000_columns_of_3"), {"off_chip": 1, "threads": 0, "sc_ok": 0}),
 }
 SWITCHES = {"QD_SCATTER_BANKS_BY_SLOT": {"sc_ok": 1}, "QD_SCATTER_WALK_GREEDY": {"sc_ok": 1}, "QD_SCATTER_NATURAL_ROUNDS": {"wide_cpl": 2},
@@ -136,3 +148,12 @@ def test_layout_invariants_under_the_validation_switches(layout_check, window_fi
     said = run(layout_check, window_files[name], SWITCHES[switch], env={switch: "1"})
     if switch in ("QD_SCATTER_BANKS_BY_SLOT", "QD_SCATTER_WALK_GREEDY"):       # the switch was read: the older bank assignment / walk costs more LDS cycles in the model
         assert int(said["walk"].split("/")[0]) > int(plain["walk"].split("/")[0]), (plain, said)
+
+
+@pytest.mark.parametrize("name", list(REFUSED))
+def test_one_past_a_limit_is_refused(layout_check, tmp_path, name):
+    """A row of 256 faults, a column of weight 17: qd_host_graph answers QD_ECAPACITY with the limit in the message, and the program exits with its refusal status."""
+    window = str(tmp_path / (name + ".bin"))
+    write_window(window, *_syn(name))
+    out = subprocess.run([layout_check, window], capture_output=True, text=True)
+    assert out.returncode == 3 and out.stderr.strip() == REFUSED[name] and not out.stdout, (out.returncode, out.stdout, out.stderr[-3000:])
