@@ -96,7 +96,7 @@ typedef struct qd_params {
     double ms_scaling_factor;   /* not exposed by the reference wrapper -> ldpc default 1.0; 0 = 1-2^-it */
 } qd_params;
 
-int qd_version(void);                 /* 108 (108: qd_shot_flags_fold, qd_tally_batch, qd_sample_circuit_shots, qd_sample_dem_shots; 107: off-chip windows decode, QD_FLAG_OFF_CHIP, QD_POST_OSD0_OFFCHIP, no new export; 106: qd_circuit_create accepts the biased-noise opcodes Y_ERROR / PAULI_CHANNEL_1 / PAULI_CHANNEL_2, no new export; 105: qd_decoder_fast_start; 104: qd_circuit_* + qd_sample_circuit; 103: qd_decoder_post_head_start; 101: qd_graph_info wrote 12 entries; 102: 10 again + qd_graph_info_ex) */
+int qd_version(void);                 /* 109 (109: qd_unpack_b8, qd_pack_b8; 108: qd_shot_flags_fold, qd_tally_batch, qd_sample_circuit_shots, qd_sample_dem_shots; 107: off-chip windows decode, QD_FLAG_OFF_CHIP, QD_POST_OSD0_OFFCHIP, no new export; 106: qd_circuit_create accepts the biased-noise opcodes Y_ERROR / PAULI_CHANNEL_1 / PAULI_CHANNEL_2, no new export; 105: qd_decoder_fast_start; 104: qd_circuit_* + qd_sample_circuit; 103: qd_decoder_post_head_start; 101: qd_graph_info wrote 12 entries; 102: 10 again + qd_graph_info_ex) */
 const char *qd_last_error(void);
 /* Number of visible HIP devices (0 if none): lets a host fail loudly before building anything. */
 int qd_device_count(void);
@@ -230,6 +230,19 @@ int qd_gf2_spmv_batch(const qd_spmat *A, const uint32_t *d_err_bits, int64_t err
 /* Packed error bits -> one byte per fault (the array ldpc's decode() returns; class-level plug-in). */
 int qd_unpack_bits(const uint32_t *d_bits, int64_t stride_words, int32_t nbits, int64_t B, uint8_t *d_out,
                    int64_t out_stride, void *stream);
+
+/* ---- Stim's bit-packed samples (format b8: what `compile_detector_sampler().sample(..., bit_packed=True)` returns and `--out_format b8`
+ *      writes), to and from the one byte per detector that qd_decode_batch reads.  The reference takes its `zcheck_samples` unpacked
+ *      (sliding_window.py:104-118); a host that holds them packed copies an eighth of the bytes and widens them here. */
+
+/* d_out[b*out_stride + c] = bit (bit0 + c) of packed row b, c < nbits.  Row b starts at d_packed + b*packed_stride (bytes, ANY alignment);
+ * bit k of a row is byte k>>3, bit k&7 (Stim's b8).  Writes exactly nbits bytes per row (values 0/1): out may be a column slice of a wider
+ * array.  bit0 >= 0 selects a field of a record, e.g. the observables Stim appends after the detectors. */
+int qd_unpack_b8(const uint8_t *d_packed, int64_t packed_stride, int64_t bit0, int32_t nbits, int64_t B,
+                 uint8_t *d_out, int64_t out_stride, void *stream);
+/* d_packed[b*packed_stride + i], i < ceil(nbits/8): bit j = d_in[b*in_stride + 8i + j] & 1; the padding bits of the last byte are 0; bytes
+ * of a row past ceil(nbits/8) are not touched. */
+int qd_pack_b8(const uint8_t *d_in, int64_t in_stride, int32_t nbits, int64_t B, uint8_t *d_packed, int64_t packed_stride, void *stream);
 
 /* Number of shots whose prediction differs from the observable flips on any of k bits: the `pL` numerator of
  * tests/test_sliding_window.py:83.  d_count (int64 on device) is incremented. */

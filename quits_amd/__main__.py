@@ -1,0 +1,110 @@
+"""`python -m quits_amd predict`: decode a file of detector samples against a detector error model, as the `predict` commands Stim users
+know do (sinter / pymatching: --dem, --in, --in_format, --out, --out_format).
+
+    python -m quits_amd predict --dem model.dem --in shots.b8 --in_format b8 --out predictions.01 --out_format 01
+
+Without --checks_per_round / --window / --commit the model is decoded over its whole history (quits_amd.decoder.decode_dem); with all three
+by the sliding-window decoder (quits_amd.decoder.sliding_window_bposd_circuit_mem), the detectors being rounds of --checks_per_round.
+Exit status: 0 done, 1 unreadable input, 2 bad arguments, or no GPU / no library (the decoder has no CPU fallback).
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+
+import numpy as np
+
+
+def _parser():
+    from .samples import FORMATS
+    ap = argparse.ArgumentParser(prog="python -m quits_amd", description="MI355X sliding-window BP-OSD decoder: command line.")
+    sub = ap.add_subparsers(dest="command", required=True)
+    p = sub.add_parser("predict", help="predict observable flips from detector samples",
+                       description="Predict the observable flips of every shot of a detector sample file.")
+    model = p.add_mutually_exclusive_group(required=True)
+    model.add_argument("--dem", metavar="FILE", help="detector error model, Stim's .dem text")
+    model.add_argument("--circuit", metavar="FILE", help="Stim circuit text (its detector error model is extracted here)")
+    p.add_argument("--in", dest="inp", metavar="FILE", required=True, help="detector samples")
+    p.add_argument("--in_format", choices=FORMATS, required=True)
+    p.add_argument("--in_includes_appended_observables", action="store_true",
+                   help="every shot of --in holds the observables after the detectors (stim sample/detect --append_observables)")
+    p.add_argument("--out", metavar="FILE", required=True, help="predicted observable flips, one shot per record")
+    p.add_argument("--out_format", choices=FORMATS, required=True)
+    p.add_argument("--obs_in", metavar="FILE", help="actual observable flips: prints one JSON line {\"shots\": .., \"errors\": ..}")
+    p.add_argument("--obs_in_format", choices=FORMATS, help="default: --in_format")
+    p.add_argument("--bp_method", default="product_sum")
+    p.add_argument("--schedule", default="serial")
+    p.add_argument("--max_iter", type=int, default=2)
+    p.add_argument("--osd_method", default="osd_cs")
+    p.add_argument("--osd_order", type=int, default=0)
+    p.add_argument("--checks_per_round", type=int, metavar="NZ", help="detectors per round (sliding window; with --window and --commit)")
+    p.add_argument("--window", type=int, metavar="W", help="rounds per window")
+    p.add_argument("--commit", type=int, metavar="F", help="rounds committed per window")
+    return ap
+
+
+def predict(args, ap) -> int:
+    from . import _lib
+    from .dem import Circuit, as_dem
+    from .samples import read_shots, write_shots
+    sliding = [args.checks_per_round, args.window, args.commit]
+    if any(v is not None for v in sliding) and not all(v is not None for v in sliding):
+        ap.error("--checks_per_round, --window and --commit go together")
+    if all(v is not None for v in sliding) and min(sliding) < 1:
+        ap.error("--checks_per_round, --window and --commit must be positive")
+    with open(args.dem or args.circuit, "r") as fh:
+        text = fh.read()
+    model = text if args.dem else Circuit(text)
+    dem = as_dem(model)
+    ndet, nobs = dem.num_detectors, dem.num_observables
+    rec = read_shots(args.inp, args.in_format, ndet, nobs if args.in_includes_appended_observables else 0)
+    det = rec.field(0, ndet)
+    actual = rec.field(ndet, nobs) if args.in_includes_appended_observables else None
+    if args.obs_in:
+        actual = read_shots(args.obs_in, args.obs_in_format or args.in_format, nobs)
+        if len(actual) != len(det):
+            raise ValueError("%s holds %d shots, %s holds %d" % (args.obs_in, len(actual), args.inp, len(det)))
+    _lib.require_gpu()
+    opts = dict(max_iter=args.max_iter, osd_order=args.osd_order, bp_method=args.bp_method, schedule=args.schedule, osd_method=args.osd_method)
+    if args.window is not None:
+        import warnings
+        from .decoder import sliding_window_bposd_circuit_mem
+        nz = args.checks_per_round
+        if ndet % nz:
+            raise ValueError("the model's %d detectors are not whole rounds of %d" % (ndet, nz))
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")           # (whole-history notice of the reference: not an error here)
+            pred = sliding_window_bposd_circuit_mem(det, model, np.zeros((nz, 1), np.uint8), np.zeros((nobs, 1), np.uint8),
+                                                    args.window, args.commit, **opts)
+    else:
+        from .decoder import decode_dem
+        pred = decode_dem(model, det, **opts)
+    write_shots(args.out, pred.astype(np.uint8), args.out_format, num_detectors=0)
+    if actual is not None:
+        import torch
+        from .decoder.device import Tally
+        tally = Tally(nobs)
+        if len(det):
+            from .decoder.pipeline import _to_device_samples
+            tally.add(torch.from_numpy(pred.astype(np.uint8)).to("cuda"), _to_device_samples(actual))
+        counts = tally.counts()
+        print(json.dumps({"shots": int(counts[0]), "errors": int(counts[1])}))
+    return 0
+
+
+def main(argv=None) -> int:
+    ap = _parser()
+    args = ap.parse_args(argv)
+    try:
+        return predict(args, ap)
+    except RuntimeError as exc:                      # no GPU, no library, a library error: the package's own text
+        print(str(exc), file=sys.stderr)
+        return 2
+    except (ValueError, OSError, NotImplementedError) as exc:
+        print("quits_amd predict: %s" % exc, file=sys.stderr)
+        return 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -49,6 +49,7 @@ EXPORTS = [
     "qd_unpack_bits", "qd_count_mismatch", "qd_sample_dem",
     "qd_circuit_create", "qd_circuit_destroy", "qd_circuit_info", "qd_sample_circuit",
     "qd_shot_flags_fold", "qd_tally_batch", "qd_sample_circuit_shots", "qd_sample_dem_shots",
+    "qd_unpack_b8", "qd_pack_b8",
 ]
 
 
@@ -118,6 +119,9 @@ def load():
         L.qd_tally_batch.argtypes = [vp, i64, vp, i64, i32, i64, vp, vp, vp, vp]
         L.qd_sample_circuit_shots.argtypes = [vp, u64, vp, i64, vp, i64, vp, i64, vp]
         L.qd_sample_dem_shots.argtypes = [vp, vp, vp, u64, vp, i64, vp, i64, vp, i64, vp]
+    if hasattr(L, "qd_unpack_b8"):                  # (library version 109; an older library named by QUITS_AMD_LIB takes unpacked samples as before)
+        L.qd_unpack_b8.argtypes = [vp, i64, i64, i32, i64, vp, i64, vp]
+        L.qd_pack_b8.argtypes = [vp, i64, i32, i64, vp, i64, vp]
     _lib = L
     return L
 
@@ -131,6 +135,13 @@ def require_experiment(L):
     """The entry points of library version 108 (tallies, flag fold, list sampling): a clear error from an older library."""
     if not hasattr(L, "qd_tally_batch"):
         raise RuntimeError("quits_amd: %s is version %d; the device-resident memory experiment needs >= 108 -- rebuild it" % (LIB_PATH, L.qd_version()))
+    return L
+
+
+def require_bitpack(L):
+    """The entry points of library version 109 (bit-packed samples): a clear error from an older library."""
+    if not hasattr(L, "qd_unpack_b8"):
+        raise RuntimeError("quits_amd: %s is version %d; bit-packed samples need >= 109 -- rebuild it" % (LIB_PATH, L.qd_version()))
     return L
 
 

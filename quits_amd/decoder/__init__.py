@@ -4,6 +4,7 @@ from .base import (detector_error_model_to_matrix, dict_to_csc_matrix_column_row
 from .sliding_window import sliding_window_circuit_mem, sliding_window_phenom_mem
 from .bposd import BpOsdDecoder, sliding_window_bposd_circuit_mem, sliding_window_bposd_phenom_mem
 from .bplsd import BpLsdDecoder, sliding_window_bplsd_circuit_mem, sliding_window_bplsd_phenom_mem
+from .whole_history import decode_dem
 
 __all__ = [
     "dict_to_csc_matrix_column_row",
@@ -18,4 +19,5 @@ __all__ = [
     "sliding_window_bplsd_circuit_mem",
     "BpOsdDecoder",
     "BpLsdDecoder",
+    "decode_dem",              # beyond the reference's names: any detector error model over its whole history (whole_history.py)
 ]

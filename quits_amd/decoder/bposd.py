@@ -57,11 +57,15 @@ class BpOsdDecoder:
         self.last_status = None
 
     def decode_batch(self, syndromes):
-        """syndromes: [B, m] numpy/torch (any integer/bool dtype)  ->  numpy uint8 [B, n]."""
+        """syndromes: [B, m] numpy/torch (any integer/bool dtype), or bit-packed quits_amd.samples.PackedSamples of m bits  ->  numpy uint8 [B, n]."""
         import torch
         from .device import unpack_bits
         from .pipeline import _to_device_samples
-        if not isinstance(syndromes, torch.Tensor):
+        from ..samples import PackedSamples
+        if isinstance(syndromes, PackedSamples):
+            if syndromes.num_bits != self.m:
+                raise ValueError("syndromes must have shape [B, %d]" % self.m)
+        elif not isinstance(syndromes, torch.Tensor):
             syndromes = np.asarray(syndromes)
             if syndromes.ndim != 2 or syndromes.shape[1] != self.m:
                 raise ValueError("syndromes must have shape [B, %d]" % self.m)

@@ -316,6 +316,13 @@ class DemSampler:
                                    det.stride(0), _ptr(obs), obs.stride(0), _stream_ptr()))
         return det, obs
 
+    def sample_packed(self, shots: int, seed: int, shot0: int = 0):
+        """`sample` bit-packed on the device (qd_pack_b8): (PackedSamples det, PackedSamples obs), CUDA tensors of ceil(m / 8) and
+        ceil(nobs / 8) bytes per shot -- Stim's `sample(..., bit_packed=True, separate_observables=True)`."""
+        from ..samples import PackedSamples
+        det, obs = self.sample(shots, seed, shot0)
+        return PackedSamples.pack(det), PackedSamples.pack(obs)
+
     def sample_shots(self, indices, seed: int):
         """Row b = shot indices[b] of this seed's stream (qd_sample_dem_shots): what `sample(1, seed, shot0=indices[b])` returns.  `indices`: an
         int64 cuda tensor or any integer sequence; any order, repeats allowed."""
@@ -371,6 +378,13 @@ class CircuitSampler:
         _lib.check(self._L.qd_sample_circuit(self._h, C.c_uint64(int(seed) & (2 ** 64 - 1)), int(shot0), int(shots), _ptr(det),
                                              det.stride(0), _ptr(obs), obs.stride(0), _stream_ptr()))
         return det, obs
+
+    def sample_packed(self, shots: int, seed: int, shot0: int = 0):
+        """`sample` bit-packed on the device (qd_pack_b8): (PackedSamples det, PackedSamples obs), CUDA tensors of ceil(m / 8) and
+        ceil(nobs / 8) bytes per shot -- Stim's `sample(..., bit_packed=True, separate_observables=True)`."""
+        from ..samples import PackedSamples
+        det, obs = self.sample(shots, seed, shot0)
+        return PackedSamples.pack(det), PackedSamples.pack(obs)
 
     def sample_shots(self, indices, seed: int):
         """Row b = shot indices[b] of this seed's stream (qd_sample_circuit_shots): what `sample(1, seed, shot0=indices[b])` returns.

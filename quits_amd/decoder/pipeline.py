@@ -6,6 +6,13 @@ import numpy as np
 
 def _to_device_samples(zcheck_samples):
     import torch
+    from ..samples import PackedSamples
+    if isinstance(zcheck_samples, PackedSamples):              # bit-packed rows: moved as they are, widened on the device (qd_unpack_b8)
+        ps = zcheck_samples
+        if not ps.is_cuda:
+            lo, hi = ps.bit0 >> 3, (ps.bit0 + ps.num_bits + 7) >> 3
+            ps = PackedSamples(torch.from_numpy(np.ascontiguousarray(ps.data[:, lo:hi])).to("cuda"), ps.num_bits, ps.bit0 & 7)
+        return ps.unpack()
     if isinstance(zcheck_samples, torch.Tensor):
         t = zcheck_samples
         if t.dtype == torch.bool:
@@ -150,10 +157,20 @@ class HostStaging:
         self.device = device
         self.copy = torch.cuda.Stream(device=device)
         self.pin = self.dev = self.out = None
+        self.pin_packed = self.dev_packed = None               # bit-packed rows on their way to `dev` (PackedSamples input)
 
-    def fit(self, rows, ndet, shots, nobs):
+    def fit(self, rows, ndet, shots, nobs, packed_bytes=0):
+        """packed_bytes > 0: the host rows arrive bit-packed, that many bytes each: the pinned buffers (and their device copies) are cut for
+        them, [rows, packed_bytes], and only the device buffers hold a byte per detector."""
         import torch
-        if self.pin is None or self.pin[0].shape[1] != ndet or self.pin[0].shape[0] < rows:
+        if packed_bytes:
+            if self.pin_packed is None or self.pin_packed[0].shape[1] != packed_bytes or self.pin_packed[0].shape[0] < rows:
+                self.pin_packed = [torch.empty((rows, packed_bytes), dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+                self.dev_packed = [torch.empty((rows, packed_bytes), dtype=torch.uint8, device=self.device) for _ in range(2)]
+            if self.dev is None or self.dev[0].shape[1] != ndet or self.dev[0].shape[0] < rows:
+                self.pin = None
+                self.dev = [torch.empty((rows, ndet), dtype=torch.uint8, device=self.device) for _ in range(2)]
+        elif self.pin is None or self.pin[0].shape[1] != ndet or self.pin[0].shape[0] < rows:
             self.pin = [torch.empty((rows, ndet), dtype=torch.uint8, pin_memory=True) for _ in range(2)]
             self.dev = [torch.empty((rows, ndet), dtype=torch.uint8, device=self.device) for _ in range(2)]
         if self.out is None or self.out.shape[0] < shots:
@@ -163,12 +180,18 @@ class HostStaging:
 def decode_host_samples(plan, stage, a):
     """a: numpy [N, ndet], N > 0, any integer dtype or bool  ->  int64 numpy [N, nobs], through `stage` (a HostStaging): pieces of
     `plan.host_piece` shots, rounded down to whole chunks, are copied chunk by chunk into a pinned buffer and on to the device on the copy
-    stream, beside the decoding of the piece before."""
+    stream, beside the decoding of the piece before.  `a` may be host PackedSamples: then the PACKED rows are staged and copied, and
+    qd_unpack_b8 on the copy stream fills the device buffer ahead of the event the decode waits for."""
     import torch
+    from ..samples import PackedSamples, unpack_b8_into
     N, ndet = a.shape
-    as_u8 = (lambda x: x.view(np.uint8)) if a.dtype == np.bool_ else ((lambda x: x) if a.dtype == np.uint8 else (lambda x: (x % 2).astype(np.uint8)))
+    packed = isinstance(a, PackedSamples)
+    if packed:
+        byte_lo, byte_hi, bit_lo = a.bit0 >> 3, (a.bit0 + a.num_bits + 7) >> 3, a.bit0 & 7
+        rows_packed = a.data
+    as_u8 = None if packed else (lambda x: x.view(np.uint8)) if a.dtype == np.bool_ else ((lambda x: x) if a.dtype == np.uint8 else (lambda x: (x % 2).astype(np.uint8)))
     piece = N if N <= plan.chunk else min(N, max(plan.chunk, int(plan.host_piece) // plan.chunk * plan.chunk))
-    stage.fit(piece, ndet, N, plan.nobs)
+    stage.fit(piece, ndet, N, plan.nobs, packed_bytes=(byte_hi - byte_lo) if packed else 0)
     out = stage.out
     cur = torch.cuda.current_stream()
     h2d_done, dec_done = [None, None], [None, None]
@@ -197,8 +220,13 @@ def decode_host_samples(plan, stage, a):
             with torch.cuda.stream(stage.copy):                # chunk by chunk: the first chunk's BP starts behind ITS copy, not the piece's
                 for c0 in range(0, hi - lo, plan.chunk):
                     c1 = min(hi - lo, c0 + plan.chunk)
-                    np.copyto(stage.pin[b][c0:c1].numpy(), as_u8(a[lo + c0:lo + c1]))
-                    stage.dev[b][c0:c1].copy_(stage.pin[b][c0:c1], non_blocking=True)
+                    if packed:
+                        np.copyto(stage.pin_packed[b][c0:c1].numpy(), rows_packed[lo + c0:lo + c1, byte_lo:byte_hi])
+                        stage.dev_packed[b][c0:c1].copy_(stage.pin_packed[b][c0:c1], non_blocking=True)
+                        unpack_b8_into(stage.dev_packed[b][c0:c1], bit_lo, ndet, stage.dev[b][c0:c1], stream=stage.copy)
+                    else:
+                        np.copyto(stage.pin[b][c0:c1].numpy(), as_u8(a[lo + c0:lo + c1]))
+                        stage.dev[b][c0:c1].copy_(stage.pin[b][c0:c1], non_blocking=True)
                     ready.append(torch.cuda.Event())
                     ready[-1].record(stage.copy)
             h2d_done[b] = ready[-1]

@@ -172,19 +172,26 @@ class DeviceWindowPlan:
         return pred
 
     def decode_host(self, zcheck_samples):
-        """The reference call's data path: host samples [N, ndet] (bool / uint8 / any integer numpy array, or a torch tensor)
+        """The reference call's data path: host samples [N, ndet] (bool / uint8 / any integer numpy array, a torch tensor, or
+        quits_amd.samples.PackedSamples on either side)
         -> int64 numpy [N, nobs] (reference sliding_window.py:160,186).  Host arrays are streamed: pieces of `self.host_piece`
         shots go through two pinned staging buffers and a copy stream, so that the host-side copy and the PCIe transfer of one
         piece run beside the decoding of the previous one, and the predictions come back through a pinned buffer
         (pipeline.decode_host_samples).  Tensors that already live on the GPU skip the staging."""
         import torch
+        from ..samples import PackedSamples
         with self.in_use():
             dev = torch.device("cuda", self.device) if self.device >= 0 else torch.device("cuda")
-            if isinstance(zcheck_samples, torch.Tensor) and zcheck_samples.is_cuda:
-                if zcheck_samples.device != dev:
-                    raise RuntimeError("samples live on %s, the plan on %s" % (zcheck_samples.device, dev))
+            packed = isinstance(zcheck_samples, PackedSamples)
+            on_gpu = zcheck_samples.data if packed and zcheck_samples.is_cuda else zcheck_samples
+            if isinstance(on_gpu, torch.Tensor) and on_gpu.is_cuda:
+                if on_gpu.device != dev:
+                    raise RuntimeError("samples live on %s, the plan on %s" % (on_gpu.device, dev))
                 return self.decode(pipeline._to_device_samples(zcheck_samples)).cpu().numpy().astype(np.int64)
-            a = zcheck_samples.cpu().numpy() if isinstance(zcheck_samples, torch.Tensor) else np.asarray(zcheck_samples)
+            if packed:
+                a = zcheck_samples                                # (staged packed: pipeline.decode_host_samples)
+            else:
+                a = zcheck_samples.cpu().numpy() if isinstance(zcheck_samples, torch.Tensor) else np.asarray(zcheck_samples)
             if a.ndim != 2:
                 raise ValueError("zcheck_samples must be a [shots, detectors] array")
             if a.shape[0] == 0:

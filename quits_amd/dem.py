@@ -31,6 +31,7 @@ from __future__ import annotations
 import hashlib
 import math
 import os
+import re
 import threading
 from collections import OrderedDict
 from typing import Dict, List, Tuple
@@ -427,16 +428,201 @@ class Circuit(str):
 
 
 def as_dem(circuit) -> DetectorErrorModel:
-    """Accept a stim.Circuit (if Stim is installed), circuit text, a Circuit or a DEM-like object.
+    """Accept a stim.Circuit (if Stim is installed), circuit text, a Circuit, a DEM-like object or the text of a detector error model
+    (Stim's .dem grammar, `parse_dem`).
 
     A circuit is recognised by its `detector_error_model` method and asked for the DEM exactly as the reference does
     (`decoder/base.py:151`: `circuit.detector_error_model(decompose_errors=False)`); this has to be tested FIRST because a
     real stim.Circuit also carries `flattened()` and `num_detectors`.  Only an object without that method is taken for
     an already-built DEM (stim.DetectorErrorModel or the duck type `detector_error_model_to_matrix` reads)."""
     if isinstance(circuit, str):
-        return (circuit if isinstance(circuit, Circuit) else Circuit(circuit)).detector_error_model()
+        if isinstance(circuit, Circuit):
+            return circuit.detector_error_model()
+        if looks_like_dem_text(circuit):          # Stim's .dem text: no circuit starts with a detector-error-model instruction
+            return parse_dem(circuit)
+        return Circuit(circuit).detector_error_model()
     if hasattr(circuit, "detector_error_model"):
         return circuit.detector_error_model(decompose_errors=False)
     if hasattr(circuit, "flattened") and hasattr(circuit, "num_detectors"):
         return circuit
     raise TypeError("circuit must be a stim.Circuit, circuit text, quits_amd.dem.Circuit or a DEM")
+
+
+# ---- Stim's detector-error-model text (.dem) ---------------------------------------------------------------------------------------------
+class DemParseError(ValueError):
+    """Malformed detector-error-model text; the message names the line."""
+
+
+_DEM_INSTRUCTIONS = ("error", "detector", "logical_observable", "shift_detectors", "repeat")
+_DEM_HEAD = re.compile(r"\s*([A-Za-z_][A-Za-z_0-9]*)\s*(\[[^\]]*\])?\s*(\(([^)]*)\))?(.*)$")      # name [tag] (arguments) targets
+
+
+def _dem_code(line: str) -> str:
+    return line.split("#", 1)[0].strip()
+
+
+def looks_like_dem_text(text: str) -> bool:
+    """True if the first instruction of `text` (comments, blank lines and `repeat N {` heads skipped) is one of a detector error model:
+    `error(`, `detector` with D# targets, `logical_observable`, `shift_detectors`.  A circuit's DETECTOR names rec[-k] targets (or none)."""
+    for line in text.split("\n"):
+        code = _dem_code(line)
+        if not code or code == "}":
+            continue
+        m = _DEM_HEAD.match(code)
+        name = m.group(1).lower() if m else ""
+        if name == "repeat":
+            continue
+        if name == "detector":
+            return re.search(r"(^|\s)[Dd]\d+", m.group(5)) is not None
+        return name in _DEM_INSTRUCTIONS
+    return False
+
+
+def _dem_numbers(text, no, what):
+    out = []
+    for tok in (text or "").split(","):
+        tok = tok.strip()
+        if not tok and not (text or "").strip():
+            continue
+        try:
+            out.append(float(tok))
+        except ValueError:
+            raise DemParseError("line %d: bad %s %r" % (no, what, tok)) from None
+    return out
+
+
+def _dem_targets(rest, no, allow_obs=True, allow_det=True, separators=False):
+    dets, obs = [], []
+    for tok in rest.split():
+        if tok == "^":
+            if separators:
+                continue
+            raise DemParseError("line %d: '^' outside an error instruction" % no)
+        m = re.fullmatch(r"([DdLl])(\d+)", tok)
+        if not m:
+            raise DemParseError("line %d: bad target %r" % (no, tok))
+        if m.group(1) in "Dd":
+            if not allow_det:
+                raise DemParseError("line %d: detector target %s where an observable is expected" % (no, tok))
+            dets.append(int(m.group(2)))
+        else:
+            if not allow_obs:
+                raise DemParseError("line %d: observable target %s where a detector is expected" % (no, tok))
+            obs.append(int(m.group(2)))
+    return dets, obs
+
+
+def _odd(ids):
+    """The ids that occur an odd number of times, ascending: repeated targets cancel."""
+    seen = set()
+    for i in ids:
+        seen ^= {i}
+    return tuple(sorted(seen))
+
+
+def parse_dem(text: str) -> DetectorErrorModel:
+    """Stim's detector-error-model text -> the flat DetectorErrorModel: `repeat` blocks unrolled, `shift_detectors` applied (detector ids
+    are absolute), `^` separators dropped, targets repeated inside one error cancelled.  Instruction names are matched without regard to
+    case, as Stim matches them.  Zero-probability and empty-symptom mechanisms are kept; num_detectors / num_observables = 1 + the largest
+    id in any error, `detector` or `logical_observable` instruction.  DemParseError (a ValueError) names the offending line."""
+    root, stack = [], []            # a block is a list of ("error", p, dets, obs, largest obs) / ("detector", dets) / ("shift", k) / ("repeat", n, block)
+    cur = root
+    for no, line in enumerate(str(text).split("\n"), 1):
+        code = _dem_code(line)
+        if not code:
+            continue
+        if code == "}":
+            if not stack:
+                raise DemParseError("line %d: '}' without a repeat block" % no)
+            cur = stack.pop()[0]
+            continue
+        m = _DEM_HEAD.match(code)
+        if not m:
+            raise DemParseError("line %d: cannot read %r" % (no, code[:40]))
+        name, args, rest = m.group(1).lower(), m.group(4), m.group(5).strip()
+        if name == "repeat":
+            if m.group(3) or not rest.endswith("{"):
+                raise DemParseError("line %d: a block opens as 'repeat N {'" % no)
+            try:
+                count = int(rest[:-1].strip())
+            except ValueError:
+                raise DemParseError("line %d: bad repeat count %r" % (no, rest[:-1].strip())) from None
+            if count < 0:
+                raise DemParseError("line %d: negative repeat count" % no)
+            body = []
+            cur.append(("repeat", count, body))
+            stack.append((cur, no))
+            cur = body
+        elif name == "error":
+            nums = _dem_numbers(args, no, "probability")
+            if len(nums) != 1 or not 0.0 <= nums[0] <= 1.0:
+                raise DemParseError("line %d: error takes one probability in [0, 1], got (%s)" % (no, args if args is not None else ""))
+            dets, obs = _dem_targets(rest, no, separators=True)
+            cur.append(("error", nums[0], dets, _odd(obs), max(obs, default=-1)))
+        elif name == "detector":
+            _dem_numbers(args, no, "coordinate")
+            dets, _ = _dem_targets(rest, no, allow_obs=False)
+            cur.append(("detector", dets))
+        elif name == "logical_observable":
+            _dem_numbers(args, no, "argument")
+            _, obs = _dem_targets(rest, no, allow_det=False)
+            cur.append(("observable", obs))
+        elif name == "shift_detectors":
+            _dem_numbers(args, no, "coordinate")
+            toks = rest.split()
+            try:
+                k = int(toks[0]) if toks else 0
+            except ValueError:
+                k = -1
+            if len(toks) > 1 or k < 0:
+                raise DemParseError("line %d: shift_detectors takes one non-negative integer, got %r" % (no, rest))
+            cur.append(("shift", k))
+        else:
+            raise DemParseError("line %d: unknown instruction %r" % (no, m.group(1)))
+    if stack:
+        raise DemParseError("line %d: repeat block is never closed" % stack[-1][1])
+
+    errors: List[Tuple[float, Tuple[int, ...], Tuple[int, ...]]] = []
+    top = {"det": -1, "obs": -1, "shift": 0}
+
+    def run(block):
+        for item in block:
+            kind = item[0]
+            if kind == "error":
+                off = top["shift"]
+                dets = _odd(d + off for d in item[2])
+                if item[2]:
+                    top["det"] = max(top["det"], off + max(item[2]))
+                top["obs"] = max(top["obs"], item[4])
+                errors.append((item[1], dets, item[3]))
+            elif kind == "detector":
+                if item[1]:
+                    top["det"] = max(top["det"], top["shift"] + max(item[1]))
+            elif kind == "observable":
+                if item[1]:
+                    top["obs"] = max(top["obs"], max(item[1]))
+            elif kind == "shift":
+                top["shift"] += item[1]
+            else:
+                for _ in range(item[1]):
+                    run(item[2])
+
+    run(root)
+    return DetectorErrorModel(errors, top["det"] + 1, top["obs"] + 1)
+
+
+def dem_to_text(dem, digits: int = 17) -> str:
+    """The `error(p) D# ... L# ...` lines of a flat DetectorErrorModel with p printed to `digits` significant digits (17 round-trips a double),
+    plus a `detector D{n-1}` / `logical_observable L{k-1}` line where the last id occurs in no error, so that parse_dem(dem_to_text(d)) has
+    d's sizes."""
+    fmt = "error(%%.%dg)" % int(digits)
+    lines, top_d, top_o = [], -1, -1
+    for p, dets, obs in dem.errors:
+        lines.append(" ".join([fmt % p] + ["D%d" % d for d in dets] + ["L%d" % o for o in obs]))
+        top_d = max(top_d, max(dets, default=-1))
+        top_o = max(top_o, max(obs, default=-1))
+    if dem.num_detectors - 1 > top_d:
+        lines.append("detector D%d" % (dem.num_detectors - 1))
+    if dem.num_observables - 1 > top_o:
+        lines.append("logical_observable L%d" % (dem.num_observables - 1))
+    return "\n".join(lines) + "\n"
