@@ -96,7 +96,7 @@ typedef struct qd_params {
     double ms_scaling_factor;   /* not exposed by the reference wrapper -> ldpc default 1.0; 0 = 1-2^-it */
 } qd_params;
 
-int qd_version(void);                 /* 109 (109: qd_unpack_b8, qd_pack_b8; 108: qd_shot_flags_fold, qd_tally_batch, qd_sample_circuit_shots, qd_sample_dem_shots; 107: off-chip windows decode, QD_FLAG_OFF_CHIP, QD_POST_OSD0_OFFCHIP, no new export; 106: qd_circuit_create accepts the biased-noise opcodes Y_ERROR / PAULI_CHANNEL_1 / PAULI_CHANNEL_2, no new export; 105: qd_decoder_fast_start; 104: qd_circuit_* + qd_sample_circuit; 103: qd_decoder_post_head_start; 101: qd_graph_info wrote 12 entries; 102: 10 again + qd_graph_info_ex) */
+int qd_version(void);                 /* 110 (110: qd_sample_dem_faults, qd_commit_bits, qd_fault_stats_batch; 109: qd_unpack_b8, qd_pack_b8; 108: qd_shot_flags_fold, qd_tally_batch, qd_sample_circuit_shots, qd_sample_dem_shots; 107: off-chip windows decode, QD_FLAG_OFF_CHIP, QD_POST_OSD0_OFFCHIP, no new export; 106: qd_circuit_create accepts the biased-noise opcodes Y_ERROR / PAULI_CHANNEL_1 / PAULI_CHANNEL_2, no new export; 105: qd_decoder_fast_start; 104: qd_circuit_* + qd_sample_circuit; 103: qd_decoder_post_head_start; 101: qd_graph_info wrote 12 entries; 102: 10 again + qd_graph_info_ex) */
 const char *qd_last_error(void);
 /* Number of visible HIP devices (0 if none): lets a host fail loudly before building anything. */
 int qd_device_count(void);
@@ -287,6 +287,41 @@ int qd_sample_dem(const qd_spmat *Ht, const qd_spmat *Lt, const double *priors, 
  * (`sampler.sample(shots)[0][indices]`, simulation.py:23-27 -- Stim can only draw a whole range again); B <= 2^31 - 1. */
 int qd_sample_dem_shots(const qd_spmat *Ht, const qd_spmat *Lt, const double *priors, uint64_t seed, const int64_t *d_shots, int64_t B,
                         uint8_t *d_det, int64_t det_stride, uint8_t *d_obs, int64_t obs_stride, void *stream);
+
+/* The same again -- qd_sample_dem where d_shots is NULL (shots shot0 .. shot0 + B - 1), qd_sample_dem_shots otherwise, the same Philox stream and
+ * the same d_det / d_obs -- and WHICH faults fired: bit (j & 31) of word (j >> 5) of row b of d_fault_bits (fault_stride_words words per row) = 1
+ * iff fault j fired in row b's shot.  The padding bits of word ceil(n / 32) - 1 are 0; words of a row past it are not touched.  The bitmap is built in
+ * the kernel's LDS beside the detector and observable bits and streamed out in whole words; where the three exceed 64 KiB the row is zeroed
+ * and set in place with vector atomics, so n is not bounded.  Like its two siblings the call uploads its threshold table and waits for `stream`.
+ * No reference counterpart: Stim's detector sampler does not say which mechanisms fired. */
+int qd_sample_dem_faults(const qd_spmat *Ht, const qd_spmat *Lt, const double *priors, uint64_t seed, int64_t shot0, const int64_t *d_shots,
+                         int64_t B, uint8_t *d_det, int64_t det_stride, uint8_t *d_obs, int64_t obs_stride, uint32_t *d_fault_bits,
+                         int64_t fault_stride_words, void *stream);
+
+/* ---- fault-level outputs: the space-time correction of a sliding-window decode and what an experiment tallies of it.  The reference computes
+ *      a window's correction, keeps `window_observable_set[k] @ e` and `window_update[k] @ e` of it and drops it (sliding_window.py:171-183). */
+
+/* Bits [out_bit0, out_bit0 + nbits) of row b of d_out = bits [0, nbits) of row b of d_err_bits (qd_decode_batch's packed rows), b < B; every
+ * other bit of d_out keeps its value; nbits = 0 is a no-op.  One call per window, on the stream of that window's qd_gf2_spmv_batch, with
+ * nbits = the window's committed columns and out_bit0 = the columns committed before it, lays the windows' corrections end to end: ranges
+ * that share a word compose when the calls are stream-ordered (a boundary word is read, merged and written by one lane; no atomics).
+ * Stands in for concatenating `e[:ncommit]` over the windows of sliding_window.py:162-186, which the reference never does. */
+int qd_commit_bits(const uint32_t *d_err_bits, int64_t err_stride_words, int32_t nbits, int64_t B, uint32_t *d_out, int64_t out_stride_words,
+                   int64_t out_bit0, void *stream);
+
+/* Tallies of a decoded batch by fault weight.  E = row b of d_faults (qd_sample_dem_faults), C = row b of d_corr (qd_commit_bits), both nbits
+ * bits in rows of stride_words words; r = 1 iff row b of d_residual (m bytes, row stride res_stride: H C xor det, made by qd_gf2_spmv_batch with
+ * accumulate = 1 onto a copy of det) has a non-zero byte; "failing" = bit b of d_fail_mask (qd_tally_batch's mask of the same batch).
+ *   d_hist (int64 [3][QD_FAULT_HIST], accumulated): [0][min(|E|, 255)] += 1 for every shot, [1][min(|E|, 255)] += 1 for every failing shot,
+ *     [2][min(|E xor C|, 255)] += 1 for every failing shot with r = 0 -- there E xor C is an undetectable logical fault;
+ *   d_counts (int64 [4], accumulated): shots, failing shots, shots with r = 1, failing shots with r = 1;
+ *   d_best (uint64, initialised to all ones by the caller): the minimum of (|E xor C| << 40) | (shot0 + b) over the failing shots with r = 0:
+ *     the lightest such residual and the shot that certifies it (shot0 + B <= 2^40).
+ * One launch; the number of global atomics does not depend on B.  No reference counterpart. */
+#define QD_FAULT_HIST 256
+int qd_fault_stats_batch(const uint32_t *d_faults, const uint32_t *d_corr, int64_t stride_words, int32_t nbits, const uint8_t *d_residual,
+                         int64_t res_stride, int32_t m, const uint64_t *d_fail_mask, int64_t B, int64_t shot0, int64_t *d_hist,
+                         int64_t *d_counts, uint64_t *d_best, void *stream);
 
 /* ---- circuit-level input: a Pauli-frame simulation of the circuit itself (what stim's compile_detector_sampler().sample(...,
  *      separate_observables=True) returns, simulation.py:8-28), without gauge randomisation: exact when every detector and observable

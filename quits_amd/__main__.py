@@ -5,6 +5,8 @@ know do (sinter / pymatching: --dem, --in, --in_format, --out, --out_format).
 
 Without --checks_per_round / --window / --commit the model is decoded over its whole history (quits_amd.decoder.decode_dem); with all three
 by the sliding-window decoder (quits_amd.decoder.sliding_window_bposd_circuit_mem), the detectors being rounds of --checks_per_round.
+--corrections_out FILE (--corrections_format b8 | 01 | hits, default b8) also writes every shot's correction, one bit per fault of the model
+in the column order of detector_error_model_to_matrix (quits_amd.decoder.sliding_window_corrections / decode_dem_corrections).
 Exit status: 0 done, 1 unreadable input, 2 bad arguments, or no GPU / no library (the decoder has no CPU fallback).
 """
 from __future__ import annotations
@@ -41,6 +43,9 @@ def _parser():
     p.add_argument("--checks_per_round", type=int, metavar="NZ", help="detectors per round (sliding window; with --window and --commit)")
     p.add_argument("--window", type=int, metavar="W", help="rounds per window")
     p.add_argument("--commit", type=int, metavar="F", help="rounds committed per window")
+    p.add_argument("--corrections_out", metavar="FILE",
+                   help="also write every shot's correction, one bit per fault of the model (the columns of detector_error_model_to_matrix)")
+    p.add_argument("--corrections_format", choices=("b8", "01", "hits"), default="b8")
     return ap
 
 
@@ -69,17 +74,20 @@ def predict(args, ap) -> int:
     opts = dict(max_iter=args.max_iter, osd_order=args.osd_order, bp_method=args.bp_method, schedule=args.schedule, osd_method=args.osd_method)
     if args.window is not None:
         import warnings
-        from .decoder import sliding_window_bposd_circuit_mem
+        from .decoder import sliding_window_bposd_circuit_mem, sliding_window_corrections
         nz = args.checks_per_round
         if ndet % nz:
             raise ValueError("the model's %d detectors are not whole rounds of %d" % (ndet, nz))
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")           # (whole-history notice of the reference: not an error here)
-            pred = sliding_window_bposd_circuit_mem(det, model, np.zeros((nz, 1), np.uint8), np.zeros((nobs, 1), np.uint8),
-                                                    args.window, args.commit, **opts)
+            decode = sliding_window_corrections if args.corrections_out else sliding_window_bposd_circuit_mem
+            pred = decode(det, model, np.zeros((nz, 1), np.uint8), np.zeros((nobs, 1), np.uint8), args.window, args.commit, **opts)
     else:
-        from .decoder import decode_dem
-        pred = decode_dem(model, det, **opts)
+        from .decoder import decode_dem, decode_dem_corrections
+        pred = (decode_dem_corrections if args.corrections_out else decode_dem)(model, det, **opts)
+    if args.corrections_out:
+        pred, corrections = pred
+        write_shots(args.corrections_out, corrections, args.corrections_format)
     write_shots(args.out, pred.astype(np.uint8), args.out_format, num_detectors=0)
     if actual is not None:
         import torch

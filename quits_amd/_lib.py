@@ -26,6 +26,7 @@ STATUS_ZERO = 1 << 19
 SHOT_POST, SHOT_INCONSISTENT, SHOT_INEXACT, SHOT_COARSE = 1, 2, 4, 8     # QD_SHOT_*: the flag byte qd_shot_flags_fold keeps per shot
 SHOT_FLAG_NAMES = ("post", "inconsistent", "inexact", "coarse")         # ... bit j <-> name j
 TALLY_HEAD = 10                                                         # QD_TALLY_HEAD
+FAULT_HIST = 256                                                        # QD_FAULT_HIST
 
 
 class QdParams(C.Structure):
@@ -50,6 +51,7 @@ EXPORTS = [
     "qd_circuit_create", "qd_circuit_destroy", "qd_circuit_info", "qd_sample_circuit",
     "qd_shot_flags_fold", "qd_tally_batch", "qd_sample_circuit_shots", "qd_sample_dem_shots",
     "qd_unpack_b8", "qd_pack_b8",
+    "qd_sample_dem_faults", "qd_commit_bits", "qd_fault_stats_batch",
 ]
 
 
@@ -122,6 +124,10 @@ def load():
     if hasattr(L, "qd_unpack_b8"):                  # (library version 109; an older library named by QUITS_AMD_LIB takes unpacked samples as before)
         L.qd_unpack_b8.argtypes = [vp, i64, i64, i32, i64, vp, i64, vp]
         L.qd_pack_b8.argtypes = [vp, i64, i32, i64, vp, i64, vp]
+    if hasattr(L, "qd_commit_bits"):                # (library version 110; an older library named by QUITS_AMD_LIB returns logical predictions as before)
+        L.qd_sample_dem_faults.argtypes = [vp, vp, vp, u64, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
+        L.qd_commit_bits.argtypes = [vp, i64, i32, i64, vp, i64, i64, vp]
+        L.qd_fault_stats_batch.argtypes = [vp, vp, i64, i32, vp, i64, i32, vp, i64, i64, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -142,6 +148,13 @@ def require_bitpack(L):
     """The entry points of library version 109 (bit-packed samples): a clear error from an older library."""
     if not hasattr(L, "qd_unpack_b8"):
         raise RuntimeError("quits_amd: %s is version %d; bit-packed samples need >= 109 -- rebuild it" % (LIB_PATH, L.qd_version()))
+    return L
+
+
+def require_faults(L):
+    """The entry points of library version 110 (sampled faults, committed corrections, fault statistics): a clear error from an older library."""
+    if not hasattr(L, "qd_commit_bits"):
+        raise RuntimeError("quits_amd: %s is version %d; fault-level outputs need >= 110 -- rebuild it" % (LIB_PATH, L.qd_version()))
     return L
 
 

@@ -1,6 +1,7 @@
 // gf2_kernels.hip -- the byte/bit plumbing around the decoder: window hand-off, unpacking, counting, sampling.
 #include "qd_internal.h"
 #include "qd_host.h"
+#include "sample_dem_kernel.h"
 
 // out[b][r] (^)= parity(row r of A AND e_b).  Replaces `window_observable_set[k] @ e % 2` and
 // `window_update[k] @ e % 2` (quits/decoder/sliding_window.py:172,174,183).  CPU restatement: the L/U loops of
@@ -82,46 +83,7 @@ __global__ void qd_count_mismatch_kernel(const uint8_t *__restrict__ pred, const
     if ((threadIdx.x & 63) == 0 && bal) atomicAdd(count, (unsigned long long)__popcll(bal));
 }
 
-// ---- DEM sampler (stands in for stim's detector sampler, quits/simulation.py:23-27).  Same integer recipe as
-// oq_sample_dem (oracle/qd_oracle.c): Philox4x32-10, key = seed, counter = (shot lo, shot hi, j / 4, 0); word j & 3
-// fires fault j iff it is < floor(p_j * 2^32) (qd_philox4x32_10: qd_internal.h).  One workgroup per shot, detector/observable bits accumulated in LDS.
-__global__ void qd_sample_dem_kernel(SpmatDev Ht, SpmatDev Lt, const uint32_t *__restrict__ thr, uint32_t k0,
-                                     uint32_t k1, int64_t shot0, const int64_t *__restrict__ shot_list, int m, int nobs, uint8_t *det,
-                                     int64_t det_stride, uint8_t *obs, int64_t obs_stride)
-{
-    extern __shared__ __align__(16) unsigned char smem[];
-    uint32_t *dbits = reinterpret_cast<uint32_t *>(smem);
-    const int dwords = (m + 31) >> 5, owords = (nobs + 31) >> 5;
-    uint32_t *obits = dbits + dwords;
-    const int tid = threadIdx.x, T = blockDim.x;
-    const int64_t b = blockIdx.x;
-    const uint64_t shot = (uint64_t)(shot_list ? shot_list[b] : shot0 + b);     // (qd_sample_dem_shots: row b is shot shot_list[b])
-    for (int w = tid; w < dwords + owords; w += T) dbits[w] = 0u;
-    __syncthreads();
-    const int n = Ht.nrows;
-    for (int c = tid; 4 * c < n; c += T) {
-        uint32_t r[4];
-        qd_philox4x32_10((uint32_t)shot, (uint32_t)(shot >> 32), (uint32_t)c, 0u, k0, k1, r);
-#pragma unroll
-        for (int x = 0; x < 4; ++x) {
-            const int j = 4 * c + x;
-            if (j < n && r[x] < thr[j]) {
-                for (uint32_t e = Ht.row_ptr[j]; e < Ht.row_ptr[j + 1]; ++e) {
-                    const uint32_t d = Ht.col_idx[e];
-                    atomicXor(&dbits[d >> 5], 1u << (d & 31u));
-                }
-                for (uint32_t e = Lt.row_ptr[j]; e < Lt.row_ptr[j + 1]; ++e) {
-                    const uint32_t o = Lt.col_idx[e];
-                    atomicXor(&obits[o >> 5], 1u << (o & 31u));
-                }
-            }
-        }
-    }
-    __syncthreads();
-    for (int i = tid; i < m; i += T) det[b * det_stride + i] = (uint8_t)((dbits[i >> 5] >> (i & 31)) & 1u);
-    for (int i = tid; i < nobs; i += T) obs[b * obs_stride + i] = (uint8_t)((obits[i >> 5] >> (i & 31)) & 1u);
-}
-
+// ---- DEM sampler: the kernel is in sample_dem_kernel.h (this file launches it without the fault bitmap, faults.hip with it)
 // Stage caller-supplied LLRs (fault order) as if the BP kernel had published them: slot order rows, identity fail list.
 __global__ void qd_stage_llr_kernel(const float *__restrict__ llr_in, int n, int n_pad, const uint32_t *__restrict__ bit_orig,
                                     int64_t B, float *llr_ws, int32_t *fail_list, int32_t *fail_count, int32_t *status)
@@ -200,7 +162,7 @@ hipError_t qd_launch_sample(const SpmatDev &Ht, const SpmatDev &Lt, const uint32
 {
     if (B == 0) return hipSuccess;
     const size_t lds = sizeof(uint32_t) * (size_t)(((m + 31) >> 5) + ((nobs + 31) >> 5));
-    hipLaunchKernelGGL(qd_sample_dem_kernel, dim3((unsigned)B), dim3(256), lds, s, Ht, Lt, thr, (uint32_t)seed,
-                       (uint32_t)(seed >> 32), shot0, shot_list, m, nobs, det, det_stride, obs, obs_stride);
+    hipLaunchKernelGGL(qd_sample_dem_kernel<0>, dim3((unsigned)B), dim3(256), lds, s, Ht, Lt, thr, (uint32_t)seed,
+                       (uint32_t)(seed >> 32), shot0, shot_list, m, nobs, det, det_stride, obs, obs_stride, nullptr, (int64_t)0);
     return hipGetLastError();
 }

@@ -192,6 +192,19 @@ hipError_t qd_launch_count(const uint8_t *pred, const uint8_t *obs, int k, int64
 hipError_t qd_launch_sample(const SpmatDev &Ht, const SpmatDev &Lt, const uint32_t *thr, uint64_t seed, int64_t shot0,
                             const int64_t *shot_list, int64_t B, int m, int nobs, uint8_t *det, int64_t det_stride, uint8_t *obs,
                             int64_t obs_stride, hipStream_t s);
+#define QD_SAMPLE_LDS_MAX (64 * 1024)   // the DEM sampler's LDS: detector and observable bits, and the fault bitmap where it still fits (else a global row)
+// qd_sample.hip: qd_sample_dem / qd_sample_dem_shots / qd_sample_dem_faults (d_fault_bits == nullptr: the faults are not kept)
+int qd_sample_dem_impl(const qd_spmat *Ht, const qd_spmat *Lt, const double *priors, uint64_t seed, int64_t shot0, const int64_t *d_shots,
+                       int64_t B, uint8_t *d_det, int64_t det_stride, uint8_t *d_obs, int64_t obs_stride, uint32_t *d_fault_bits,
+                       int64_t fault_stride_words, void *stream);
+// faults.hip: the sampler with its fault bitmap, committed corrections and the fault statistics of a memory experiment
+hipError_t qd_launch_sample_faults(const SpmatDev &Ht, const SpmatDev &Lt, const uint32_t *thr, uint64_t seed, int64_t shot0,
+                                   const int64_t *shot_list, int64_t B, int m, int nobs, uint8_t *det, int64_t det_stride, uint8_t *obs,
+                                   int64_t obs_stride, uint32_t *fault_bits, int64_t fault_stride, hipStream_t s);
+hipError_t qd_launch_commit_bits(const uint32_t *err, int64_t err_stride, int nbits, int64_t B, uint32_t *out, int64_t out_stride, int64_t out_bit0,
+                                 hipStream_t s);
+hipError_t qd_launch_fault_stats(const uint32_t *faults, const uint32_t *corr, int64_t stride, int nbits, const uint8_t *residual, int64_t res_stride,
+                                 int m, const uint64_t *fail_mask, int64_t B, int64_t shot0, int64_t *hist, int64_t *counts, uint64_t *best, hipStream_t s);
 // experiment.hip: the flag byte per shot and the tallies of a memory experiment
 hipError_t qd_launch_shot_flags(const int32_t *status, int64_t B, uint8_t *flags, hipStream_t s);
 hipError_t qd_launch_tally(const uint8_t *pred, int64_t pred_stride, const uint8_t *obs, int64_t obs_stride, int k, int64_t B,

@@ -70,14 +70,16 @@ extern "C" int qd_count_mismatch(const uint8_t *d_pred, const uint8_t *d_obs, in
 }
 
 // qd_sample_dem (d_shots == nullptr: shots shot0 .. shot0 + B - 1) and qd_sample_dem_shots (row b = shot d_shots[b])
-static int sample_dem_impl(const qd_spmat *Ht, const qd_spmat *Lt, const double *priors, uint64_t seed, int64_t shot0, const int64_t *d_shots,
-                           int64_t B, uint8_t *d_det, int64_t det_stride, uint8_t *d_obs, int64_t obs_stride, void *stream)
+int qd_sample_dem_impl(const qd_spmat *Ht, const qd_spmat *Lt, const double *priors, uint64_t seed, int64_t shot0, const int64_t *d_shots,
+                       int64_t B, uint8_t *d_det, int64_t det_stride, uint8_t *d_obs, int64_t obs_stride, uint32_t *d_fault_bits,
+                       int64_t fault_stride_words, void *stream)
 {
     if (!Ht || !Lt || !priors || !d_det || !d_obs) return qd_fail(QD_EINVAL, "null argument");
     if (Ht->d.nrows != Lt->d.nrows) return qd_fail(QD_EINVAL, "Ht and Lt must both have one row per fault");
     const int n = Ht->d.nrows, m = Ht->d.ncols, nobs = Lt->d.ncols;
     if (det_stride < m || obs_stride < nobs) return qd_fail(QD_EINVAL, "output strides too small");
-    if (((m + 31) / 32 + (nobs + 31) / 32) * 4 > 64 * 1024) return qd_fail(QD_ECAPACITY, "too many detectors for the sampler's LDS bit array");
+    if (d_fault_bits && fault_stride_words * 32 < n) return qd_fail(QD_EINVAL, "fault rows hold %lld bits, the model has %d faults", (long long)fault_stride_words * 32, n);
+    if (((m + 31) / 32 + (nobs + 31) / 32) * 4 > QD_SAMPLE_LDS_MAX) return qd_fail(QD_ECAPACITY, "too many detectors for the sampler's LDS bit array");
     HIP_TRY(hipSetDevice(Ht->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     std::vector<uint32_t> thr((size_t)n);
@@ -88,7 +90,10 @@ static int sample_dem_impl(const qd_spmat *Ht, const qd_spmat *Lt, const double 
     uint32_t *d_thr = nullptr;
     HIP_TRY(hipMalloc((void **)&d_thr, sizeof(uint32_t) * (size_t)std::max(n, 4)));
     hipError_t e = hipMemcpy(d_thr, thr.data(), sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = qd_launch_sample(Ht->d, Lt->d, d_thr, seed, shot0, d_shots, B, m, nobs, d_det, det_stride, d_obs, obs_stride, s);
+    if (e == hipSuccess)
+        e = d_fault_bits ? qd_launch_sample_faults(Ht->d, Lt->d, d_thr, seed, shot0, d_shots, B, m, nobs, d_det, det_stride, d_obs, obs_stride, d_fault_bits,
+                                                   fault_stride_words, s)
+                         : qd_launch_sample(Ht->d, Lt->d, d_thr, seed, shot0, d_shots, B, m, nobs, d_det, det_stride, d_obs, obs_stride, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     (void)hipFree(d_thr);
     if (e != hipSuccess) return qd_fail(QD_EHIP, "sampler: %s", hipGetErrorString(e));
@@ -99,7 +104,7 @@ extern "C" int qd_sample_dem(const qd_spmat *Ht, const qd_spmat *Lt, const doubl
                              int64_t B, uint8_t *d_det, int64_t det_stride, uint8_t *d_obs, int64_t obs_stride,
                              void *stream)
 {
-    return sample_dem_impl(Ht, Lt, priors, seed, shot0, nullptr, B, d_det, det_stride, d_obs, obs_stride, stream);
+    return qd_sample_dem_impl(Ht, Lt, priors, seed, shot0, nullptr, B, d_det, det_stride, d_obs, obs_stride, nullptr, 0, stream);
 }
 
 extern "C" int qd_sample_dem_shots(const qd_spmat *Ht, const qd_spmat *Lt, const double *priors, uint64_t seed, const int64_t *d_shots,
@@ -108,7 +113,7 @@ extern "C" int qd_sample_dem_shots(const qd_spmat *Ht, const qd_spmat *Lt, const
     if (B == 0) return QD_OK;
     if (B < 0 || B > INT32_MAX) return qd_fail(QD_EINVAL, "bad shot count (one workgroup per shot: at most 2^31 - 1 in one call)");
     if (!d_shots) return qd_fail(QD_EINVAL, "null shot list");
-    return sample_dem_impl(Ht, Lt, priors, seed, 0, d_shots, B, d_det, det_stride, d_obs, obs_stride, stream);
+    return qd_sample_dem_impl(Ht, Lt, priors, seed, 0, d_shots, B, d_det, det_stride, d_obs, obs_stride, nullptr, 0, stream);
 }
 
 // ---- circuit-level sampler (frame_sampler.hip): the program comes from quits_amd/frame.py; everything the kernel indexes with is

@@ -5,6 +5,7 @@ from .sliding_window import sliding_window_circuit_mem, sliding_window_phenom_me
 from .bposd import BpOsdDecoder, sliding_window_bposd_circuit_mem, sliding_window_bposd_phenom_mem
 from .bplsd import BpLsdDecoder, sliding_window_bplsd_circuit_mem, sliding_window_bplsd_phenom_mem
 from .whole_history import decode_dem
+from .corrections import decode_dem_corrections, sliding_window_corrections
 
 __all__ = [
     "dict_to_csc_matrix_column_row",
@@ -20,4 +21,6 @@ __all__ = [
     "BpOsdDecoder",
     "BpLsdDecoder",
     "decode_dem",              # beyond the reference's names: any detector error model over its whole history (whole_history.py)
+    "sliding_window_corrections",   # ... and the corrections themselves next to the predictions (corrections.py)
+    "decode_dem_corrections",
 ]

@@ -193,6 +193,19 @@ def spacetime(circuit, hz, W, F, num_cor_rounds):
     return checks, observables, prior_sets, updates
 
 
+def commit_ranges(window_observable_set):
+    """[(col0, ncommit), ...]: where window k's committed columns lie among the faults of the whole model -- the running sum of the widths
+    of `spacetime`'s observable matrices (window k commits its first ncommit columns, the last window all of its columns).  The ranges
+    partition [0, number of faults): laid end to end the committed parts of the windows' corrections are one space-time correction (the
+    reference computes each part and drops it, sliding_window.py:171-183)."""
+    out, col0 = [], 0
+    for Lk in window_observable_set:
+        ncommit = int(Lk.shape[1])
+        out.append((col0, ncommit))
+        col0 += ncommit
+    return out
+
+
 def window_support_report(check: csc_matrix, nz: int, W: int, F: int, num_cor_rounds: int) -> dict:
     """The reference's slicing silently assumes time-ordered columns.  Report what it would
     lose: committed columns with support before the window or beyond the carried round, and columns never
@@ -234,4 +247,5 @@ __all__ = [
     "dict_to_csc_matrix_row_column",
     "detector_error_model_to_matrix",
     "spacetime",
+    "commit_ranges",
 ]

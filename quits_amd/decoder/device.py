@@ -277,6 +277,65 @@ class Tally:
         return self.data.cpu().numpy()
 
 
+def commit_bits(err_bits, nbits: int, out, out_bit0: int, stream=None):
+    """Bits [out_bit0, out_bit0 + nbits) of every row of `out` = bits [0, nbits) of the same row of `err_bits` (qd_commit_bits); the other bits of
+    `out` stay.  cuda int32 [B, words] tensors with unit stride inside a row.  Asynchronous on `stream` (default: the current one)."""
+    torch = _torch()
+    L = _lib.require_faults(_lib.load())
+    assert err_bits.is_cuda and out.is_cuda and err_bits.dtype == torch.int32 and out.dtype == torch.int32
+    assert err_bits.dim() == 2 and out.dim() == 2 and err_bits.shape[0] == out.shape[0]
+    assert (err_bits.shape[1] <= 1 or err_bits.stride(1) == 1) and (out.shape[1] <= 1 or out.stride(1) == 1)
+    B = out.shape[0]
+    es = err_bits.stride(0) if B > 1 else max(err_bits.stride(0), err_bits.shape[1])
+    os_ = out.stride(0) if B > 1 else max(out.stride(0), out.shape[1])
+    if 32 * err_bits.shape[1] < nbits or 32 * out.shape[1] < out_bit0 + nbits:
+        raise ValueError("rows of %d / %d words cannot hold %d bits / bits %d .. %d" % (err_bits.shape[1], out.shape[1], nbits, out_bit0, out_bit0 + nbits - 1))
+    sp = _stream_ptr() if stream is None else C.c_void_p(stream.cuda_stream)
+    _lib.check(L.qd_commit_bits(_ptr(err_bits), es, int(nbits), B, _ptr(out), os_, int(out_bit0), sp))
+    return out
+
+
+class FaultStats:
+    """Tallies of a memory experiment by fault weight, on the device (qd_fault_stats_batch): shots and failing shots by the number of sampled
+    faults, the failing shots whose correction reproduces the syndrome by the weight of E xor C, the lightest of those and its shot.  `add`
+    accumulates and returns nothing to the host; `result` does."""
+
+    def __init__(self, device=None):
+        torch = _torch()
+        self._L = _lib.require_faults(_lib.require_gpu())
+        dev = "cuda" if device is None else device
+        self.hist = torch.zeros((3, _lib.FAULT_HIST), dtype=torch.int64, device=dev)
+        self.counts = torch.zeros((4,), dtype=torch.int64, device=dev)
+        self.best = torch.full((1,), -1, dtype=torch.int64, device=dev)          # all ones: no failing shot with a zero residual yet
+
+    def add(self, faults, corr, nbits: int, residual, fail_mask, shot0: int = 0):
+        """faults, corr: cuda int32 [B, words] of the same row stride, nbits bits each; residual: cuda uint8 [B, m] (H C xor det); fail_mask: cuda
+        int64 [>= ceil(B / 64)], Tally.add's mask of the same batch; shot0: the global index of row 0."""
+        torch = _torch()
+        for t in (faults, corr):
+            assert t.is_cuda and t.dtype == torch.int32 and t.dim() == 2 and (t.shape[1] <= 1 or t.stride(1) == 1)
+        B = faults.shape[0]
+        assert corr.shape[0] == B and residual.shape[0] == B
+        if B == 0:
+            return
+        stride = faults.stride(0) if B > 1 else min(faults.shape[1], corr.shape[1])
+        assert B == 1 or corr.stride(0) == stride, "faults and corrections must share a row stride"
+        assert 32 * min(faults.shape[1], corr.shape[1]) >= nbits
+        assert residual.is_cuda and residual.dtype == torch.uint8 and residual.dim() == 2 and (residual.shape[1] <= 1 or residual.stride(1) == 1)
+        assert fail_mask.is_cuda and fail_mask.dtype == torch.int64 and fail_mask.dim() == 1 and fail_mask.is_contiguous()
+        assert fail_mask.shape[0] >= (B + 63) // 64
+        m = residual.shape[1]
+        rs = residual.stride(0) if B > 1 else max(residual.stride(0), m)
+        _lib.check(self._L.qd_fault_stats_batch(_ptr(faults), _ptr(corr), stride, int(nbits), _ptr(residual), rs, m, _ptr(fail_mask), B, int(shot0),
+                                                _ptr(self.hist), _ptr(self.counts), _ptr(self.best), _stream_ptr()))
+
+    def result(self):
+        """(hist int64 [3, 256], counts int64 [4], lightest) on the host (synchronises); lightest = (weight, shot) or None."""
+        best = int(self.best.cpu().numpy().view(np.uint64)[0])
+        lightest = None if best == 2 ** 64 - 1 else (best >> 40, best & ((1 << 40) - 1))
+        return self.hist.cpu().numpy(), self.counts.cpu().numpy(), lightest
+
+
 def _shot_indices(indices):
     """int64 cuda tensor of shot indices from a tensor or any integer sequence."""
     torch = _torch()
@@ -335,6 +394,38 @@ class DemSampler:
         _lib.check(L.qd_sample_dem_shots(self.Ht._h, self.Lt._h, self.priors.ctypes.data_as(C.c_void_p), C.c_uint64(int(seed) & (2 ** 64 - 1)),
                                          _ptr(idx), n, _ptr(det), det.stride(0), _ptr(obs), obs.stride(0), _stream_ptr()))
         return det, obs
+
+
+    @property
+    def nfaults(self) -> int:
+        return self.Ht.shape[0]
+
+    def _sample_with_faults(self, idx, shots, seed, shot0, fault_bits):
+        torch = _torch()
+        L = _lib.require_faults(self.Ht._L)
+        words = (self.nfaults + 31) // 32
+        det = torch.empty((shots, self.m), dtype=torch.uint8, device="cuda")
+        obs = torch.empty((shots, self.nobs), dtype=torch.uint8, device="cuda")
+        if fault_bits is None:
+            fault_bits = torch.empty((shots, words), dtype=torch.int32, device="cuda")
+        assert fault_bits.is_cuda and fault_bits.dtype == torch.int32 and fault_bits.dim() == 2 and fault_bits.shape[0] == shots
+        assert fault_bits.shape[1] >= words and (fault_bits.shape[1] <= 1 or fault_bits.stride(1) == 1)
+        fs = fault_bits.stride(0) if shots > 1 else max(fault_bits.stride(0), fault_bits.shape[1])
+        _lib.check(L.qd_sample_dem_faults(self.Ht._h, self.Lt._h, self.priors.ctypes.data_as(C.c_void_p), C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                          int(shot0), C.c_void_p(0) if idx is None else _ptr(idx), shots, _ptr(det), det.stride(0), _ptr(obs),
+                                          obs.stride(0), _ptr(fault_bits), fs, _stream_ptr()))
+        return det, obs, fault_bits
+
+    def sample_faults(self, shots: int, seed: int, shot0: int = 0, fault_bits=None):
+        """`sample` and which faults fired (qd_sample_dem_faults): (det, obs, fault_bits), fault_bits a cuda int32 [shots, ceil(n / 32)] tensor,
+        bit j & 31 of word j >> 5 = fault j (a column of the check matrix) fired.  Same random stream: det and obs are `sample`'s.
+        fault_bits: rows to write into instead (they may be wider; the words past ceil(n / 32) are left alone)."""
+        return self._sample_with_faults(None, int(shots), seed, shot0, fault_bits)
+
+    def sample_shots_faults(self, indices, seed: int, fault_bits=None):
+        """`sample_shots` and which faults fired: row b is what `sample_faults(1, seed, shot0=indices[b])` returns."""
+        idx = _shot_indices(indices)
+        return self._sample_with_faults(idx, int(idx.shape[0]), seed, 0, fault_bits)
 
 
 class CircuitSampler:

@@ -26,6 +26,14 @@ def _to_device_samples(zcheck_samples):
     return torch.from_numpy(np.ascontiguousarray(a)).to("cuda")
 
 
+def correction_words_to_packed(words, nfaults):
+    """int32 numpy [N, >= ceil(nfaults / 32)] of correction words -> host PackedSamples of nfaults bits: the library's little-endian words are
+    Stim's b8 bytes as they are (bit j of a shot is bit j & 7 of byte j >> 3)."""
+    from ..samples import PackedSamples
+    w = np.ascontiguousarray(words).astype("<i4", copy=False)
+    return PackedSamples(w.view(np.uint8).reshape(w.shape[0], 4 * w.shape[1])[:, :max((nfaults + 7) // 8, 0)], nfaults)
+
+
 def lane_groups(nchunks, lanes):
     """Chunks of a call dealt to groups of at most `lanes`, as few groups as possible and as even as they come: 4 chunks on three lanes are 2 + 2,
     not 3 + 1 (a chunk alone overlaps nothing), 16 on three are 3 + 3 + 3 + 3 + 2 + 2."""
@@ -68,7 +76,7 @@ class TwoStreams:
         self.s_post.synchronize()
 
 
-def decode_pipelined(plan, det, stats, ready=None):
+def decode_pipelined(plan, det, stats, ready=None, correction=None):
     """Calls of two or more chunks: the BP stages run on one side stream, the post-processing (OSD / LSD over the shots BP
     parked, acc ^= L e, the hand-off U e) on a second one, so that a chunk's post-processing runs beside the BP of the other
     chunks of its group -- the post-processors are chains of dependent steps that leave most issue slots of a CU idle, BP fills
@@ -87,7 +95,10 @@ def decode_pipelined(plan, det, stats, ready=None):
     the caller opened with plan.two_streams(device).begin(...): the lanes carry over from the call before, so that the BP stream of piece
     i + 1 starts behind its INPUT and the lanes, not behind piece i's last post stage.  The caller's stream is not made to wait at all and
     the result is not joined: the caller queues what it wants behind the post stream, synchronises the side streams itself when it has
-    queued everything, and then calls end() (profiles/r06_host_chain_ab.txt)."""
+    queued everything, and then calls end() (profiles/r06_host_chain_ab.txt).
+
+    `correction`: DeviceWindowPlan.decode's; zero-filled on the caller's stream ahead of the side streams' start, then every window's
+    committed bits are laid into it on the post stream, behind that window's acc ^= L e."""
     import torch
     lane_decs = plan.lane_decoders()
     ts = plan.two_streams(det.device)
@@ -95,6 +106,10 @@ def decode_pipelined(plan, det, stats, ready=None):
     N, C, NL = det.shape[0], plan.chunk, int(plan.lanes)
     cur = torch.cuda.current_stream()
     pred = torch.zeros((N, plan.nobs), dtype=torch.uint8, device=det.device)
+    if correction is not None:
+        from .device import commit_bits
+        plan.check_correction(correction, N, det.device)
+        correction.zero_()
     if ready is None:
         ts.begin(plan, det.device, N if stats is not None else None)
     else:
@@ -129,6 +144,8 @@ def decode_pipelined(plan, det, stats, ready=None):
                     s_post.wait_event(bp_done)
                     d.decode(chunk, w["row0"], upd, err_bits=err, status=st, stage=2, stream=s_post)
                     w["L"].xor_apply(err, acc, accumulate=True, stream=s_post)
+                    if correction is not None:
+                        commit_bits(err, w["ncommit"], correction[c0:c0 + C], w["col0"], stream=s_post)
                     if w["U"] is not None:
                         w["U"].xor_apply(err, ts.upd[lane][:B], accumulate=False, stream=s_post)
                     post_done[lane] = torch.cuda.Event()
@@ -158,6 +175,14 @@ class HostStaging:
         self.copy = torch.cuda.Stream(device=device)
         self.pin = self.dev = self.out = None
         self.pin_packed = self.dev_packed = None               # bit-packed rows on their way to `dev` (PackedSamples input)
+        self.corr = self.corr_out = None                       # corrections wanted: two device buffers of correction words, the pinned output
+
+    def fit_corrections(self, rows, shots, words):
+        import torch
+        if self.corr is None or self.corr[0].shape[1] != words or self.corr[0].shape[0] < rows:
+            self.corr = [torch.empty((rows, words), dtype=torch.int32, device=self.device) for _ in range(2)]
+        if self.corr_out is None or self.corr_out.shape[1] != words or self.corr_out.shape[0] < shots:
+            self.corr_out = torch.empty((shots, words), dtype=torch.int32, pin_memory=True)
 
     def fit(self, rows, ndet, shots, nobs, packed_bytes=0):
         """packed_bytes > 0: the host rows arrive bit-packed, that many bytes each: the pinned buffers (and their device copies) are cut for
@@ -177,11 +202,13 @@ class HostStaging:
             self.out = torch.empty((shots, nobs), dtype=torch.uint8, pin_memory=True)
 
 
-def decode_host_samples(plan, stage, a):
+def decode_host_samples(plan, stage, a, corrections=False):
     """a: numpy [N, ndet], N > 0, any integer dtype or bool  ->  int64 numpy [N, nobs], through `stage` (a HostStaging): pieces of
     `plan.host_piece` shots, rounded down to whole chunks, are copied chunk by chunk into a pinned buffer and on to the device on the copy
     stream, beside the decoding of the piece before.  `a` may be host PackedSamples: then the PACKED rows are staged and copied, and
-    qd_unpack_b8 on the copy stream fills the device buffer ahead of the event the decode waits for."""
+    qd_unpack_b8 on the copy stream fills the device buffer ahead of the event the decode waits for.
+    corrections=True: returns (predictions, host PackedSamples of plan.nfaults bits): every piece is decoded with a device buffer of correction
+    words (one per staging buffer) that leaves for a pinned buffer behind the piece's predictions."""
     import torch
     from ..samples import PackedSamples, unpack_b8_into
     N, ndet = a.shape
@@ -193,7 +220,16 @@ def decode_host_samples(plan, stage, a):
     piece = N if N <= plan.chunk else min(N, max(plan.chunk, int(plan.host_piece) // plan.chunk * plan.chunk))
     stage.fit(piece, ndet, N, plan.nobs, packed_bytes=(byte_hi - byte_lo) if packed else 0)
     out = stage.out
+    cwords = (plan.nfaults + 31) // 32
+    if corrections:
+        stage.fit_corrections(piece, N, cwords)
+        res_corr = np.empty((N, cwords), dtype=np.int32)
     cur = torch.cuda.current_stream()
+
+    def collect(lo_, hi_):                                     # a finished piece: widened / copied here, beside the decoding of the next one
+        res[lo_:hi_] = out[lo_:hi_].numpy()
+        if corrections:
+            res_corr[lo_:hi_] = stage.corr_out[lo_:hi_].numpy()
     h2d_done, dec_done = [None, None], [None, None]
     # calls of two or more chunks: the pieces go through the two-stream driver as ONE chain: the lanes carry over from piece to piece, a piece's BP
     # starts behind its own host-to-device copy, its predictions leave on the post stream; the caller's stream only waits at the very end
@@ -214,7 +250,7 @@ def decode_host_samples(plan, stage, a):
                 h2d_done[b].synchronize()                      # the staging buffer has left for the GPU
             if dec_done[b] is not None:
                 dec_done[b].synchronize()                      # the device buffer has been decoded, its predictions are in `out`:
-                res[span[b][0]:span[b][1]] = out[span[b][0]:span[b][1]].numpy()     # widened here, beside the decoding of the next piece
+                collect(*span[b])
             span[b] = (lo, hi)
             ready = []
             with torch.cuda.stream(stage.copy):                # chunk by chunk: the first chunk's BP starts behind ITS copy, not the piece's
@@ -232,14 +268,21 @@ def decode_host_samples(plan, stage, a):
             h2d_done[b] = ready[-1]
             dec_done[b] = torch.cuda.Event()
             if chained:                                        # (a ragged last piece too, whatever its size: it runs beside the piece before it)
-                pred = decode_pipelined(plan, stage.dev[b][:hi - lo], None, ready)
+                corr = stage.corr[b][:hi - lo] if corrections else None
+                pred = (decode_pipelined(plan, stage.dev[b][:hi - lo], None, ready) if corr is None else
+                        decode_pipelined(plan, stage.dev[b][:hi - lo], None, ready, correction=corr))
                 with torch.cuda.stream(ts.s_post):             # (in order behind the piece's post stages)
                     out[lo:hi].copy_(pred, non_blocking=True)
+                    if corrections:
+                        stage.corr_out[lo:hi].copy_(corr, non_blocking=True)
                     dec_done[b].record(ts.s_post)
             else:
                 cur.wait_event(h2d_done[b])
-                pred = plan.decode(stage.dev[b][:hi - lo])
+                corr = stage.corr[b][:hi - lo] if corrections else None
+                pred = plan.decode(stage.dev[b][:hi - lo]) if corr is None else plan.decode(stage.dev[b][:hi - lo], None, corr)
                 out[lo:hi].copy_(pred, non_blocking=True)
+                if corrections:
+                    stage.corr_out[lo:hi].copy_(corr, non_blocking=True)
                 dec_done[b].record(cur)
     finally:
         if ts is not None:
@@ -249,5 +292,5 @@ def decode_host_samples(plan, stage, a):
         stage.copy.synchronize()
     for b in (0, 1):
         if span[b] is not None:
-            res[span[b][0]:span[b][1]] = out[span[b][0]:span[b][1]].numpy()
-    return res
+            collect(*span[b])
+    return (res, correction_words_to_packed(res_corr, plan.nfaults)) if corrections else res

@@ -9,7 +9,7 @@ import numpy as np
 from scipy.sparse import csr_matrix
 
 from . import pipeline
-from .base import spacetime, window_count
+from .base import commit_ranges, spacetime, window_count
 from .plan_cache import _current_device, cached_plan, plan_key
 
 _CHUNK = 1 << 16   # shots per device batch
@@ -56,6 +56,9 @@ class DeviceWindowPlan:
         self.nz, self.nobs = int(nz), int(nobs)
         self.windows = []
         nwin = len(checks)
+        # where every window's committed columns lie in the space-time correction `decode(..., correction=...)` fills
+        self.commit_ranges = commit_ranges(commits)
+        self.nfaults = sum(nc for _, nc in self.commit_ranges)
         cache = {}
         for k in range(nwin):
             kw = dict(dict2 if k == nwin - 1 else dict1)
@@ -75,7 +78,8 @@ class DeviceWindowPlan:
                 Uk = csr_matrix(updates[k])
                 Uk = csr_matrix((Uk.data, Uk.indices, Uk.indptr), shape=(Uk.shape[0], graph.n))
                 U = GF2Matrix(Uk)
-            self.windows.append({"dec": dec, "graph": graph, "L": GF2Matrix(Lk), "U": U, "row0": int(row0[k]), "H": checks[k], "kw": kw})
+            self.windows.append({"dec": dec, "graph": graph, "L": GF2Matrix(Lk), "U": U, "row0": int(row0[k]), "H": checks[k], "kw": kw,
+                                 "col0": self.commit_ranges[k][0], "ncommit": self.commit_ranges[k][1]})
         self.env = driver_env()
         decs = self.decoders()
         edge = any(d.info()["edge_kernel"] for d in decs)
@@ -143,10 +147,22 @@ class DeviceWindowPlan:
             self._two_streams = pipeline.TwoStreams(device)
         return self._two_streams
 
-    def decode(self, det, stats=None):
+    def check_correction(self, correction, N, device):
+        import torch
+        words = (self.nfaults + 31) // 32
+        if not (isinstance(correction, torch.Tensor) and correction.is_cuda and correction.dtype == torch.int32 and correction.dim() == 2
+                and correction.shape[0] == N and correction.shape[1] >= words and (correction.shape[1] <= 1 or correction.stride(1) == 1)):
+            raise ValueError("correction must be a cuda int32 [%d, >= %d] tensor with unit stride inside a row" % (N, words))
+        if correction.device != device:
+            raise ValueError("correction lives on %s, the samples on %s" % (correction.device, device))
+
+    def decode(self, det, stats=None, correction=None):
         """det: cuda uint8 [N, ndet]  ->  cuda uint8 [N, nobs] logical predictions.
 
         Chunks of `self.chunk` shots, windows inner.  `stats`, if given, receives (window index, status tensor) pairs.
+        `correction`, if given, is a cuda int32 [N, >= ceil(nfaults / 32)] tensor that the call zero-fills and then fills with the space-time
+        correction: bit j & 31 of word j >> 5 of row b = fault j of the whole model is in shot b's correction -- every window's committed
+        columns at `commit_ranges[k]` (qd_commit_bits next to the window's acc ^= L_k e, on its stream).  Without it no launch is added.
         A call of two or more chunks runs a chunk's post-processing on a second stream beside the BP of the other chunks of its
         group (pipeline.decode_pipelined: headline 1.21 -> 1.30 M shots/s, BP-LSD order 1 690 k -> 866 k, p = 6e-3 320 k -> 355 k,
         W = 3 / F = 1 windows 511 k -> 539 k, identical outputs; profiles/r03x_pipelined_driver_ab.txt,
@@ -155,8 +171,14 @@ class DeviceWindowPlan:
         import torch
         N = det.shape[0]
         if self.pipeline and N >= 2 * self.chunk:
-            return pipeline.decode_pipelined(self, det, stats)
+            if correction is None:
+                return pipeline.decode_pipelined(self, det, stats)
+            return pipeline.decode_pipelined(self, det, stats, correction=correction)
         pred = torch.zeros((N, self.nobs), dtype=torch.uint8, device=det.device)
+        if correction is not None:
+            from .device import commit_bits
+            self.check_correction(correction, N, det.device)
+            correction.zero_()
         for c0 in range(0, N, self.chunk):
             chunk = det[c0:c0 + self.chunk]
             acc = pred[c0:c0 + self.chunk]
@@ -164,6 +186,8 @@ class DeviceWindowPlan:
             for k, w in enumerate(self.windows):
                 err_bits, status = w["dec"].decode(chunk, w["row0"], upd)
                 w["L"].xor_apply(err_bits, acc, accumulate=True)
+                if correction is not None:
+                    commit_bits(err_bits, w["ncommit"], correction[c0:c0 + self.chunk], w["col0"])
                 if w["U"] is not None:
                     upd = torch.empty((chunk.shape[0], self.nz), dtype=torch.uint8, device=det.device)
                     w["U"].xor_apply(err_bits, upd, accumulate=False)
@@ -171,13 +195,15 @@ class DeviceWindowPlan:
                     stats.append((k, status))
         return pred
 
-    def decode_host(self, zcheck_samples):
+    def decode_host(self, zcheck_samples, corrections=False):
         """The reference call's data path: host samples [N, ndet] (bool / uint8 / any integer numpy array, a torch tensor, or
         quits_amd.samples.PackedSamples on either side)
         -> int64 numpy [N, nobs] (reference sliding_window.py:160,186).  Host arrays are streamed: pieces of `self.host_piece`
         shots go through two pinned staging buffers and a copy stream, so that the host-side copy and the PCIe transfer of one
         piece run beside the decoding of the previous one, and the predictions come back through a pinned buffer
-        (pipeline.decode_host_samples).  Tensors that already live on the GPU skip the staging."""
+        (pipeline.decode_host_samples).  Tensors that already live on the GPU skip the staging.
+        corrections=True: returns (predictions, PackedSamples of `nfaults` bits per shot on the host), the space-time corrections of
+        `decode(..., correction=...)`; they come back through a pinned buffer of their own, piece by piece like the predictions."""
         import torch
         from ..samples import PackedSamples
         with self.in_use():
@@ -187,7 +213,12 @@ class DeviceWindowPlan:
             if isinstance(on_gpu, torch.Tensor) and on_gpu.is_cuda:
                 if on_gpu.device != dev:
                     raise RuntimeError("samples live on %s, the plan on %s" % (on_gpu.device, dev))
-                return self.decode(pipeline._to_device_samples(zcheck_samples)).cpu().numpy().astype(np.int64)
+                det = pipeline._to_device_samples(zcheck_samples)
+                if not corrections:
+                    return self.decode(det).cpu().numpy().astype(np.int64)
+                corr = torch.empty((det.shape[0], (self.nfaults + 31) // 32), dtype=torch.int32, device=dev)
+                pred = self.decode(det, None, corr)
+                return pred.cpu().numpy().astype(np.int64), pipeline.correction_words_to_packed(corr.cpu().numpy(), self.nfaults)
             if packed:
                 a = zcheck_samples                                # (staged packed: pipeline.decode_host_samples)
             else:
@@ -195,10 +226,13 @@ class DeviceWindowPlan:
             if a.ndim != 2:
                 raise ValueError("zcheck_samples must be a [shots, detectors] array")
             if a.shape[0] == 0:
-                return np.zeros((0, self.nobs), dtype=np.int64)
+                pred = np.zeros((0, self.nobs), dtype=np.int64)
+                return (pred, pipeline.correction_words_to_packed(np.zeros((0, (self.nfaults + 31) // 32), np.int32), self.nfaults)) if corrections else pred
             if self._staging is None:
                 self._staging = pipeline.HostStaging(dev)
-            return pipeline.decode_host_samples(self, self._staging, a)
+            if not corrections:
+                return pipeline.decode_host_samples(self, self._staging, a)
+            return pipeline.decode_host_samples(self, self._staging, a, corrections=True)
 
     def in_use(self):
         """Context manager around a run of `decode` calls that owns the plan: checks the current device, takes the plan's lock and marks

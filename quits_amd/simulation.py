@@ -7,6 +7,9 @@
                                                 the reference's users write around the two calls above (tests/test_sliding_window.py:72-83),
                                                 without a host array per shot
   replay_shots                                  the samples of given shot indices again (both samplers are counter-based)
+  get_fault_spectrum                            the same experiment on DEM-sampled shots with the faults in view: shots and failures by the
+                                                number of sampled faults, the residual E xor C of the failing shots, the lightest one seen
+  replay_faults                                 which faults fired in given shots of the DEM sampler
 
 `get_codecap_pL` keeps the reference's signature and its random stream (`np.random.seed(seed)` followed by one
 `np.random.binomial(1, p, n)` per trial), so a given seed produces the same noise vectors as the reference.  With a plug-in
@@ -314,3 +317,120 @@ def replay_shots(circuit, shot_indices, seed, sampler='circuit'):
     _lib.require_experiment(_lib.require_gpu())
     det, obs = _make_sampler(_as_circuit(circuit), sampler).sample_shots(shot_indices, int(seed))
     return det.cpu().numpy().astype(bool), obs.cpu().numpy().astype(bool)
+
+
+# ---- the same experiment with the faults in view --------------------------------------------------------------------------------------
+@dataclasses.dataclass
+class FaultSpectrumResult:
+    """What `get_fault_spectrum` returns.  shots, errors, pL as in MemExperimentResult.  shots_by_faults[w], errors_by_faults[w]: shots /
+    failing shots in which w faults of the detector error model fired (bin 255 collects w >= 255).  residual_shots: shots whose correction C
+    does not reproduce the syndrome (H C != det; some window reported an inconsistent syndrome), failing_residual_shots: the failing ones
+    among them.  residual_weight_hist[w]: failing shots with H C = det whose residual E xor C -- then an undetectable logical fault -- has
+    weight w (bin 255: >= 255).  lightest: (weight, global shot index) of the lightest such residual, ties to the smaller index, or None: an
+    explicit upper bound on the circuit-level distance; `replay_faults(circuit, [shot], seed)` regenerates its fault set."""
+    shots: int
+    errors: int
+    pL: float
+    shots_by_faults: np.ndarray
+    errors_by_faults: np.ndarray
+    residual_weight_hist: np.ndarray
+    residual_shots: int
+    failing_residual_shots: int
+    lightest: object
+    seed: int = 0
+    batch: int = 0
+    seconds: float = 0.0
+
+    def failure_fraction(self):
+        """f(w) = errors_by_faults[w] / shots_by_faults[w], float64 [256]; NaN where no shot had w faults."""
+        s = self.shots_by_faults.astype(np.float64)
+        return np.divide(self.errors_by_faults.astype(np.float64), s, out=np.full(s.shape, np.nan), where=s > 0)
+
+    @classmethod
+    def from_counts(cls, hist, counts, lightest, seed=0, batch=0, seconds=0.0):
+        """From decoder.device.FaultStats.result(): hist int64 [3, 256], counts = (shots, failing, shots with H C != det, failing ones of those)."""
+        h = np.asarray(hist, dtype=np.int64)
+        c = np.asarray(counts, dtype=np.int64)
+        shots, errors = int(c[0]), int(c[1])
+        if int(h[0].sum()) != shots or int(h[1].sum()) != errors or int(h[2].sum()) != errors - int(c[3]):
+            raise ValueError("fault histograms and counters disagree: %d / %d / %d shots in the histograms, counters %s"
+                             % (h[0].sum(), h[1].sum(), h[2].sum(), c.tolist()))
+        return cls(shots, errors, errors / shots if shots else float("nan"), h[0].copy(), h[1].copy(), h[2].copy(), int(c[2]), int(c[3]),
+                   None if lightest is None else (int(lightest[0]), int(lightest[1])), int(seed), int(batch), float(seconds))
+
+
+def get_fault_spectrum(circuit, hz, lz, W, F, num_trials, max_iter=2, osd_order=0, bp_method='product_sum', schedule='serial',
+                       osd_method='osd_cs', *, seed=0, batch=None, shard=None):
+    """`get_circuit_mem_pL(..., sampler='dem')` with the faults in view: every batch (experiment_batches') is sampled with its fault set E
+    (DemSampler.sample_faults), decoded with its space-time correction C (plan.decode(..., correction=...)), tallied (Tally), and
+    qd_fault_stats_batch bins the shots by |E|, the failing ones too, and the failing shots with H C = det by |E xor C|.  Nothing per shot
+    reaches the host.  Same shots, same decoder, same cached plan as that call: `shots` and `errors` are its numbers.
+
+    The shots always come from the circuit's detector error model: its columns (merged faults, detector_error_model_to_matrix) are what the
+    decoder's correction is written in.  The noise sites of the circuit-level frame sampler are not DEM columns -- one site is several
+    columns, several sites one column -- so there is no `sampler` argument here.
+
+    Returns a FaultSpectrumResult; `replay_faults(circuit, [result.lightest[1]], seed)` regenerates the lightest residual's fault set."""
+    import time
+    import warnings
+    from . import _lib
+    from .decoder.base import detector_error_model_to_matrix, window_count
+    from .decoder.bposd import BpOsdDecoder
+    from .decoder.plan import cached_circuit_plan
+    if F == 0:
+        raise ValueError("Input parameter F cannot be zero.")
+    _lib.require_faults(_lib.require_experiment(_lib.require_gpu()))
+    import torch
+    from .decoder.device import DemSampler, FaultStats, GF2Matrix, Tally
+    rank, world = (0, 1) if shard is None else (int(shard[0]), int(shard[1]))
+    circ = _as_circuit(circuit)
+    H, L, priors = detector_error_model_to_matrix(circ.detector_error_model())
+    smp = DemSampler(H, L, priors)
+    nz = hz.shape[0]
+    num_rounds = smp.m // nz - 2
+    if window_count(num_rounds, W, F)[2]:
+        warnings.warn("Window size larger than the syndrome extraction rounds: Doing whole history correction")
+    opts = {'bp_method': bp_method, 'max_iter': max_iter, 'schedule': schedule, 'osd_method': osd_method, 'osd_order': osd_order}
+    plan = cached_circuit_plan(circ, hz, W, F, num_rounds, BpOsdDecoder, BpOsdDecoder, opts, opts)
+    k = plan.nobs
+    if smp.nobs != k or np.asarray(lz.shape)[0] != k:
+        raise ValueError("the circuit has %d observables, lz %d rows, the window plan commits %d" % (smp.nobs, lz.shape[0], k))
+    if plan.nfaults != smp.nfaults:
+        raise ValueError("the windows commit %d faults, the detector error model has %d" % (plan.nfaults, smp.nfaults))
+    if batch is None:
+        batch = max(2, int(plan.lanes) if plan.pipeline else 2) * int(plan.chunk)
+    batches = experiment_batches(num_trials, batch, rank, world)
+    if batches and batches[-1][0] + batches[-1][1] > 1 << 40:
+        raise ValueError("shot indices must stay below 2^40")
+    Hdev = GF2Matrix(H)
+    words = (plan.nfaults + 31) // 32
+    with plan.in_use():
+        tally, fstats = Tally(k), FaultStats()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for shot0, n in batches:
+            det, obs, faults = smp.sample_faults(n, seed, shot0)
+            corr = torch.empty((n, words), dtype=torch.int32, device="cuda")
+            pred = plan.decode(det, None, corr)
+            mask = torch.empty(((n + 63) // 64,), dtype=torch.int64, device="cuda")
+            tally.add(pred, obs, None, mask)
+            Hdev.xor_apply(corr, det, accumulate=True)         # det is this batch's own: it becomes the residual H C xor det in place
+            fstats.add(faults, corr, plan.nfaults, det, mask, shot0)
+        torch.cuda.synchronize()
+        seconds = time.perf_counter() - t0
+        hist, counts, lightest = fstats.result()
+        tc = tally.counts()
+    if int(tc[0]) != int(counts[0]) or int(tc[1]) != int(counts[1]):
+        raise RuntimeError("the tally counted %d shots and %d failures, the fault statistics %d and %d" % (tc[0], tc[1], counts[0], counts[1]))
+    return FaultSpectrumResult.from_counts(hist, counts, lightest, seed, _batch_step(batch), seconds)
+
+
+def replay_faults(circuit, shot_indices, seed):
+    """Which faults of the circuit's detector error model fired in the given shots of `seed`'s DEM-sampled stream (get_fault_spectrum's, and
+    get_circuit_mem_pL's with sampler='dem'): numpy bool [len(shot_indices), nfaults], column j = column j of
+    detector_error_model_to_matrix(circuit)."""
+    from . import _lib
+    _lib.require_faults(_lib.require_experiment(_lib.require_gpu()))
+    smp = _make_sampler(_as_circuit(circuit), "dem")
+    bits = smp.sample_shots_faults(shot_indices, int(seed))[2].cpu().numpy()
+    return np.unpackbits(np.ascontiguousarray(bits).view(np.uint8), axis=1, bitorder="little")[:, :smp.nfaults].astype(bool)
