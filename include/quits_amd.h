@@ -75,12 +75,12 @@ typedef struct qd_circuit qd_circuit;   /* compiled circuit program of the frame
  * use; an object keeps what it read for its whole life, and nothing on the decode path reads the environment.
  *   QD_NO_SCATTER              D  flooding min-sum in the gather kernel (bp_kernels.hip) where a scatter kernel would take the window
  *   QD_SCATTER_M2_LIMIT=<u>    D  lower the scatter kernels' exactness bound to u grid units: shots take the gather kernel's recheck pass
- *   QD_SCATTER_CPL1            G  one check per lane (bp_scatter.hip) where the default is two per lane on half the lanes
- *   QD_SCATTER_WIDE_T704       G  several-checks-per-lane kernel (bp_scatter_wide.hip) on 704 lanes x 2 checks instead of 512 x 3
+ *   QD_SCATTER_CPL1            G  one check per lane where the default is two per lane on half the lanes (bp_scatter_wide.hip)
+ *   QD_SCATTER_WIDE_T704       G  the scatter kernel on 704 lanes x 2 checks instead of 512 x 3
  *   QD_SCATTER_NATURAL_ROUNDS  G  ... its wavefronts take the slot-waves in natural order (no balancing of their rounds)
  *   QD_SCATTER_BANKS_BY_SLOT   G  the scatter accumulators' banks = the degree-sorted bit slots mod 32 (no balancing)
  *   QD_SCATTER_WALK_GREEDY     G  the scatter kernels' walk without matching: every check takes its least busy bank
- *   QD_BP_NO_FAST_START=1      D  the several-checks-per-lane kernel runs gather pass 0 itself and the full last gather pass, instead of starting
+ *   QD_BP_NO_FAST_START=1      D  the scatter kernel runs gather pass 0 itself and the full last gather pass, instead of starting
  *                                 from the decoder's first-pass table and folding only the hard-decision parity in the last pass
  *   QD_OSDCS_OLD=1             D  higher-order OSD by row (osd_kernels.hip) instead of the panel kernel (osd_cs.hip)
  *   QD_GEN_STAGES="3,6" / =0   D  iteration bounds between the launches of the serial schedule (one-message-per-edge kernel) / one launch */
@@ -122,7 +122,7 @@ int qd_graph_info(const qd_graph *g, int32_t *info);
 /* The same with the caller saying how many int32 entries `info` has room for; entries 10, 11 = modelled LDS cycles of one pass of
  * the scatter kernels' walk over the accumulators (bank conflicts included) and the same without any conflict (0, 0: the window
  * does not run there); entries 12, 13 = lanes per workgroup and checks per lane of qd_bp_scatter_wide_kernel's instantiation for this
- * window (0, 0: the window does not take that kernel); entries beyond the ones this version knows are set to 0. */
+ * window (one check per lane: the gather kernel's lanes, 1; 0, 0: no scatter kernel for this window); entries beyond the ones this version knows are set to 0. */
 int qd_graph_info_ex(const qd_graph *g, int32_t *info, int32_t n_entries);
 
 /* ---- decoder: replaces BpOsdDecoder.__init__'s parameter half. */
@@ -136,12 +136,12 @@ void qd_decoder_destroy(qd_decoder *d);
  * (bound S < 2^(23-k), bp_kernels.hip); a shot whose bound trips is decoded again on the coarser grid info[1]
  * (QD_STATUS_COARSE_GRID), and flagged QD_STATUS_INEXACT if that trips too.  k = max(10, r), r = 23 - ceil(log2(8 * max|llr| * max_iter))
  * clamped to [2, 20]; info[1] = max(r - 4, 0) if r >= 10, else r (the rule's own grid takes the shots that outgrow 2^-10).  info[2] = 1 if BP runs in the one-message-per-edge kernel.  info[3] = 1 if the fine-grid pass of flooding min-sum runs in
- * the scatter kernel (bp_scatter.hip: same results, bit for bit; QD_NO_SCATTER=1 in the environment keeps the gather kernel),
- * 2 if in its several-checks-per-lane form (bp_scatter_wide.hip: the default shape -- two checks per lane on half the lanes; three per
- * lane for windows of more than 1024 checks or rows of 65..96 faults).
+ * the scatter kernel (bp_scatter_wide.hip: same results, bit for bit; QD_NO_SCATTER=1 in the environment keeps the gather kernel) with
+ * one check per lane, 2 if with several (the default shape -- two checks per lane on half the lanes; three per lane for windows of more
+ * than 1024 checks or rows of 65..96 faults).
  * No reference counterpart (ldpc computes in double). */
 int qd_decoder_info(const qd_decoder *d, int32_t *info);
-/* 1 if the several-checks-per-lane scatter kernel of this decoder starts from the first-pass table (gather pass 0 of flooding min-sum reads the
+/* 1 if the scatter kernel of this decoder starts from the first-pass table (gather pass 0 of flooding min-sum reads the
  * priors alone, so what it finds is made once, when the decoder is created) and runs its last gather pass in the thin form; 0 otherwise
  * (another BP kernel, max_iter < 1, QD_BP_NO_FAST_START=1).  Same results either way, bit for bit. */
 int qd_decoder_fast_start(const qd_decoder *d);

@@ -1,6 +1,6 @@
-// bp_scatter_edge.h -- the per-edge steps of the scatter form of flooding min-sum (gather pass: QS_EDGE, scatter pass: QS_SCAT), shared by
-// qd_bp_scatter_kernel (bp_scatter.hip: one check per lane) and qd_bp_scatter_wide_kernel (bp_scatter_wide.hip: several checks per lane).
-// The macros work on the enclosing scope's names: s1, s2, kold, sgnw (what the check sent last), a1, a2, ltw, neww, hp (what this pass
+// bp_scatter_edge.h -- the per-edge steps of the scatter form of flooding min-sum (gather pass: QS_EDGE_M, scatter pass: QS_SCAT) of
+// qd_bp_scatter_wide_kernel and qd_bp_first_pass_kernel (bp_scatter_wide.hip, bp_scatter_wide_walk.inc).
+// The macros work on the enclosing scope's names: s1, s2 (what the check sent last), a1, a2, ltw, neww, hp (what this pass
 // collects), dc (the check's degree), pdif, pxq, own, xw (scatter pass).
 #pragma once
 #include "qd_internal.h"
@@ -19,33 +19,27 @@ typedef __attribute__((address_space(3))) int32_t qs_lds_i32;
 #define QS_BIG 1.0e30f
 #define QS_PRIO 1         // wavefront priority during the scatter pass (short, bound by the LDS): 53.4 -> 52.8 ms at the headline
 
-// Gather pass, one edge.  off = LDS byte offset of the fault's accumulator (L - 1) in the buffer being read; k_ = position of the
-// edge in the check's walk (wave-uniform), compared with the argmin label of the last pass; SGN_ = the sign of the message this check sent on the edge, at
-// bit 31 (QS_SIGN31(sb): sb = the bit of `sgnw` that holds it; QS_SIGN_TOP: the wide walk keeps it at the top of the word that collects the new signs).
+// Gather pass, one edge.  off = LDS byte offset of the fault's accumulator (L - 1); k_ = position of the edge in the check's walk
+// (wave-uniform); SGN_ = the sign of the message this check sent on the edge, at bit 31 (QS_SIGN_TOP: the walk keeps it at the top of the word that
+// collects the new signs).
 // d_ = (L - 1) - prev = bm - 1 is an integer-valued float, so (bm <= 0) is its sign bit (-0.0 cannot occur: an integer converted to float is never -0,
 // and x - y is -0 only for x = -0).
 // HP: how the accumulator's bits enter `hp` (only bit 31, the hard decision, is used): QS_HP1 one XOR per edge; QS_HPA / QS_HPB on the
 // two edges of a pair -- the first is remembered in `hpa`, the second folds both in with one v_bitop3_b32 (a ^ b ^ c): half an instruction per edge
-// QS_SIGN31(sb): the sign this check sent on the edge (bit `sb` of sgnw) moved to bit 31.  (Keeping sgnw pre-shifted so that the shift amounts are
-// immediates instead of one scalar each measured slower: 42.6 -> 43.1 ms, profiles/r05_k1sw_micro_ab.txt.)
 // QS_SIGN_TOP: bit 31 of `neww` as it stands (bp_scatter_wide_walk.inc starts neww at the sent word, first edge on top): no shift of its own, the v_alignbit
 // that collects this edge's new sign brings the next edge's sent sign up (profiles/bp_sign_register_ab.txt).
 // QS_ACC(off): the accumulator itself -- an LDS read in the kernels; the first-pass table (bp_scatter_wide.hip) redefines it to read the priors from
 // global memory.
 #define QS_ACC(off) (*QS_LDS(off))
-#define QS_SIGN31(sb) (((sgnw >> (sb)) & 1u) << 31)
 #define QS_SIGN_TOP (neww & 0x80000000u)
 #define QS_HP1(A_) hp ^= (uint32_t)(A_);
 #define QS_HPA(A_) hpa = (uint32_t)(A_);
 #define QS_HPB(A_) hp = __builtin_amdgcn_bitop3_b32(hp, hpa, (uint32_t)(A_), 0x96);
-// MAG_: what this check sent on the edge last time, as a magnitude: min2 on its old argmin edge, min1 elsewhere.  QS_MAG_CMP asks every edge
-// (one v_cmp + v_cndmask each); QS_MAG_MASK(q_) (bp_scatter_wide_walk.inc) picks by lane masks kept in scalar registers: `gsel_` = the lanes whose
+// MAG_: what this check sent on the edge last time, as a magnitude: min2 on its old argmin edge, min1 elsewhere.  QS_MAG_MASK(q_)
+// (bp_scatter_wide_walk.inc) picks by lane masks kept in scalar registers, not with a compare per edge: `gsel_` = the lanes whose
 // old argmin lies in this group of four edges (one v_cmp per group), `lq[q_]` = the lanes whose old argmin is edge q_ of its group (one v_cmp per
 // check and pass); the AND runs on the scalar unit and the select takes the scalar pair as it is.
-#define QS_MAG_CMP(k_) (((uint32_t)(k_) == kold) ? s2 : s1)
 #define QS_MAG_MASK(q_) (__builtin_amdgcn_inverse_ballot_w64(gsel_ & lq[q_]) ? s2 : s1)
-#define QS_EDGE(off, k_, sb, TAILFIX) QS_EDGE_H(off, k_, sb, TAILFIX, QS_HP1)
-#define QS_EDGE_H(off, k_, sb, TAILFIX, HP) QS_EDGE_M(off, k_, QS_SIGN31(sb), TAILFIX, HP, QS_MAG_CMP(k_))
 #define QS_EDGE_M(off, k_, SGN_, TAILFIX, HP, MAG_)                                                          \
     {                                                                                                        \
         const int A_ = QS_ACC(off);                                                                          \

@@ -1,33 +1,56 @@
-// bp_scatter_wide.hip -- the scatter form of flooding min-sum BP (bp_scatter.hip) with CPL checks per lane and NSW 32-bit sign words
-// per check.  The default shape of flooding min-sum on the LLR grid:
-//   * windows bp_scatter.hip could take with one check per lane run here on HALF the lanes with two checks each -- the headline window
-//     (1008 checks) on 512 lanes: the same 32 wavefronts per CU in four workgroups instead of two, i.e. half as many wavefronts per
-//     barrier (BP 50.3 -> 44.2 ms per 65 536 shots); 512-thread windows on 256 lanes, windows of <= 128 checks on 128;
-//   * windows it cannot take -- more checks than a workgroup has lanes, or rows of 65..96 faults (three sign words) -- on 512 lanes x 3
-//     checks (or 704 / 1024 x 2): the windows of BASELINE configs[4] (QLP [[1020,136]], W = 3: 1350 checks of up to 78 faults, 18 900 faults).
+// bp_scatter_wide.hip -- flooding min-sum belief propagation on an LLR grid, scatter form: one workgroup per shot, CPL checks per lane
+// with NSW 32-bit sign words each, the checks' message state in their lane's REGISTERS, the faults' posteriors as 32-bit integers (grid
+// units) in LDS.  The only scatter kernel, and the default of flooding min-sum on the grid for the windows ScatGraphDev::ok admits.
 //
 // Replaces ldpc.BpOsdDecoder.decode -> BpDecoder::bp_decode_parallel (MINIMUM_SUM, ms_scaling_factor 1) as the reference calls it at
-// quits/decoder/sliding_window.py:171,182.  Same arithmetic, same certificate and the same outputs as qd_bp_scatter_kernel and
-// qd_bp_minsum_kernel, bit for bit; oracle: oracle/bp_core.inc bp_parallel_edge in double on the same LLR grid.
+// quits/decoder/sliding_window.py:171,182.  Returns exactly what qd_bp_minsum_kernel (bp_kernels.hip) returns -- hard decisions,
+// iteration counts, status words, posteriors of the shots that go to OSD -- bit for bit; oracle: oracle/bp_core.inc bp_parallel_edge in
+// double on the same LLR grid.
 //
-// Why for the QLP windows.  qd_bp_minsum_kernel keeps 16 bytes of packed state per check plus sign words plus a float posterior per
-// fault in LDS: 112 KB per QLP shot, ONE workgroup of 1024 threads per CU, four wavefronts per SIMD.  In the scatter form the LDS holds
-// one int32 accumulator per fault (76 KB), so TWO shots share a CU (BP 36.8 -> 19.0 ms per 8192-shot window launch).
+// Why a scatter form.  bp_kernels.hip spends 8.3 vector instructions and one 16-byte LDS gather per edge in its bit pass (a fault
+// rebuilding every check's message from the check's packed state).  On the grid every message is an integer multiple of 2^-k, so a
+// posterior is an INTEGER sum -- and integer LDS atomics run at the rate of a 4-byte gather (ds_add_u32: 2.2 ns per wavefront
+// instruction per CU, scattered addresses; ds_add_f32: 80 ns, profiles/r03z_lds_atomic_rates.txt).  So the check that has just
+// computed (min1, min2, argmin, signs) adds +-min1 to each of its faults' accumulators itself (one sign mask, one xor, one subtract,
+// one ds_add_u32 per edge), corrects the argmin fault by +-(min2 - min1), and the bit pass is gone.  The check state never leaves the
+// lane, so the LDS holds one int32 accumulator per fault and nothing per check: 38 KB + 2 KB at the headline window, 76 KB for a QLP
+// window of BASELINE configs[4] where qd_bp_minsum_kernel needs 112 KB (ONE workgroup of 1024 threads per CU; here two: BP 36.8 ->
+// 19.0 ms per 8192-shot window launch).
+//
+// The shapes (graph_layout.hip: build_scatter chooses, qd_launch_bp_scatter_wide below instantiates):
+//   * a window with a lane for every check and rows of up to 64 faults runs on HALF the lanes with two checks each where the LDS holds
+//     twice the workgroups -- the headline window (1008 checks) on 512 lanes: the same 32 wavefronts per CU in four workgroups instead
+//     of two, i.e. half as many wavefronts per barrier (BP 50.3 -> 44.2 ms per 65 536 shots); 512-thread windows on 256 lanes, windows
+//     of <= 128 checks on 128;
+//   * where it does not, or under QD_SCATTER_CPL1=1, on 256 / 512 / 1024 lanes with one check each;
+//   * more checks than a workgroup has lanes, or rows of 65..96 faults (three sign words): 512 lanes x 3 checks (or 704 / 1024 x 2) --
+//     the windows of BASELINE configs[4] (QLP [[1020,136]], W = 3: 1350 checks of up to 78 faults, 18 900 faults).
 //
 // A lane's checks keep their state in registers (two minima, argmin position, the sign words, twice: what was sent and what the gather
 // pass just found).  Check slots are sorted by degree; a wavefront's 64 checks of one round are 64 consecutive slots (sg.wave_map), so
 // the trip count stays wave-uniform, and the rounds are dealt out so that the wavefronts of a workgroup walk equally many edges between
 // two barriers.
 //
-// One iteration = [gather pass of check 0 .. CPL-1] barrier [converged? | scatter pass of check 0 .. CPL-1] barrier, in place as in
-// bp_scatter.hip (every gather of the iteration precedes every add).
+// One iteration = [gather pass of check 0 .. CPL-1 over L(t): new minima and signs, and the syndrome of L(t)'s hard decision] barrier
+// [converged? | scatter pass of check 0 .. CPL-1] barrier.  The scatter pass works in place: every gather of the iteration precedes
+// every add, and each edge's accumulator moves by (new message) - (message sent last time), so L(t+1) = prior + sum of the new messages
+// without a second buffer and without a reset.  An accumulator holds L - 1, so that (L <= 0) is its sign bit: a check gets the parity
+// of its faults' hard decisions with one XOR per edge, and (bit->check message <= 0) is the sign bit of the difference it computes anyway.
+//
+// Exactness.  Integer accumulation cannot round; what must not round are the float operations of the gather
+// pass, on integer-valued floats: exact below 2^24.  Every |posterior partial sum| and |bit->check message| of fault j is at most
+// S_j = |prior_j| + sum_i |c2b_ij| <= max|prior| + max_cdeg * max_i min2_i, so max over checks and iterations of min2 <
+// (2^23 - max|prior|) / max_cdeg - 1 (ScatArgs::m2_limit; one v_max per CHECK per iteration) certifies the run.  That bound is
+// looser than qd_bp_minsum_kernel's per-fault one, which the oracle restates: a shot it cannot certify is parked and decoded again
+// by qd_bp_minsum_kernel (recheck pass), which then decides about the coarse grid as before.  A certified shot is exact in both
+// kernels, hence identical.
 #include "qd_internal.h"
 #include "qd_host.h"
 #include "../../include/quits_amd.h"
 #include "bp_scatter_edge.h"
 
-// Wavefront priorities.  A wavefront raises its priority for its last gather round (0 -> 2; the scatter pass runs at QS_PRIO = 1 as
-// in bp_scatter.hip): the wavefronts closest to the barrier go first, so a workgroup's stragglers are fewer.  Headline BP stage 44.1 ->
+// Wavefront priorities.  A wavefront raises its priority for its last gather round (0 -> 2; the scatter pass runs at QS_PRIO = 1,
+// bp_scatter_edge.h): the wavefronts closest to the barrier go first, so a workgroup's stragglers are fewer.  Headline BP stage 44.1 ->
 // 43.2 ms per 65 536 shots; the other way round (first round high) 43.7, scatter pass at 0 / 2 / 3 no change, alternate wavefronts
 // high no change (profiles/r03x_wavefront_priority_ab.txt).  Between the passes the kernel runs at priority 0: every priority raised by one, so that
 // a kernel beside this one (the pipelined driver's post-processing) only issues when this one does not, was no faster (profiles/r06_bp_stream_bubble.txt).
@@ -425,6 +448,12 @@ hipError_t qd_launch_bp_scatter_wide(const BpGraphDev &g, const ScatGraphDev &sg
         return two_words ? launch_scatter_wide_t<256, 8, 2, 2>(g, sg, a, x, B, s) : hipErrorInvalidValue;
     case 128 * 8 + 2:           // <= 256 checks: sixteen workgroups of two wavefronts per CU (ONE wavefront with four checks per lane, no barrier partner: 7.73 -> 8.99 ms on 216-check windows, profiles/r05_scatter_small_ab.txt)
         return two_words ? launch_scatter_wide_t<128, 8, 2, 2>(g, sg, a, x, B, s) : hipErrorInvalidValue;
+    case 256 * 8 + 1:           // one check per lane: the windows whose LDS does not hold twice the workgroups, and QD_SCATTER_CPL1
+        return two_words ? launch_scatter_wide_t<256, 8, 1, 2>(g, sg, a, x, B, s) : hipErrorInvalidValue;
+    case 512 * 8 + 1:
+        return two_words ? launch_scatter_wide_t<512, 8, 1, 2>(g, sg, a, x, B, s) : hipErrorInvalidValue;
+    case 1024 * 8 + 1:
+        return two_words ? launch_scatter_wide_t<1024, 8, 1, 2>(g, sg, a, x, B, s) : hipErrorInvalidValue;
     case 704 * 8 + 2:           // 11 wavefronts; two workgroups per CU: <= 6 per SIMD, 80 registers
         return launch_scatter_wide_t<704, 6, 2, 3>(g, sg, a, x, B, s);
     case 1024 * 8 + 2: return launch_scatter_wide_t<1024, 4, 2, 3>(g, sg, a, x, B, s);      // (a 64-register budget -- two workgroups of 16 wavefronts per CU -- measured no faster on the QLP windows and spills with the prefetch registers)

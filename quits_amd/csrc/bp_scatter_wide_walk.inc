@@ -41,7 +41,7 @@
                         uint4 nx = (j == 0 && w == 0) ? pf : QS_ADJ(row0);
                         int kk = 0;
                         {
-                            uint4 eb;                                         // two groups per trip on two register sets (bp_scatter.hip)
+                            uint4 eb;                                         // two groups per trip on two register sets: the next group's offsets are requested while this one is worked on, without copying them
 #pragma unroll 1
                             for (; kk + 8 <= kplain; kk += 8) {
                                 eb = QS_ADJ(row0 + (kk >> 2) + 1);            // (the table has spare group rows)

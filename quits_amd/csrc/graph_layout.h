@@ -43,7 +43,7 @@ struct GraphImage {
     BpGraphDev bp{};
     GenGraphDev gen{};
     OsdGraphDev osd{};
-    ScatGraphDev sc{};                 // scatter form of the flooding min-sum kernel (bp_scatter.hip); sc.ok = 0: not for this window
+    ScatGraphDev sc{};                 // scatter form of the flooding min-sum kernel (bp_scatter_wide.hip); sc.ok = 0: not for this window
     std::vector<int32_t> h_cp, h_ri;   // host CSC, for the rank
     std::vector<double> h_llr0;        // log((1-p)/p) in double, fault order
     std::vector<uint32_t> h_bit_rec;   // host copy of bp.bit_rec: a decoder on an LLR grid uploads its own with word 0 replaced

@@ -45,7 +45,7 @@ Switches qd_read_switches()
     return w;
 }
 
-// ---- LDS banks for the scatter kernels (bp_scatter.hip, bp_scatter_wide.hip) --------------------------------------------------
+// ---- LDS banks for the scatter kernel (bp_scatter_wide.hip) -------------------------------------------------------------------
 // Step k of a wavefront's walk is one ds_read_b32 (gather pass) and one ds_add_u32 (scatter pass) over the accumulators of the faults
 // its 64 checks meet at that step, serviced in two groups of 32 lanes with bank = (address / 4) mod 32 and one extra LDS cycle per
 // additional lane on a busy bank (MI355X_MICROARCH.md, LDS; an atomic does not broadcast).  Two things are free: which bank a fault's
@@ -245,10 +245,10 @@ static int bp_block_threads(int m, int n) { return std::max(m, (n + 9) / 10) <= 
 
 static int scatter_wide_threads(int m) { return pad64((m + 1) / 2) <= 704 ? 704 : 1024; }
 
-// The shape conditions of the scatter kernels (build_scatter checks their LDS fit).  1: one check per lane (bp_scatter.hip): every check
-// has a lane and rows hold 2..64 faults (two sign words; a row of one fault has no second minimum) -- also the windows of <= 256 checks,
+// The shape conditions of the scatter kernel (build_scatter checks the LDS fit and chooses the shape).  1: every check can have a lane of
+// its own (one check per lane, or two on half the lanes) and rows hold 2..64 faults (two sign words; a row of one fault has no second minimum) -- also the windows of <= 256 checks,
 // 3.78 -> 3.00 ms per launch on the 108-check and 8.92 -> 7.73 ms on the 216-check windows of the W = 3 plans (profiles/r05_scatter_small_ab.txt).
-// 2: several checks per lane (bp_scatter_wide.hip): more checks than a workgroup has lanes, or rows of 65..96 faults -- the QLP windows
+// 2: several checks per lane always: more checks than a workgroup has lanes, or rows of 65..96 faults -- the QLP windows
 // of BASELINE configs[4] (1326 checks of up to 78 faults on 704 lanes).  0: neither.
 static int scatter_form(const HostGraph &h)
 {
@@ -329,7 +329,7 @@ static void build_bp(GraphImage *g, HostGraph &h, bool walk_for_atomics)
     // Greedy per group of 32 check slots: at every step each check takes, among its remaining edges, the one whose bank has
     // the fewest distinct addresses so far in that step.  Headline window: 2918 -> 1463 LDS cycles per iteration for these
     // gathers (1062 without any conflict; tools/lds_model.py).
-    // The scatter kernel (bp_scatter.hip) walks the same order with ds_add_u32, and lanes of one instruction that add to the SAME
+    // The scatter kernel (bp_scatter_wide.hip) walks the same order with ds_add_u32, and lanes of one instruction that add to the SAME
     // address serialise like any other bank conflict (profiles/r03z_lds_atomic_rates.txt: two lanes per address 2.2 -> 4.7 ns per
     // instruction), where a gather broadcasts for free: for the windows that kernel takes (walk_for_atomics), a lane on a busy bank
     // costs one cycle whatever its address.
@@ -537,7 +537,7 @@ static void build_gen(GraphImage *g, const HostGraph &h)
     g->stage(std::move(srec), &gg.srec);
 }
 
-// Scatter form of the flooding min-sum kernel (bp_scatter.hip, bp_scatter_wide.hip; ScatGraphDev): checks in lanes with their state in
+// Scatter form of the flooding min-sum kernel (bp_scatter_wide.hip; ScatGraphDev): checks in lanes with their state in
 // registers, the faults' integer posterior accumulators in LDS.  Taken (sc.ok) for the windows of scatter_form whose accumulators leave
 // as many workgroups per CU as the gather kernel's layout does.
 static int build_scatter(GraphImage *g, const HostGraph &h, int form, const Switches &env)
@@ -617,18 +617,19 @@ static int build_scatter(GraphImage *g, const HostGraph &h, int form, const Swit
     g->stage(std::move(slot_fault), &sc.slot_fault); g->stage(std::move(k1_slot), &sc.k1_slot);
     g->stage(deg_w, &sc.deg_w); g->stage(h.chk_deg, &sc.chk_deg);
     sc.ok = 1;
-    // Several checks per lane (bp_scatter_wide.hip).  (a) windows the one-check-per-lane kernel cannot take: three checks per
-    // lane on 512 lanes (or two on 704 / 1024).  (b) windows it can take, on HALF the lanes with two checks each: the same number
-    // of wavefronts per CU in twice as many workgroups, i.e. half as many wavefronts per barrier -- headline BP 50.3 -> 44.2 ms per
-    // 65 536 shots, same bits (profiles/r03x_scatter_cpl2_ab.txt); taken when the LDS holds twice the workgroups.
-    // QD_SCATTER_CPL1=1 keeps one check per lane.  Measured and not kept (profiles/r03x_scatter_shapes2_ab.txt): four checks per
-    // lane on a quarter of the lanes (headline 46.2 -> 50.9 ms), 384 lanes x 4 checks for the QLP windows (19.2 -> 24.4 ms).
-    sc.wide_threads = shape_cpl > 1 ? shape_threads : 0; sc.wide_cpl = shape_cpl > 1 ? shape_cpl : 0;
-    if (!sc.wide_threads) return QD_OK;
+    // The shape of qd_bp_scatter_wide_kernel (bp_scatter_wide.hip).  (a) windows with more checks than lanes or rows of three sign
+    // words: three checks per lane on 512 lanes (or two on 704 / 1024).  (b) windows with a lane for every check, on HALF the lanes
+    // with two checks each: the same number of wavefronts per CU in twice as many workgroups, i.e. half as many wavefronts per
+    // barrier -- headline BP 50.3 -> 44.2 ms per 65 536 shots, same bits (profiles/r03x_scatter_cpl2_ab.txt); taken when the LDS
+    // holds twice the workgroups.  (c) the rest of (b), and all of it under QD_SCATTER_CPL1=1: one check per lane on bp.threads
+    // lanes.  Measured and not kept (profiles/r03x_scatter_shapes2_ab.txt): four checks per lane on a quarter of the lanes
+    // (headline 46.2 -> 50.9 ms), 384 lanes x 4 checks for the QLP windows (19.2 -> 24.4 ms).
+    sc.wide_threads = shape_threads; sc.wide_cpl = shape_cpl;
     // deal the slot-waves (64 consecutive check slots, heaviest first) to the workgroup's wavefronts so that the largest
     // number of edges a wavefront walks between two barriers is small: each goes to the wavefront with the fewest edges so
     // far that still has a free round (longest-processing-time rule), then single moves / swaps out of the heaviest
-    // wavefront while they lower the maximum (QLP windows on 8 wavefronts x 3 rounds: 222 -> 202 edge steps)
+    // wavefront while they lower the maximum (QLP windows on 8 wavefronts x 3 rounds: 222 -> 202 edge steps).  With one
+    // round there is nothing to balance: every slot-wave gets a wavefront of its own.
     const int nw = sc.wide_threads / 64, nsw = m_pad / 64, cpl = sc.wide_cpl;
     const bool natural = env.scatter_natural_rounds;                   // round j of wavefront w = slot-wave j * nw + w
     auto cost = [&](int sw) { return (int)(deg_w[sw] & 0xFF) + 6; };   // trip count + the per-check work outside the edge loops

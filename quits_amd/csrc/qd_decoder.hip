@@ -113,7 +113,7 @@ extern "C" int qd_decoder_create(const qd_graph *g, const qd_params *p, qd_decod
         if (!edge) d->bp = BP_GATHER_GRID;
         if (!edge && g->sc.ok && !env.no_scatter) {
             // scatter kernel: fine-grid priors of the bit slots as integers (grid units) and the second-minimum bound that
-            // certifies a run (bp_scatter.hip): max|prior| + max_cdeg * max min2 < 2^23
+            // certifies a run (bp_scatter_wide.hip): max|prior| + max_cdeg * max min2 < 2^23
             std::vector<int32_t> pg((size_t)g->sc.nslots, 0);      // (unused and trash slots: 0)
             long long mxp = 0;
             for (int j = 0; j < g->n; ++j) {
@@ -125,8 +125,8 @@ extern "C" int qd_decoder_create(const qd_graph *g, const qd_params *p, qd_decod
             if (mxp < (1ll << 22) && lim > 0) {
                 rc |= d->mem.upload(pg, &d->prior_g);
                 d->m2_limit = std::min((float)lim, env.scatter_m2_limit);     // (QD_SCATTER_M2_LIMIT: tests force the recheck pass)
-                d->bp = g->sc.wide_threads ? BP_SCATTER_WIDE : BP_SCATTER;
-                if (d->bp == BP_SCATTER_WIDE && !env.bp_no_fast_start && rc == 0) {
+                d->bp = BP_SCATTER_WIDE;
+                if (!env.bp_no_fast_start && rc == 0) {
                     // gather pass 0 does not depend on the shot: made here once, on the device, by the kernel's own walk (bp_scatter_wide.hip)
                     const std::vector<uint32_t> zero((size_t)g->bp.m_pad * 8, 0u);
                     rc |= d->mem.upload(zero, &d->first_pass);
@@ -146,7 +146,7 @@ extern "C" int qd_decoder_info(const qd_decoder *d, int32_t *info)
 {
     if (!d || !info) return qd_fail(QD_EINVAL, "null argument");
     info[0] = d->grid_k; info[1] = d->grid_kc; info[2] = d->bp == BP_LDS_EDGE || d->bp == BP_HBM_EDGE;
-    info[3] = d->bp == BP_SCATTER_WIDE ? 2 : (d->bp == BP_SCATTER ? 1 : 0);
+    info[3] = d->bp == BP_SCATTER_WIDE ? (d->g->sc.wide_cpl > 1 ? 2 : 1) : 0;
     return QD_OK;
 }
 
@@ -190,7 +190,7 @@ extern "C" int qd_decoder_reserve(qd_decoder *d, int64_t max_batch)
     ws.fail_count = ws.ctr_base; d->cset = 0; d->set_clean[0] = d->set_clean[1] = false;     // (see Workspace::ctr_base)
     HIP_TRY(hipHostMalloc((void **)&ws.host_fail, 2 * sizeof(int32_t)));
     HIP_TRY(hipEventCreateWithFlags(&ws.fail_ready, hipEventDisableTiming));
-    const bool grid = d->bp == BP_SCATTER_WIDE || d->bp == BP_SCATTER || d->bp == BP_GATHER_GRID;
+    const bool grid = d->bp == BP_SCATTER_WIDE || d->bp == BP_GATHER_GRID;
     if (grid || d->edge_cert) {
         ws.redo_cap = (int)(d->grid_floor ? max_batch : std::min<int64_t>(max_batch, 4096));
         HIP_TRY(ws.dev.alloc((size_t)ws.redo_cap, &ws.redo_list));
@@ -398,7 +398,6 @@ static int launch_bp(qd_decoder *d, const DecodeArgs &a, int64_t B, hipStream_t 
         break;
     }
     case BP_SCATTER_WIDE:
-    case BP_SCATTER:
     case BP_GATHER_GRID: {
         // grid arithmetic: first pass on the fine grid parks the shots whose exactness bound tripped; they are decoded
         // again on the coarse grid by a second launch (one workgroup per parked shot; the others exit at once)
@@ -416,8 +415,7 @@ static int launch_bp(qd_decoder *d, const DecodeArgs &a, int64_t B, hipStream_t 
             x.prior_g = d->prior_g; x.grid_inv = std::ldexp(1.0f, -d->grid_k); x.m2_limit = d->m2_limit;
             x.recheck_list = d->ws.recheck_list; x.recheck_count = recheck_count; x.recheck_cap = d->ws.recheck_cap;
             x.first_pass = d->first_pass;
-            if (d->bp == BP_SCATTER_WIDE) HIP_TRY(qd_launch_bp_scatter_wide(d->bp_fine, g->sc, a1, x, B, s));
-            else HIP_TRY(qd_launch_bp_scatter(d->bp_fine, g->sc, a1, x, B, s));
+            HIP_TRY(qd_launch_bp_scatter_wide(d->bp_fine, g->sc, a1, x, B, s));
             a1.shot_list = d->ws.recheck_list; a1.shot_count = recheck_count;
             HIP_TRY(qd_launch_bp(d->bp_fine, a1, std::min<int64_t>(B, d->ws.recheck_cap), s));
         }

@@ -98,7 +98,7 @@ int qd_host_rank(qd_graph *g)
 // 8-byte overwrite for a C caller compiled against the older header); whoever wants more says how many it has room for.
 static void graph_info_fill(const qd_graph *g, int32_t *info, int n_entries)
 {
-    // [12], [13]: lanes and checks per lane of qd_bp_scatter_wide_kernel's instantiation for this window (0: the window does not take that kernel)
+    // [12], [13]: lanes and checks per lane of qd_bp_scatter_wide_kernel's instantiation for this window (0, 0: no scatter kernel)
     const int32_t v[14] = {g->m, g->n, g->nnz, g->max_rdeg, g->max_cdeg, g->bp.threads, g->bp.lds_bytes, g->osd.threads, g->osd.lds_bytes,
                            n_entries > 9 ? qd_host_rank(const_cast<qd_graph *>(g)) : 0, (int32_t)g->sc_walk_cycles, (int32_t)g->sc_walk_ideal,
                            g->sc.wide_threads, g->sc.wide_cpl};

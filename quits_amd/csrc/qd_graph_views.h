@@ -40,13 +40,13 @@ struct BpGraphDev {
     int threads;
 };
 
-// The scatter form of the flooding min-sum kernel (bp_scatter.hip): a check keeps its state in the registers of its lane and ADDS its
-// messages to the faults' integer accumulators in LDS (ds_add_u32), so there is no bit pass.  Two posterior buffers A / B alternate
-// (one is read while the other accumulates); the adjacency exists once per buffer so that a gather / scatter needs no address add.
+// The scatter form of the flooding min-sum kernel (bp_scatter_wide.hip): a check keeps its state in the registers of its lane and ADDS its
+// messages to the faults' integer accumulators in LDS (ds_add_u32), so there is no bit pass.  One posterior buffer, updated in place
+// (offA = offB, adjA = adjB: the kernel reads the A members); the adjacency holds LDS byte offsets so that a gather / scatter needs no address add.
 struct ScatGraphDev {
-    int ok;                     // 1: this window can run in the scatter kernel (m <= threads, rows of 2..64 faults, the LDS holds both buffers)
-    const uint32_t *adjA, *adjB;// [max_rdeg_pad/4][m_pad][4] LDS byte offset of the fault's accumulator in buffer A / B, in the walk order of
-                                //                        BpGraphDev::chk_adj; the trash slot beyond a check's degree
+    int ok;                     // 1: this window runs in the scatter kernel (a shape of bp_scatter_wide.hip covers it, rows of 2..96 faults, the LDS fit of build_scatter)
+    const uint32_t *adjA, *adjB;// [max_rdeg_pad/4 + 2][m_pad][4] LDS byte offset of the fault's accumulator, in the walk order of scatter_walk
+                                //                        (graph_layout.hip); a trash slot beyond a check's degree and in the two spare rows
     const uint32_t *deg_w;      // [m_pad/64]             per wavefront of check slots: trip count (multiple of 4) | largest degree << 8 | smallest << 16
     const uint8_t *chk_deg;     // [m_pad]                degree of the check slot (0 beyond m)
     int offA, offB, off_out, off_bmap, off_misc, lds_bytes;
@@ -57,8 +57,7 @@ struct ScatGraphDev {
     const uint32_t *k1_slot;    // [n] BpGraphDev's bit slot (the OSD workspace's row layout) -> accumulator slot of that fault
     const int32_t *wave_map;    // [wide_cpl][wide_threads / 64] the 64 consecutive check slots (index / 64) a wavefront takes in its j-th round, -1:
                                 //                        none; chosen so that the wavefronts of a workgroup walk equally many edges (slots are sorted by degree)
-    int wide_threads, wide_cpl; // 0: one check per lane (bp_scatter.hip); else the workgroup size and the checks per lane of
-                                //    qd_bp_scatter_wide_kernel (bp_scatter_wide.hip)
+    int wide_threads, wide_cpl; // the workgroup size and the checks per lane of qd_bp_scatter_wide_kernel (bp_scatter_wide.hip); (0, 0): no scatter kernel (ok = 0)
 };
 
 // The general (one message per edge) BP kernel's view: plain CSR + CSC in fault / detector order, prior LLRs in float.

@@ -65,8 +65,7 @@ enum BpPath {
     BP_LDS_EDGE,        // flooding product-sum, one message per edge, every message in LDS (qd_launch_bp_ps_lds)
     BP_HBM_EDGE,        // one message per edge in an HBM workspace (bp_general.hip): every other method / schedule, QD_FLAG_EDGE_MESSAGES, and every
                         // pair of an off-chip decoder (flooding min-sum on the grid: with the exactness certificate and the coarse-grid redo pass)
-    BP_SCATTER_WIDE,    // flooding min-sum on the LLR grid, several checks per lane (bp_scatter_wide.hip); recheck + coarse grid: gather kernel
-    BP_SCATTER,         // ... one check per lane (bp_scatter.hip); recheck + coarse grid: gather kernel
+    BP_SCATTER_WIDE,    // flooding min-sum on the LLR grid, the scatter kernel (bp_scatter_wide.hip: one or several checks per lane); recheck + coarse grid: gather kernel
     BP_GATHER_GRID,     // ... the gather kernel (bp_kernels.hip) on the fine grid, then on the coarse grid
     BP_GATHER_RAW,      // flooding min-sum on float LLRs off the grid (ms_scaling_factor != 1, QD_FLAG_RAW_LLR): the gather kernel
 };
@@ -131,7 +130,7 @@ struct qd_decoder {
     bool edge_cert = false;                    // off_chip and on the LLR grid: the edge kernel certifies its shots and the tripped ones are decoded again
     const int32_t *prior_g = nullptr;          // [n_pad] fine-grid channel LLRs of the bit slots in grid units (scatter kernels)
     float m2_limit = 0.f;
-    const uint32_t *first_pass = nullptr;      // [m_pad][8] gather pass 0 of every check slot (ScatArgs::first_pass); null: the kernel runs it (QD_BP_NO_FAST_START=1, one check per lane)
+    const uint32_t *first_pass = nullptr;      // [m_pad][8] gather pass 0 of every check slot (ScatArgs::first_pass); null: the kernel runs it (QD_BP_NO_FAST_START=1)
     DevAllocs mem;
     int profiling = 0;
     struct Span { int kind; hipEvent_t t0, t1; };   // kind 0 = BP kernel, 1 = OSD kernel(s)
@@ -155,7 +154,6 @@ struct qd_circuit {
 
 // ---- the launchers and layout functions of the kernel files
 hipError_t qd_launch_bp(const BpGraphDev &g, const DecodeArgs &a, int64_t B, hipStream_t s);
-hipError_t qd_launch_bp_scatter(const BpGraphDev &g, const ScatGraphDev &sg, const DecodeArgs &a, const ScatArgs &x, int64_t B, hipStream_t s);
 hipError_t qd_launch_bp_scatter_wide(const BpGraphDev &g, const ScatGraphDev &sg, const DecodeArgs &a, const ScatArgs &x, int64_t B, hipStream_t s);
 hipError_t qd_launch_bp_first_pass(const BpGraphDev &g, const ScatGraphDev &sg, const int32_t *prior_g, uint32_t *rec, hipStream_t s);
 hipError_t qd_launch_bp_general(const GenGraphDev &g, const BpGraphDev &bg, const DecodeArgs &a, const GenWs &w, int bp_method,

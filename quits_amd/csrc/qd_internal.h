@@ -15,7 +15,7 @@ struct ScatArgs {
     int recheck_cap;
     const uint32_t *first_pass; // [m_pad][8] what gather pass 0 finds for each check slot, the same for every shot (qd_bp_first_pass_kernel, bp_scatter_wide.hip):
                                 //   a1, a2 (float bits), argmin position, sign words 0..2, parity of all signs, LDS offset of the argmin edge's accumulator.
-                                //   null: the kernel runs pass 0 itself and the full last pass (QD_BP_NO_FAST_START, bp_scatter.hip)
+                                //   null: the kernel runs pass 0 itself and the full last pass (QD_BP_NO_FAST_START)
 };
 
 // ... and its per-chunk workspace, [index][shot] with S shots per row

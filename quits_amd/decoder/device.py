@@ -45,10 +45,10 @@ class WindowGraph:
         self.priors = pri
 
     def info(self) -> dict:
-        arr = (C.c_int32 * 12)()
-        _lib.check(self._L.qd_graph_info_ex(self._h, arr, 12))
+        arr = (C.c_int32 * 14)()
+        _lib.check(self._L.qd_graph_info_ex(self._h, arr, 14))
         keys = ("m", "n", "nnz", "max_row_weight", "max_col_weight", "bp_threads", "bp_lds_bytes", "osd_threads",
-                "osd_lds_bytes", "rank", "scatter_walk_cycles", "scatter_walk_ideal")
+                "osd_lds_bytes", "rank", "scatter_walk_cycles", "scatter_walk_ideal", "scatter_threads", "scatter_checks_per_lane")
         return dict(zip(keys, [int(x) for x in arr]))
 
     def __del__(self):

@@ -175,7 +175,7 @@ static int check(const HostGraph &h, const GraphImage &g)
         }
         const auto wmap = arr<int32_t>(g, &sc.wave_map);
         CHECK(wmap.size() == (size_t)sc.wide_cpl * (sc.wide_threads / 64));
-        for (int sw = 0; sw < m_pad / 64 && sc.wide_threads; ++sw) CHECK(std::count(wmap.begin(), wmap.end(), sw) == 1);
+        for (int sw = 0; sw < m_pad / 64; ++sw) CHECK(std::count(wmap.begin(), wmap.end(), sw) == 1);
         for (int32_t x : wmap) CHECK(x >= -1 && x < m_pad / 64);
     }
     // ---- the elimination kernels' carve-ups (the s_* layout of osd_sr.hip is not here: qd_graph_create asks that kernel file for it after this layout)

@@ -202,9 +202,8 @@ _NO_SCRATCH = [
     ("osd_sr.hip", "qd_osd0_sr_kernel", 8, "keeps ~100 spilled scalar registers in lanes of vector registers: only safe while no vector register "
                                            "is spilled (a spill-heavy build faulted on the GPU, DESIGN.md K2s)"),
     ("osd_cs.hip", "qd_osdcs_kernel", 3, "OSD-CS / OSD-E, the reference wrapper's default post-processor (bposd.py:54); the kernel it replaced spilled 648-684 B"),
-    ("bp_scatter_wide.hip", "qd_bp_scatter_wide_kernel", 6, "flooding min-sum, the headline's BP kernel"),
-    ("bp_scatter.hip", "qd_bp_scatter_kernel", 3, "flooding min-sum, one check per lane"),
-    ("bp_kernels.hip", "qd_bp_minsum_kernel", 36, "the recheck / coarse-grid pass behind the scatter kernels (VERDICT r5 weak 9: 96 instantiations with 12-16 B each)"),
+    ("bp_scatter_wide.hip", "qd_bp_scatter_wide_kernel", 9, "flooding min-sum, the headline's BP kernel; three of the nine with one check per lane"),
+    ("bp_kernels.hip", "qd_bp_minsum_kernel", 36, "the recheck / coarse-grid pass behind the scatter kernel (VERDICT r5 weak 9: 96 instantiations with 12-16 B each)"),
     ("osd_kernels.hip", "Lb0E", 8, "qd_osd0_reg_kernel<., ., false>: the shots qd_osd0_sr_kernel hands over (VERDICT r5 weak 9: 88-144 B)"),
     ("gf2_kernels.hip", "qd_", 7, "acc ^= L e, U e, the sampler, unpack, mismatch count, the hold of the two-stream driver"),
     ("lsd_kernels.hip", "qd_lsd", 4, "BP-LSD"),

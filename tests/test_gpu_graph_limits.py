@@ -192,7 +192,7 @@ def _paths(monkeypatch, which, synd, max_iter):
     st = outs["default"][1][1]
     run = st[(st >> 19) & 1 == 0]
     assert run.size and (run & 0x3FFF).min() >= 1 and (run & 0x3FFF).max() <= max_iter
-    print("%s: %s" % (which, {tag: "K1sw" if i["scatter_wide_kernel"] else ("K1s" if i["scatter_kernel"] else "K1") for tag, i in kernels.items()}))
+    print("%s: %s" % (which, {tag: "K1sw" if i["scatter_wide_kernel"] else ("K1sw, one check per lane" if i["scatter_kernel"] else "K1") for tag, i in kernels.items()}))
 
 
 @pytest.mark.parametrize("max_iter", [1, 3, 50])

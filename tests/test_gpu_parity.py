@@ -1139,7 +1139,7 @@ def test_wide_scatter_kernel_and_gather_kernel_agree(gpu, monkeypatch, scale, sh
 ])
 def test_scatter_kernel_and_gather_kernel_agree(gpu, monkeypatch, name, shots, max_iter):
     """Flooding min-sum on the LLR grid has two kernels: the scatter form (checks add their messages to integer accumulators; the
-    default where the window fits it: bp_scatter_wide.hip with two checks per lane on half the lanes, or bp_scatter.hip with one,
+    default where the window fits it: bp_scatter_wide.hip with two checks per lane on half the lanes, or with one on all of them,
     QD_SCATTER_CPL1=1) and the gather form (bp_kernels.hip, QD_NO_SCATTER=1).  All are exact, so
     hard decisions, status words (iteration counts, convergence) and the OSD outputs computed from the posteriors must be
     identical -- also when the scatter kernel's cheap exactness bound is made to fail for most shots (QD_SCATTER_M2_LIMIT), so that

@@ -86,9 +86,13 @@ WINDOWS = {
     "column_of_weight_16": (lambda: _syn("column_of_weight_16"), {"sign_mode": 1, "sc_ok": 1, "frec": 0, "unroll": 16, "off_chip": 0}),
     "rows_of_255_columns_of_16": (lambda: _syn("rows_of_255_columns_of_16"), {"sign_mode": 2, "sc_ok": 0, "frec": 0, "unroll": 16, "off_chip": 0}),
     "4100x9000_columns_of_3": (lambda: _syn("4100x9000_columns_of_3"), {"off_chip": 1, "threads": 0, "sc_ok": 0}),
+    # one check per lane without any switch: the accumulators leave no room for twice the workgroups (tests/test_gpu_bp_one_check_per_lane.py decodes them)
+    "hgp225_cardinal_r3_p0.01_W2F1_0": (lambda: golden("hgp225_cardinal_r3_p0.01", (2, 1)), {"sc_ok": 1, "threads": 256, "wide_threads": 256, "wide_cpl": 1}),
+    "410x5056_one_check_per_lane": (lambda: helpers.synthetic_window([36] * 410, 3, 4, 41001), {"sc_ok": 1, "threads": 512, "wide_threads": 512, "wide_cpl": 1}),
+    "800x10933_one_check_per_lane": (lambda: helpers.synthetic_window([40] * 800, 3, 4, 41002), {"sc_ok": 1, "threads": 1024, "wide_threads": 1024, "wide_cpl": 1}),
 }
 SWITCHES = {"QD_SCATTER_BANKS_BY_SLOT": {"sc_ok": 1}, "QD_SCATTER_WALK_GREEDY": {"sc_ok": 1}, "QD_SCATTER_NATURAL_ROUNDS": {"wide_cpl": 2},
-            "QD_SCATTER_CPL1": {"sc_ok": 1, "wide_threads": 0, "wide_cpl": 0}}
+            "QD_SCATTER_CPL1": {"sc_ok": 1, "wide_threads": 512, "wide_cpl": 1}}
 
 
 def write_window(path, H, priors):

@@ -112,7 +112,7 @@ def main():
         print("# bit pass, the %d blocks holding the %d check-state gathers of a fault: " % (len(bg), g) + ", ".join("%s %d" % (k, v) for k, v in tot.items() if v))
         print("#   per edge: %.2f fast + %.2f slow VALU = %.1f issue clk at 2 / 4 clk" % (tot["valu_fast"] / g, tot["valu_slow"] / g,
               (2 * tot["valu_fast"] + 4 * tot["valu_slow"]) / g))
-    # scatter kernel (bp_scatter.hip): the gather pass's innermost loop (four ds_read_b32 per trip) and the scatter pass's loop
+    # scatter kernel (--src bp_scatter_wide.hip --kernel qd_bp_scatter_wide_kernelILi512ELi8ELi2ELi2E): the gather pass's innermost loop (four ds_read_b32 per trip) and the scatter pass's loop
     # (ds_add_u32: two groups of four edges per trip, every block of that loop counted)
     gl = [(sum(i.startswith("ds_read_b32") for i in b["ins"]), cnt) for b, cnt in rows if b["inner"]
           and sum(i.startswith("ds_read_b32") for i in b["ins"]) >= 4 and not any(i.startswith("ds_add_u32") for i in b["ins"])]
