@@ -58,6 +58,7 @@ typedef struct qd_graph qd_graph;       /* one window's Tanner graph + priors, r
 typedef struct qd_decoder qd_decoder;   /* graph + parameters + device workspace                      */
 typedef struct qd_spmat qd_spmat;       /* sparse GF(2) matrix on the device (L_k, U_k, H for sampling) */
 typedef struct qd_circuit qd_circuit;   /* compiled circuit program of the frame sampler, on the device */
+typedef struct qd_strata qd_strata;     /* threshold table of the stratified DEM sampler, on the device */
 
 /* qd_params.reserved: run flooding min-sum in the one-message-per-edge kernel too (ldpc's own update order, prefix sums
  * instead of "total minus own").  On the LLR grid both kernels compute exactly and agree bit for bit.  Validation aid. */
@@ -96,7 +97,7 @@ typedef struct qd_params {
     double ms_scaling_factor;   /* not exposed by the reference wrapper -> ldpc default 1.0; 0 = 1-2^-it */
 } qd_params;
 
-int qd_version(void);                 /* 110 (110: qd_sample_dem_faults, qd_commit_bits, qd_fault_stats_batch; 109: qd_unpack_b8, qd_pack_b8; 108: qd_shot_flags_fold, qd_tally_batch, qd_sample_circuit_shots, qd_sample_dem_shots; 107: off-chip windows decode, QD_FLAG_OFF_CHIP, QD_POST_OSD0_OFFCHIP, no new export; 106: qd_circuit_create accepts the biased-noise opcodes Y_ERROR / PAULI_CHANNEL_1 / PAULI_CHANNEL_2, no new export; 105: qd_decoder_fast_start; 104: qd_circuit_* + qd_sample_circuit; 103: qd_decoder_post_head_start; 101: qd_graph_info wrote 12 entries; 102: 10 again + qd_graph_info_ex) */
+int qd_version(void);                 /* 111 (111: qd_strata_create, qd_strata_destroy, qd_strata_info, qd_sample_dem_strata; 110: qd_sample_dem_faults, qd_commit_bits, qd_fault_stats_batch; 109: qd_unpack_b8, qd_pack_b8; 108: qd_shot_flags_fold, qd_tally_batch, qd_sample_circuit_shots, qd_sample_dem_shots; 107: off-chip windows decode, QD_FLAG_OFF_CHIP, QD_POST_OSD0_OFFCHIP, no new export; 106: qd_circuit_create accepts the biased-noise opcodes Y_ERROR / PAULI_CHANNEL_1 / PAULI_CHANNEL_2, no new export; 105: qd_decoder_fast_start; 104: qd_circuit_* + qd_sample_circuit; 103: qd_decoder_post_head_start; 101: qd_graph_info wrote 12 entries; 102: 10 again + qd_graph_info_ex) */
 const char *qd_last_error(void);
 /* Number of visible HIP devices (0 if none): lets a host fail loudly before building anything. */
 int qd_device_count(void);
@@ -322,6 +323,30 @@ int qd_commit_bits(const uint32_t *d_err_bits, int64_t err_stride_words, int32_t
 int qd_fault_stats_batch(const uint32_t *d_faults, const uint32_t *d_corr, int64_t stride_words, int32_t nbits, const uint8_t *d_residual,
                          int64_t res_stride, int32_t m, const uint64_t *d_fail_mask, int64_t B, int64_t shot0, int64_t *d_hist,
                          int64_t *d_counts, uint64_t *d_best, void *stream);
+
+/* ---- stratified input: shots of the detector error model CONDITIONED on exactly k faults firing (subset sampling).  Stands in for
+ *      rejection -- drawing `sampler.sample(shots)` (simulation.py:23-27) until a shot happens to hold k faults, which Stim could not even
+ *      tell -- where P(|E| = k) is 1e-14.  No reference counterpart.
+ *      quits_amd/strata.py states the law and computes the table: thresholds[j * (kmax + 1) + r] = floor(q[j][r] 2^32), q[j][r] the probability
+ *      that fault j is included when r faults are still to place among j .. n - 1; column r = 0 must be 0 (QD_EINVAL otherwise), states no
+ *      walk reaches hold any value.  1 <= n, 0 <= kmax <= 255 (the last bin of QD_FAULT_HIST).  The table is copied to the device, n * (kmax + 1)
+ *      words in HBM: 9.7 MB for 9 480 faults at kmax = 255. */
+int qd_strata_create(int32_t n, int32_t kmax, const uint32_t *thresholds, int32_t device, qd_strata **out);
+void qd_strata_destroy(qd_strata *s);
+/* info[4] = {n, kmax, bytes of the table on the device, device} */
+int qd_strata_info(const qd_strata *s, int64_t *info);
+/* Row b = shot d_shots[b] (shot0 + b where d_shots is NULL) with exactly d_k[b] faults (int32 [B] on the device: one batch may mix strata).
+ * The walk: faults in ascending index, r = d_k[b] at the start; fault j is included iff r > 0 and (word < thresholds[j][r] or n - j == r),
+ * word = word (j & 3) of Philox4x32-10(key = (seed lo, seed hi), counter = (s lo, s hi, j >> 2, 2)) -- qd_sample_dem's last counter word is 0,
+ * qd_sample_circuit's 1 -- and an included fault lowers r by one.  So a row depends on (seed, shot, k) alone.  d_det, d_obs, d_fault_bits: the
+ * layout of qd_sample_dem_faults (the first m / nobs bytes and ceil(n / 32) words of a row are written, padding bits 0, nothing else is touched).
+ * A d_k[b] outside 0 .. min(kmax, n) is CLAMPED into that range by the kernel (the Python layer refuses it before the launch).
+ * One lane per shot, 64 shots of a wavefront walking j together; their detector and observable bits sit in LDS, ceil(m / 32) + ceil(nobs / 32)
+ * words per shot: QD_ECAPACITY beyond 64 KiB per wavefront.  B = 0: QD_OK whatever the pointers.  QD_EINVAL: a null argument (d_k included),
+ * strides too small, negative shot0, Ht->nrows != n.  Asynchronous on `stream`: nothing is uploaded, nothing waited for. */
+int qd_sample_dem_strata(const qd_strata *strata, const qd_spmat *Ht, const qd_spmat *Lt, uint64_t seed, int64_t shot0, const int64_t *d_shots,
+                         const int32_t *d_k, int64_t B, uint8_t *d_det, int64_t det_stride, uint8_t *d_obs, int64_t obs_stride,
+                         uint32_t *d_fault_bits, int64_t fault_stride_words, void *stream);
 
 /* ---- circuit-level input: a Pauli-frame simulation of the circuit itself (what stim's compile_detector_sampler().sample(...,
  *      separate_observables=True) returns, simulation.py:8-28), without gauge randomisation: exact when every detector and observable

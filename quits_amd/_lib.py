@@ -52,6 +52,7 @@ EXPORTS = [
     "qd_shot_flags_fold", "qd_tally_batch", "qd_sample_circuit_shots", "qd_sample_dem_shots",
     "qd_unpack_b8", "qd_pack_b8",
     "qd_sample_dem_faults", "qd_commit_bits", "qd_fault_stats_batch",
+    "qd_strata_create", "qd_strata_destroy", "qd_strata_info", "qd_sample_dem_strata",
 ]
 
 
@@ -128,6 +129,12 @@ def load():
         L.qd_sample_dem_faults.argtypes = [vp, vp, vp, u64, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
         L.qd_commit_bits.argtypes = [vp, i64, i32, i64, vp, i64, i64, vp]
         L.qd_fault_stats_batch.argtypes = [vp, vp, i64, i32, vp, i64, i32, vp, i64, i64, vp, vp, vp, vp]
+    if hasattr(L, "qd_strata_create"):              # (library version 111; an older library named by QUITS_AMD_LIB samples independent faults as before)
+        L.qd_strata_create.argtypes = [i32, i32, vp, i32, C.POINTER(vp)]
+        L.qd_strata_destroy.argtypes = [vp]
+        L.qd_strata_destroy.restype = None
+        L.qd_strata_info.argtypes = [vp, vp]
+        L.qd_sample_dem_strata.argtypes = [vp, vp, vp, u64, i64, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp]
     _lib = L
     return L
 
@@ -155,6 +162,13 @@ def require_faults(L):
     """The entry points of library version 110 (sampled faults, committed corrections, fault statistics): a clear error from an older library."""
     if not hasattr(L, "qd_commit_bits"):
         raise RuntimeError("quits_amd: %s is version %d; fault-level outputs need >= 110 -- rebuild it" % (LIB_PATH, L.qd_version()))
+    return L
+
+
+def require_strata(L):
+    """The entry points of library version 111 (stratified DEM sampling): a clear error from an older library."""
+    if not hasattr(L, "qd_strata_create"):
+        raise RuntimeError("quits_amd: %s is version %d; stratified sampling needs >= 111 -- rebuild it" % (LIB_PATH, L.qd_version()))
     return L
 
 

@@ -152,6 +152,13 @@ struct qd_circuit {
     DevAllocs mem;
 };
 
+struct qd_strata {
+    int device = 0;
+    int n = 0, kmax = 0;
+    const uint32_t *thr = nullptr;     // [n][kmax + 1]
+    DevAllocs mem;
+};
+
 // ---- the launchers and layout functions of the kernel files
 hipError_t qd_launch_bp(const BpGraphDev &g, const DecodeArgs &a, int64_t B, hipStream_t s);
 hipError_t qd_launch_bp_scatter_wide(const BpGraphDev &g, const ScatGraphDev &sg, const DecodeArgs &a, const ScatArgs &x, int64_t B, hipStream_t s);
@@ -203,6 +210,10 @@ hipError_t qd_launch_commit_bits(const uint32_t *err, int64_t err_stride, int nb
                                  hipStream_t s);
 hipError_t qd_launch_fault_stats(const uint32_t *faults, const uint32_t *corr, int64_t stride, int nbits, const uint8_t *residual, int64_t res_stride,
                                  int m, const uint64_t *fail_mask, int64_t B, int64_t shot0, int64_t *hist, int64_t *counts, uint64_t *best, hipStream_t s);
+// strata_sampler.hip: the stratified DEM sampler (rows with a prescribed number of faults)
+hipError_t qd_launch_sample_strata(const SpmatDev &Ht, const SpmatDev &Lt, const uint32_t *thr, int kmax, uint64_t seed, int64_t shot0,
+                                   const int64_t *shot_list, const int32_t *kk, int64_t B, int m, int nobs, uint8_t *det, int64_t det_stride,
+                                   uint8_t *obs, int64_t obs_stride, uint32_t *fault_bits, int64_t fault_stride, hipStream_t s);
 // experiment.hip: the flag byte per shot and the tallies of a memory experiment
 hipError_t qd_launch_shot_flags(const int32_t *status, int64_t B, uint8_t *flags, hipStream_t s);
 hipError_t qd_launch_tally(const uint8_t *pred, int64_t pred_stride, const uint8_t *obs, int64_t obs_stride, int k, int64_t B,

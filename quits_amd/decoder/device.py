@@ -428,6 +428,84 @@ class DemSampler:
         return self._sample_with_faults(idx, int(idx.shape[0]), seed, 0, fault_bits)
 
 
+class StratifiedDemSampler:
+    """Device-side sampler of the detector error model conditioned on the number of faults (qd_sample_dem_strata): row b holds exactly ks[b]
+    faults, drawn from the model's exact conditional law.  quits_amd/strata.py states the law, the random stream and the threshold table
+    (computed here once, for 0 .. kmax faults, and kept in device memory); `pmf[k]` = P(|E| = k) and `tail` = P(|E| > kmax) weigh the strata.
+    Returns what DemSampler.sample_faults returns."""
+
+    def __init__(self, check_matrix, observable_matrix, priors, kmax: int, device: Optional[int] = None):
+        from scipy.sparse import csr_matrix
+        from .. import strata
+        self.priors = np.ascontiguousarray(priors, dtype=np.float64)
+        self.thresholds = strata.strata_thresholds(self.priors, kmax)            # (refuses priors outside [0, 1) and kmax > 255)
+        self.kmax = int(kmax)
+        self.pmf, self.tail = strata.fault_count_pmf(self.priors, self.kmax)
+        self.Ht = GF2Matrix(csr_matrix(check_matrix).T.tocsr(), device)
+        self.Lt = GF2Matrix(csr_matrix(observable_matrix).T.tocsr(), device)
+        self.m = self.Ht.shape[1]
+        self.nobs = self.Lt.shape[1]
+        if self.priors.shape[0] != self.Ht.shape[0] or self.Lt.shape[0] != self.Ht.shape[0]:
+            raise ValueError("%d priors, %d columns of the check matrix, %d of the observable matrix" % (self.priors.shape[0], self.Ht.shape[0], self.Lt.shape[0]))
+        L = _lib.require_strata(_lib.require_faults(self.Ht._L))
+        h = C.c_void_p()
+        _lib.check(L.qd_strata_create(self.nfaults, self.kmax, self.thresholds.ctypes.data_as(C.c_void_p), self.Ht.device, C.byref(h)))
+        self._h = h
+        self._L = L
+
+    @property
+    def nfaults(self) -> int:
+        return self.Ht.shape[0]
+
+    def info(self) -> dict:
+        arr = (C.c_int64 * 4)()
+        _lib.check(self._L.qd_strata_info(self._h, arr))
+        return dict(zip(("faults", "kmax", "table_bytes", "device"), [int(x) for x in arr]))
+
+    def _sample(self, idx, shots, ks, seed, shot0, fault_bits):
+        from .. import strata
+        torch = _torch()
+        if isinstance(ks, torch.Tensor):
+            ks = ks.cpu().numpy()
+        k = torch.from_numpy(strata.check_ks(ks, shots, self.priors, self.kmax)).to("cuda")
+        words = (self.nfaults + 31) // 32
+        det = torch.empty((shots, self.m), dtype=torch.uint8, device="cuda")
+        obs = torch.empty((shots, self.nobs), dtype=torch.uint8, device="cuda")
+        if fault_bits is None:
+            fault_bits = torch.empty((shots, words), dtype=torch.int32, device="cuda")
+        assert fault_bits.is_cuda and fault_bits.dtype == torch.int32 and fault_bits.dim() == 2 and fault_bits.shape[0] == shots
+        assert fault_bits.shape[1] >= words and (fault_bits.shape[1] <= 1 or fault_bits.stride(1) == 1)
+        fs = fault_bits.stride(0) if shots > 1 else max(fault_bits.stride(0), fault_bits.shape[1])
+        _lib.check(self._L.qd_sample_dem_strata(self._h, self.Ht._h, self.Lt._h, C.c_uint64(int(seed) & (2 ** 64 - 1)), int(shot0),
+                                                C.c_void_p(0) if idx is None else _ptr(idx), _ptr(k), shots, _ptr(det), det.stride(0), _ptr(obs),
+                                                obs.stride(0), _ptr(fault_bits), fs, _stream_ptr()))
+        return det, obs, fault_bits
+
+    def sample_faults(self, ks, seed: int, shot0: int = 0, fault_bits=None, shots: Optional[int] = None):
+        """(det, obs, fault_bits) of shots shot0 .. shot0 + shots - 1 of `seed`'s stream, row b with ks[b] faults.  ks: an int array (or int
+        tensor) of length `shots`, or one int for every row -- then `shots` says how many rows (default 1).  Every count must lie in
+        0 .. min(kmax, number of faults with p > 0): ValueError otherwise.  fault_bits: as in DemSampler.sample_faults."""
+        if shots is None:
+            shots = 1 if np.ndim(ks) == 0 else len(ks)
+        if int(shot0) < 0:
+            raise ValueError("shot0 must not be negative")
+        return self._sample(None, int(shots), ks, seed, shot0, fault_bits)
+
+    def sample_shots_faults(self, indices, ks, seed: int, fault_bits=None):
+        """Row b = shot indices[b] with ks[b] faults (ks: one int for all, or one per row): what `sample_faults(ks[b], seed, shot0=indices[b])`
+        returns.  `indices`: an int64 cuda tensor or any integer sequence; any order, repeats allowed."""
+        idx = _shot_indices(indices)
+        return self._sample(idx, int(idx.shape[0]), ks, seed, 0, fault_bits)
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            try:
+                self._L.qd_strata_destroy(self._h)
+            except Exception:
+                pass
+            self._h = None
+
+
 class CircuitSampler:
     """Device-side circuit-level sampler (qd_sample_circuit): a Pauli-frame simulation of the circuit, what the reference gets from
     `circuit.compile_detector_sampler().sample(shots, separate_observables=True)` (simulation.py:8-28).  Same surface as DemSampler.

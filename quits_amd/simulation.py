@@ -10,6 +10,9 @@
   get_fault_spectrum                            the same experiment on DEM-sampled shots with the faults in view: shots and failures by the
                                                 number of sampled faults, the residual E xor C of the failing shots, the lightest one seen
   replay_faults                                 which faults fired in given shots of the DEM sampler
+  get_stratified_pL                             the same experiment on shots with a prescribed number of faults (subset sampling): f(k) where
+                                                independent faults put no mass, pL = sum_k P(|E| = k) f(k) with an explicit truncation bound
+  replay_strata_faults                          the fault sets of given shots of a stratum
 
 `get_codecap_pL` keeps the reference's signature and its random stream (`np.random.seed(seed)` followed by one
 `np.random.binomial(1, p, n)` per trial), so a given seed produces the same noise vectors as the reference.  With a plug-in
@@ -433,4 +436,166 @@ def replay_faults(circuit, shot_indices, seed):
     _lib.require_faults(_lib.require_experiment(_lib.require_gpu()))
     smp = _make_sampler(_as_circuit(circuit), "dem")
     bits = smp.sample_shots_faults(shot_indices, int(seed))[2].cpu().numpy()
+    return np.unpackbits(np.ascontiguousarray(bits).view(np.uint8), axis=1, bitorder="little")[:, :smp.nfaults].astype(bool)
+
+
+# ---- the same experiment, stratified by the number of faults -----------------------------------------------------------------------------
+@dataclasses.dataclass
+class StratifiedResult:
+    """What `get_stratified_pL` returns.  shots_by_faults[k], errors_by_faults[k] (int64 [256]): shots drawn with exactly k faults and the
+    failing ones among them; pmf[k] = P(|E| = k) under the detector error model (float64 [256]), tail = P(|E| > 255).
+    pL = sum over the sampled k of pmf_k f_k, f_k = errors_k / shots_k; sigma = sqrt(sum pmf_k^2 f_k (1 - f_k) / shots_k);
+    unsampled_mass = the pmf of the strata without shots + tail, so that pL <= truth <= pL + unsampled_mass (up to sigma).
+    sigma adds the strata's variances, as for independent strata.  The strata of one seed share their Philox words -- shot s of stratum k and
+    of stratum k + 1 make the same draws against neighbouring thresholds -- so their f are positively correlated and sigma understates the spread
+    of a pL summed over many strata; sigma_max = sum pmf_k sqrt(f_k (1 - f_k) / shots_k) bounds it whatever the correlation.
+    residual_weight_hist, residual_shots, failing_residual_shots: as in FaultSpectrumResult.  lightest: (weight, k, shot) of the lightest
+    undetectable residual E xor C seen -- ties to the smaller k, then the smaller shot -- or None;
+    `replay_strata_faults(circuit, k, [shot], seed)` regenerates its fault set."""
+    shots_by_faults: np.ndarray
+    errors_by_faults: np.ndarray
+    pmf: np.ndarray
+    tail: float
+    pL: float
+    sigma: float
+    unsampled_mass: float
+    residual_weight_hist: np.ndarray
+    residual_shots: int
+    failing_residual_shots: int
+    lightest: object
+    seed: int = 0
+    batch: int = 0
+    seconds: float = 0.0
+    sigma_max: float = 0.0
+
+    def failure_fraction(self):
+        """f(k) = errors_by_faults[k] / shots_by_faults[k], float64 [256]; NaN where stratum k has no shots."""
+        s = self.shots_by_faults.astype(np.float64)
+        return np.divide(self.errors_by_faults.astype(np.float64), s, out=np.full(s.shape, np.nan), where=s > 0)
+
+    @classmethod
+    def from_counts(cls, shots_by_faults, errors_by_faults, pmf, tail, residual_weight_hist=None, residual_shots=0, failing_residual_shots=0,
+                    lightest=None, seed=0, batch=0, seconds=0.0):
+        from .strata import estimate
+        s = np.asarray(shots_by_faults, dtype=np.int64).copy()
+        e = np.asarray(errors_by_faults, dtype=np.int64).copy()
+        pmf = np.asarray(pmf, dtype=np.float64).copy()
+        pL, sigma, unsampled = estimate(s, e, pmf, tail)
+        rw = np.zeros(s.shape, np.int64) if residual_weight_hist is None else np.asarray(residual_weight_hist, dtype=np.int64).copy()
+        on = s[:pmf.shape[0]] > 0
+        f = e[:pmf.shape[0]][on] / s[:pmf.shape[0]][on]
+        sigma_max = float(np.sum(pmf[on] * np.sqrt(f * (1.0 - f) / s[:pmf.shape[0]][on])))
+        return cls(s, e, pmf, float(tail), pL, sigma, unsampled, rw, int(residual_shots), int(failing_residual_shots),
+                   None if lightest is None else tuple(int(x) for x in lightest), int(seed), int(batch), float(seconds), sigma_max)
+
+
+def _strata_plan(shots_per_weight):
+    """[(k, N_k), ...] ascending in k, the strata with N_k > 0 of a mapping k -> N_k; ValueError on a k outside 0 .. 255 or a negative count."""
+    from .strata import KMAX_LIMIT
+    out = []
+    for k, nk in sorted((int(k), int(nk)) for k, nk in dict(shots_per_weight).items()):
+        if k < 0 or k > KMAX_LIMIT:
+            raise ValueError("stratum %d outside 0 .. %d (the last bin of the fault histograms)" % (k, KMAX_LIMIT))
+        if nk < 0:
+            raise ValueError("stratum %d: negative shot count" % k)
+        if nk > 1 << 40:
+            raise ValueError("shot indices must stay below 2^40")
+        if nk:
+            out.append((k, nk))
+    return out
+
+
+def get_stratified_pL(circuit, hz, lz, W, F, shots_per_weight, max_iter=2, osd_order=0, bp_method='product_sum', schedule='serial',
+                      osd_method='osd_cs', *, seed=0, batch=None):
+    """`get_fault_spectrum` on shots that hold a prescribed number of faults: for every k of the mapping `shots_per_weight` (k -> N_k),
+    shots 0 .. N_k - 1 of stratum k's stream are drawn from the detector error model conditioned on |E| = k
+    (decoder.device.StratifiedDemSampler), decoded with their space-time correction, tallied and binned exactly as there -- same cached
+    plan, same decoder keywords, nothing per shot on the host.  f(k) is thereby measured where independent faults put no mass (the light
+    sets that bound the distance, the heavy tail at low p), and pL = sum_k P(|E| = k) f(k) follows with the bound of StratifiedResult.
+    A row depends on (seed, shot, k) alone: the result does not depend on `batch`.
+
+    Returns a StratifiedResult."""
+    import time
+    import warnings
+    from . import _lib
+    from . import strata as st
+    from .decoder.base import detector_error_model_to_matrix, window_count
+    from .decoder.bposd import BpOsdDecoder
+    from .decoder.plan import cached_circuit_plan
+    if F == 0:
+        raise ValueError("Input parameter F cannot be zero.")
+    todo = _strata_plan(shots_per_weight)
+    _lib.require_strata(_lib.require_faults(_lib.require_experiment(_lib.require_gpu())))
+    import torch
+    from .decoder.device import FaultStats, GF2Matrix, StratifiedDemSampler, Tally
+    circ = _as_circuit(circuit)
+    H, L, priors = detector_error_model_to_matrix(circ.detector_error_model())
+    pmf, tail = st.fault_count_pmf(priors, st.KMAX_LIMIT)
+    smp = StratifiedDemSampler(H, L, priors, max([k for k, _ in todo], default=0))
+    if todo:
+        st.check_ks(np.array([k for k, _ in todo]), len(todo), priors, smp.kmax)
+    nz = hz.shape[0]
+    num_rounds = smp.m // nz - 2
+    if window_count(num_rounds, W, F)[2]:
+        warnings.warn("Window size larger than the syndrome extraction rounds: Doing whole history correction")
+    opts = {'bp_method': bp_method, 'max_iter': max_iter, 'schedule': schedule, 'osd_method': osd_method, 'osd_order': osd_order}
+    plan = cached_circuit_plan(circ, hz, W, F, num_rounds, BpOsdDecoder, BpOsdDecoder, opts, opts)
+    nobs = plan.nobs
+    if smp.nobs != nobs or np.asarray(lz.shape)[0] != nobs:
+        raise ValueError("the circuit has %d observables, lz %d rows, the window plan commits %d" % (smp.nobs, lz.shape[0], nobs))
+    if plan.nfaults != smp.nfaults:
+        raise ValueError("the windows commit %d faults, the detector error model has %d" % (plan.nfaults, smp.nfaults))
+    if batch is None:
+        batch = max(2, int(plan.lanes) if plan.pipeline else 2) * int(plan.chunk)
+    Hdev = GF2Matrix(H)
+    words = (plan.nfaults + 31) // 32
+    shots_by = np.zeros(_lib.FAULT_HIST, np.int64)
+    errors_by = np.zeros(_lib.FAULT_HIST, np.int64)
+    rw = np.zeros(_lib.FAULT_HIST, np.int64)
+    res_shots = fail_res_shots = 0
+    lightest = None
+    with plan.in_use():
+        strata_stats = []
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for k, nk in todo:
+            tally, fstats = Tally(nobs), FaultStats()                  # per stratum: the lightest residual is then known with its k
+            for shot0, n in experiment_batches(nk, batch):
+                det, obs, faults = smp.sample_faults(k, seed, shot0, shots=n)
+                corr = torch.empty((n, words), dtype=torch.int32, device="cuda")
+                pred = plan.decode(det, None, corr)
+                mask = torch.empty(((n + 63) // 64,), dtype=torch.int64, device="cuda")
+                tally.add(pred, obs, None, mask)
+                Hdev.xor_apply(corr, det, accumulate=True)             # det becomes the residual H C xor det in place
+                fstats.add(faults, corr, plan.nfaults, det, mask, shot0)
+            strata_stats.append((k, nk, tally, fstats))
+        torch.cuda.synchronize()
+        seconds = time.perf_counter() - t0
+        for k, nk, tally, fstats in strata_stats:
+            hist, counts, best = fstats.result()
+            tc = tally.counts()
+            if int(tc[0]) != nk or int(counts[0]) != nk or int(tc[1]) != int(counts[1]):
+                raise RuntimeError("stratum %d: %d shots asked for, the tally counted %d (%d failing), the fault statistics %d (%d failing)"
+                                   % (k, nk, tc[0], tc[1], counts[0], counts[1]))
+            if int(hist[0][k]) != nk or int(hist[1][k]) != int(counts[1]):
+                raise RuntimeError("stratum %d: the sampled rows do not all hold %d faults (histogram %s)" % (k, k, np.flatnonzero(hist[0]).tolist()))
+            shots_by[k], errors_by[k] = nk, int(counts[1])
+            rw += hist[2]
+            res_shots += int(counts[2])
+            fail_res_shots += int(counts[3])
+            if best is not None and (lightest is None or best[0] < lightest[0]):
+                lightest = (int(best[0]), k, int(best[1]))
+    return StratifiedResult.from_counts(shots_by, errors_by, pmf, tail, rw, res_shots, fail_res_shots, lightest, seed, _batch_step(batch), seconds)
+
+
+def replay_strata_faults(circuit, k, shot_indices, seed):
+    """The fault sets of the given shots of stratum k of `seed`'s stream (get_stratified_pL's): numpy bool [len(shot_indices), nfaults] with
+    exactly k ones per row, column j = column j of detector_error_model_to_matrix(circuit)."""
+    from . import _lib
+    from .decoder.base import detector_error_model_to_matrix
+    from .decoder.device import StratifiedDemSampler
+    _lib.require_strata(_lib.require_faults(_lib.require_gpu()))
+    H, L, priors = detector_error_model_to_matrix(_as_circuit(circuit).detector_error_model())
+    smp = StratifiedDemSampler(H, L, priors, int(k))
+    bits = smp.sample_shots_faults(shot_indices, int(k), int(seed))[2].cpu().numpy()
     return np.unpackbits(np.ascontiguousarray(bits).view(np.uint8), axis=1, bitorder="little")[:, :smp.nfaults].astype(bool)
