@@ -53,6 +53,8 @@ extern "C" {
 #define QD_STATUS_OSD (1 << 17)         /* OSD post-processing produced the output                    */
 #define QD_STATUS_INCONSISTENT (1 << 18)/* OSD: syndrome outside the column space of the window matrix */
 #define QD_STATUS_ZERO (1 << 19)        /* all-zero syndrome short-circuit                            */
+#define QD_STATUS_RELAY_LEG_SHIFT 20    /* Relay-BP (qd_decoder_create_relay): bits 20..29 = the leg that produced the returned candidate */
+#define QD_STATUS_RELAY_LEG_MASK (0x3FF << QD_STATUS_RELAY_LEG_SHIFT)   /* (no candidate: the last leg run) */
 
 typedef struct qd_graph qd_graph;       /* one window's Tanner graph + priors, resident on one device */
 typedef struct qd_decoder qd_decoder;   /* graph + parameters + device workspace                      */
@@ -97,7 +99,7 @@ typedef struct qd_params {
     double ms_scaling_factor;   /* not exposed by the reference wrapper -> ldpc default 1.0; 0 = 1-2^-it */
 } qd_params;
 
-int qd_version(void);                 /* 111 (111: qd_strata_create, qd_strata_destroy, qd_strata_info, qd_sample_dem_strata; 110: qd_sample_dem_faults, qd_commit_bits, qd_fault_stats_batch; 109: qd_unpack_b8, qd_pack_b8; 108: qd_shot_flags_fold, qd_tally_batch, qd_sample_circuit_shots, qd_sample_dem_shots; 107: off-chip windows decode, QD_FLAG_OFF_CHIP, QD_POST_OSD0_OFFCHIP, no new export; 106: qd_circuit_create accepts the biased-noise opcodes Y_ERROR / PAULI_CHANNEL_1 / PAULI_CHANNEL_2, no new export; 105: qd_decoder_fast_start; 104: qd_circuit_* + qd_sample_circuit; 103: qd_decoder_post_head_start; 101: qd_graph_info wrote 12 entries; 102: 10 again + qd_graph_info_ex) */
+int qd_version(void);                 /* 112 (112: qd_decoder_create_relay, QD_STATUS_RELAY_LEG_*; 111: qd_strata_create, qd_strata_destroy, qd_strata_info, qd_sample_dem_strata; 110: qd_sample_dem_faults, qd_commit_bits, qd_fault_stats_batch; 109: qd_unpack_b8, qd_pack_b8; 108: qd_shot_flags_fold, qd_tally_batch, qd_sample_circuit_shots, qd_sample_dem_shots; 107: off-chip windows decode, QD_FLAG_OFF_CHIP, QD_POST_OSD0_OFFCHIP, no new export; 106: qd_circuit_create accepts the biased-noise opcodes Y_ERROR / PAULI_CHANNEL_1 / PAULI_CHANNEL_2, no new export; 105: qd_decoder_fast_start; 104: qd_circuit_* + qd_sample_circuit; 103: qd_decoder_post_head_start; 101: qd_graph_info wrote 12 entries; 102: 10 again + qd_graph_info_ex) */
 const char *qd_last_error(void);
 /* Number of visible HIP devices (0 if none): lets a host fail loudly before building anything. */
 int qd_device_count(void);
@@ -129,6 +131,26 @@ int qd_graph_info_ex(const qd_graph *g, int32_t *info, int32_t n_entries);
 /* ---- decoder: replaces BpOsdDecoder.__init__'s parameter half. */
 int qd_decoder_create(const qd_graph *g, const qd_params *params, qd_decoder **out);
 void qd_decoder_destroy(qd_decoder *d);
+
+/* ---- Relay-BP (after Mueller et al. 2025): flooding min-sum run as a chain of legs in which fault j mixes its previous marginal into its
+ *      prior with a memory strength gamma_j; every leg that reproduces the syndrome yields a candidate, the lightest is returned.  The
+ *      definition, bit for bit, is quits_amd/relay.py (relay_mirror).  No reference counterpart (ldpc has no such decoder).
+ *      Leg 0: pre_iter iterations with gamma_j = gamma0; leg r = 1 .. num_sets: set_max_iter iterations with gamma_j = gammas[r - 1][j];
+ *      the decode stops after stop_nconv candidates or the last leg. */
+typedef struct qd_relay_params {
+    int32_t pre_iter, num_sets, set_max_iter, stop_nconv;   /* >= 1, 0 .. 1023, >= 1, >= 1; pre_iter + num_sets * set_max_iter <= 16383 */
+    float gamma0;
+    int32_t reserved;                                       /* 0 */
+} qd_relay_params;
+/* A decoder whose stage 1 is qd_bp_relay_kernel (bp_relay.hip) and whose stage 2 is params->osd_method's post-processor, unchanged, over the
+ * shots that found no candidate (osd_off: they return their last hard decision).  `gammas`: HOST array [num_sets][n], fault order, copied
+ * (may be NULL when num_sets = 0); every value finite and |gamma| < 1.5.  params must name QD_BP_MINIMUM_SUM + QD_SCHEDULE_PARALLEL and
+ * no flag bits; params->max_iter is ignored; ms_scaling_factor keeps its meaning (0: 1 - 2^-t, t counted within the leg).  QD_EINVAL
+ * otherwise.  QD_ECAPACITY: the relay state -- the gather kernel's LDS layout + 4 bytes per fault + the candidate's bits -- does not fit
+ * the CU's LDS (off-chip windows included).  The channel LLRs stay float32(log((1 - p) / p)): qd_decoder_info reports grid -1.
+ * Status word: iterations = the total over all legs; QD_STATUS_CONVERGED iff a candidate was found (or QD_STATUS_ZERO); the leg bits above;
+ * QD_STATUS_COARSE_GRID and QD_STATUS_INEXACT are never set. */
+int qd_decoder_create_relay(const qd_graph *g, const qd_params *params, const qd_relay_params *relay, const float *gammas, qd_decoder **out);
 /* Arithmetic of this decoder.  info[0] = k: the channel LLRs log((1-p)/p) (computed in double, as ldpc does) are rounded to
  * the nearest multiple of 2^-k before BP starts; -1 = not rounded (product-sum, ms_scaling_factor != 1, QD_FLAG_RAW_LLR).
  * Flooding min-sum with ms_scaling_factor = 1 only adds, subtracts, negates and compares messages, so on such a grid

@@ -23,6 +23,8 @@ STATUS_CONVERGED = 1 << 16
 STATUS_OSD = 1 << 17
 STATUS_INCONSISTENT = 1 << 18
 STATUS_ZERO = 1 << 19
+STATUS_RELAY_LEG_SHIFT = 20                                             # Relay-BP: bits 20..29 = the leg of the returned candidate
+STATUS_RELAY_LEG_MASK = 0x3FF << STATUS_RELAY_LEG_SHIFT
 SHOT_POST, SHOT_INCONSISTENT, SHOT_INEXACT, SHOT_COARSE = 1, 2, 4, 8     # QD_SHOT_*: the flag byte qd_shot_flags_fold keeps per shot
 SHOT_FLAG_NAMES = ("post", "inconsistent", "inexact", "coarse")         # ... bit j <-> name j
 TALLY_HEAD = 10                                                         # QD_TALLY_HEAD
@@ -33,6 +35,11 @@ class QdParams(C.Structure):
     _fields_ = [("bp_method", C.c_int32), ("schedule", C.c_int32), ("max_iter", C.c_int32),
                 ("osd_method", C.c_int32), ("osd_order", C.c_int32), ("reserved", C.c_int32),
                 ("ms_scaling_factor", C.c_double)]
+
+
+class QdRelayParams(C.Structure):
+    _fields_ = [("pre_iter", C.c_int32), ("num_sets", C.c_int32), ("set_max_iter", C.c_int32), ("stop_nconv", C.c_int32),
+                ("gamma0", C.c_float), ("reserved", C.c_int32)]
 
 
 class QdError(RuntimeError):
@@ -53,6 +60,7 @@ EXPORTS = [
     "qd_unpack_b8", "qd_pack_b8",
     "qd_sample_dem_faults", "qd_commit_bits", "qd_fault_stats_batch",
     "qd_strata_create", "qd_strata_destroy", "qd_strata_info", "qd_sample_dem_strata",
+    "qd_decoder_create_relay",
 ]
 
 
@@ -135,6 +143,8 @@ def load():
         L.qd_strata_destroy.restype = None
         L.qd_strata_info.argtypes = [vp, vp]
         L.qd_sample_dem_strata.argtypes = [vp, vp, vp, u64, i64, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp]
+    if hasattr(L, "qd_decoder_create_relay"):       # (library version 112; an older library named by QUITS_AMD_LIB decodes with BP + OSD / LSD as before)
+        L.qd_decoder_create_relay.argtypes = [vp, C.POINTER(QdParams), C.POINTER(QdRelayParams), vp, C.POINTER(vp)]
     _lib = L
     return L
 
@@ -169,6 +179,13 @@ def require_strata(L):
     """The entry points of library version 111 (stratified DEM sampling): a clear error from an older library."""
     if not hasattr(L, "qd_strata_create"):
         raise RuntimeError("quits_amd: %s is version %d; stratified sampling needs >= 111 -- rebuild it" % (LIB_PATH, L.qd_version()))
+    return L
+
+
+def require_relay(L):
+    """The entry point of library version 112 (Relay-BP): a clear error from an older library."""
+    if not hasattr(L, "qd_decoder_create_relay"):
+        raise RuntimeError("quits_amd: %s is version %d; Relay-BP needs >= 112 -- rebuild it" % (LIB_PATH, L.qd_version()))
     return L
 
 

@@ -142,6 +142,50 @@ extern "C" int qd_decoder_create(const qd_graph *g, const qd_params *p, qd_decod
     return QD_OK;
 }
 
+// Relay-BP: the decoder qd_decoder_create makes for flooding min-sum on float LLRs (its post-processor, workspace and stage 2 as they are), with
+// qd_bp_relay_kernel as its stage 1
+extern "C" int qd_decoder_create_relay(const qd_graph *g, const qd_params *p, const qd_relay_params *r, const float *gammas, qd_decoder **out)
+{
+    if (!g || !p || !r || !out) return qd_fail(QD_EINVAL, "null argument");
+    *out = nullptr;
+    if (p->bp_method != QD_BP_MINIMUM_SUM || p->schedule != QD_SCHEDULE_PARALLEL)
+        return qd_fail(QD_EINVAL, "Relay-BP is flooding min-sum: bp_method %d / schedule %d are not QD_BP_MINIMUM_SUM / QD_SCHEDULE_PARALLEL", p->bp_method, p->schedule);
+    if (p->reserved != 0 || r->reserved != 0) return qd_fail(QD_EINVAL, "Relay-BP takes no flag bits (0x%x, 0x%x)", p->reserved, r->reserved);
+    if (r->pre_iter < 1 || r->set_max_iter < 1 || r->stop_nconv < 1 || r->num_sets < 0 || r->num_sets > (QD_STATUS_RELAY_LEG_MASK >> QD_STATUS_RELAY_LEG_SHIFT))
+        return qd_fail(QD_EINVAL, "relay budgets out of range: pre_iter %d, num_sets %d, set_max_iter %d, stop_nconv %d", r->pre_iter, r->num_sets, r->set_max_iter, r->stop_nconv);
+    const long long total = (long long)r->pre_iter + (long long)r->num_sets * r->set_max_iter;
+    if (total > QD_STATUS_ITER_MASK) return qd_fail(QD_EINVAL, "%lld iterations over all legs exceed the status word's %d", total, QD_STATUS_ITER_MASK);
+    if (r->num_sets > 0 && !gammas) return qd_fail(QD_EINVAL, "num_sets = %d without a gamma table", r->num_sets);
+    const auto bad_gamma = [](float v) { return !std::isfinite(v) || std::fabs(v) >= 1.5f; };
+    if (bad_gamma(r->gamma0)) return qd_fail(QD_EINVAL, "gamma0 = %g: memory strengths must be finite with |gamma| < 1.5", (double)r->gamma0);
+    for (size_t i = 0; i < (size_t)r->num_sets * g->n; ++i)
+        if (bad_gamma(gammas[i])) return qd_fail(QD_EINVAL, "gammas[%zu][%zu] = %g: memory strengths must be finite with |gamma| < 1.5", i / g->n, i % g->n, (double)gammas[i]);
+    RelayArgs x{};
+    x.pre_iter = r->pre_iter; x.num_sets = r->num_sets; x.set_max_iter = r->set_max_iter; x.stop_nconv = r->stop_nconv; x.gamma0 = r->gamma0;
+    if (g->off_chip)
+        return qd_fail(QD_ECAPACITY, "Relay-BP keeps a shot's state in LDS: the off-chip window %d x %d (16 bytes per detector + 8 per fault > %d) does not fit", g->m,
+                       g->n, QD_LDS_BYTES);
+    if (qd_relay_layout(g->bp, &x) > QD_LDS_BYTES)
+        return qd_fail(QD_ECAPACITY, "Relay-BP state of window %d x %d: %d bytes of LDS (%d of them the min-sum layout), the CU has %d", g->m, g->n, x.lds_bytes,
+                       g->bp.lds_bytes, QD_LDS_BYTES);
+    qd_params q = *p;
+    q.reserved = QD_FLAG_RAW_LLR;                        // float LLRs as they are: no grid, nothing certified
+    q.max_iter = (int32_t)total;
+    qd_decoder *d = nullptr;
+    if (int rc = qd_decoder_create(g, &q, &d)) return rc;
+    std::vector<float> slot((size_t)std::max(1, r->num_sets) * g->bp.n_pad, 0.f);
+    for (int s = 0; s < r->num_sets; ++s)
+        for (int b = 0; b < g->n; ++b) slot[(size_t)s * g->bp.n_pad + b] = gammas[(size_t)s * g->n + g->h_bit_orig[b]];
+    if (hipSetDevice(g->device) != hipSuccess || d->mem.upload(slot, &x.gammas)) {
+        qd_decoder_destroy(d);
+        return qd_fail(QD_EHIP, "device allocation failed for the gamma table");
+    }
+    d->bp = BP_RELAY;
+    d->relay = x;
+    *out = d;
+    return QD_OK;
+}
+
 extern "C" int qd_decoder_info(const qd_decoder *d, int32_t *info)
 {
     if (!d || !info) return qd_fail(QD_EINVAL, "null argument");
@@ -373,6 +417,7 @@ static int launch_bp(qd_decoder *d, const DecodeArgs &a, int64_t B, hipStream_t 
     switch (d->bp) {
     case BP_LDS_EDGE: HIP_TRY(qd_launch_bp_ps_lds(gg, g->bp, a, B, s)); break;
     case BP_GATHER_RAW: HIP_TRY(qd_launch_bp(g->bp, a, B, s)); break;
+    case BP_RELAY: HIP_TRY(qd_launch_bp_relay(g->bp, a, d->relay, B, s)); break;
     case BP_HBM_EDGE: {
         // edge_cert (off-chip decoder on the LLR grid): the first pass parks the shots whose exactness bound tripped, the redo pass decodes them
         // on the coarse grid -- the gather kernel's rule (BP_GATHER_GRID below), chunk by chunk of the message workspace

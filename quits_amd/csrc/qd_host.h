@@ -68,6 +68,7 @@ enum BpPath {
     BP_SCATTER_WIDE,    // flooding min-sum on the LLR grid, the scatter kernel (bp_scatter_wide.hip: one or several checks per lane); recheck + coarse grid: gather kernel
     BP_GATHER_GRID,     // ... the gather kernel (bp_kernels.hip) on the fine grid, then on the coarse grid
     BP_GATHER_RAW,      // flooding min-sum on float LLRs off the grid (ms_scaling_factor != 1, QD_FLAG_RAW_LLR): the gather kernel
+    BP_RELAY,           // Relay-BP on float LLRs (qd_decoder_create_relay): qd_bp_relay_kernel (bp_relay.hip)
 };
 
 // What qd_decoder_reserve allocates for a batch size; free_ws gives all of it back
@@ -131,6 +132,7 @@ struct qd_decoder {
     const int32_t *prior_g = nullptr;          // [n_pad] fine-grid channel LLRs of the bit slots in grid units (scatter kernels)
     float m2_limit = 0.f;
     const uint32_t *first_pass = nullptr;      // [m_pad][8] gather pass 0 of every check slot (ScatArgs::first_pass); null: the kernel runs it (QD_BP_NO_FAST_START=1)
+    RelayArgs relay{};                         // BP_RELAY: budgets, the gamma table in slot order (owned by mem), the kernel's LDS layout
     DevAllocs mem;
     int profiling = 0;
     struct Span { int kind; hipEvent_t t0, t1; };   // kind 0 = BP kernel, 1 = OSD kernel(s)
@@ -165,6 +167,8 @@ hipError_t qd_launch_bp_scatter_wide(const BpGraphDev &g, const ScatGraphDev &sg
 hipError_t qd_launch_bp_first_pass(const BpGraphDev &g, const ScatGraphDev &sg, const int32_t *prior_g, uint32_t *rec, hipStream_t s);
 hipError_t qd_launch_bp_general(const GenGraphDev &g, const BpGraphDev &bg, const DecodeArgs &a, const GenWs &w, int bp_method,
                                 int schedule, int64_t shot0, int nshots, hipStream_t s, GenStagePlan *plan);
+hipError_t qd_launch_bp_relay(const BpGraphDev &g, const DecodeArgs &a, const RelayArgs &x, int64_t B, hipStream_t s);
+int qd_relay_layout(const BpGraphDev &g, RelayArgs *x);        // fills the off_* members and lds_bytes, which it returns
 hipError_t qd_launch_hold(const int32_t *count, int threshold, int microseconds, hipStream_t s);
 int qd_bp_ps_lds_bytes(const GenGraphDev &g, int max_rdeg);
 hipError_t qd_launch_bp_ps_lds(const GenGraphDev &g, const BpGraphDev &bg, const DecodeArgs &a, int64_t B, hipStream_t s);

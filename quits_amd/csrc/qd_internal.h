@@ -100,6 +100,14 @@ struct DecodeArgs {
     int status_or;              // ORed into the status word (QD_STATUS_COARSE_GRID in the redo pass)
 };
 
+// Relay-BP (bp_relay.hip): the legs' budgets, the table of memory strengths and the kernel's LDS beyond the gather kernel's layout
+struct RelayArgs {
+    int pre_iter, num_sets, set_max_iter, stop_nconv;
+    float gamma0;
+    const float *gammas;        // [num_sets][n_pad] memory strengths of legs 1.., by bit slot (null: num_sets = 0)
+    int off_marg, off_best, off_wsum, lds_bytes;   // marginals [n_pad + 1] floats, best candidate [out_words], 64-bit weight sum
+};
+
 // Workgroup-wide OR without static LDS (a static __shared__ object in front of the dynamic region can knock the
 // 16-byte alignment the ds_read_b128 gathers rely on).  `red` = 32 ints of dynamic LDS, 16-byte aligned; `phase`
 // alternates 0/1 between successive calls so a fast wave cannot overwrite flags a slow wave still reads.  One barrier.

@@ -4,6 +4,7 @@ from .base import (detector_error_model_to_matrix, dict_to_csc_matrix_column_row
 from .sliding_window import sliding_window_circuit_mem, sliding_window_phenom_mem
 from .bposd import BpOsdDecoder, sliding_window_bposd_circuit_mem, sliding_window_bposd_phenom_mem
 from .bplsd import BpLsdDecoder, sliding_window_bplsd_circuit_mem, sliding_window_bplsd_phenom_mem
+from .relaybp import RelayBpDecoder, sliding_window_relaybp_circuit_mem, sliding_window_relaybp_phenom_mem
 from .whole_history import decode_dem
 from .corrections import decode_dem_corrections, sliding_window_corrections
 
@@ -23,4 +24,7 @@ __all__ = [
     "decode_dem",              # beyond the reference's names: any detector error model over its whole history (whole_history.py)
     "sliding_window_corrections",   # ... and the corrections themselves next to the predictions (corrections.py)
     "decode_dem_corrections",
+    "RelayBpDecoder",          # Relay-BP (relaybp.py, quits_amd/relay.py): a decoder that needs no elimination
+    "sliding_window_relaybp_phenom_mem",
+    "sliding_window_relaybp_circuit_mem",
 ]

@@ -178,6 +178,39 @@ class BatchDecoder:
             self._h = None
 
 
+class RelayBatchDecoder(BatchDecoder):
+    """qd_decoder_create_relay: Relay-BP over a batch of shots for one window (csrc/bp_relay.hip; the definition is quits_amd/relay.py), then
+    `osd_method`'s post-processor over the shots that found no candidate ("osd_off": they return their last hard decision).  `decode`,
+    `info`, `profile` and the rest are BatchDecoder's.  `gammas`: float32 [cfg.num_sets, n] in fault order; None = relay_gammas(n, cfg)."""
+
+    def __init__(self, graph: WindowGraph, cfg=None, osd_method="osd_off", osd_order=0, ms_scaling_factor=1.0, gammas=None):
+        from .. import relay as _relay
+        cfg = _relay.RelayConfig() if cfg is None else cfg
+        if not isinstance(cfg, _relay.RelayConfig):
+            raise TypeError("cfg must be a RelayConfig, not %r" % type(cfg).__name__)
+        self.graph = graph
+        self.cfg = cfg
+        L = _lib.require_relay(graph._L)
+        try:
+            prm = _lib.QdParams(_lib.QD_BP["minimum_sum"], _lib.QD_SCHEDULE["parallel"], 0, _lib.QD_OSD[_norm(osd_method)], int(osd_order), 0,
+                                float(ms_scaling_factor))
+        except KeyError as exc:
+            raise ValueError("unknown decoder option %s" % exc) from exc
+        self.gammas = _relay.check_table(gammas, cfg, graph.n)
+        rp = _lib.QdRelayParams(cfg.pre_iter, cfg.num_sets, cfg.set_max_iter, cfg.stop_nconv, float(cfg.gamma0), 0)
+        h = C.c_void_p()
+        rc = L.qd_decoder_create_relay(graph._h, C.byref(prm), C.byref(rp), self.gammas.ctypes.data_as(C.c_void_p) if cfg.num_sets else C.c_void_p(0), C.byref(h))
+        if rc == -2:
+            raise NotImplementedError(L.qd_last_error().decode())
+        _lib.check(rc)
+        self._h = h
+        self._L = L
+        self.params = prm
+
+    def info(self) -> dict:
+        return dict(super().info(), bp_kernel="qd_bp_relay_kernel", total_iter=self.cfg.total_iter)
+
+
 class GF2Matrix:
     """Sparse GF(2) matrix on the device (qd_spmat), CSR."""
 

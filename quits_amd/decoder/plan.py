@@ -47,12 +47,21 @@ def set_workspace_limits(decs, general_ws_gb):
         decs[0].set_workspace_limit(int(max(0.001, general_ws_gb) * (1 << 30)))
 
 
+def _new_decoder(graph, kw):
+    """The batch decoder of a window from its device options (_kwargs_for_device): Relay-BP where they carry a RelayConfig."""
+    from .device import BatchDecoder, RelayBatchDecoder
+    if "relay" in kw:
+        kw = dict(kw)
+        return RelayBatchDecoder(graph, kw.pop("relay"), **kw)
+    return BatchDecoder(graph, **kw)
+
+
 class DeviceWindowPlan:
     """Everything the batched driver needs, resident on the GPU: per window a decoder, the commit matrix L_k, the
     hand-off matrix U_k and the first detector row."""
 
     def __init__(self, checks, commits, priors, updates, row0, nz, nobs, dict1, dict2):
-        from .device import BatchDecoder, GF2Matrix, WindowGraph
+        from .device import GF2Matrix, WindowGraph
         self.nz, self.nobs = int(nz), int(nobs)
         self.windows = []
         nwin = len(checks)
@@ -68,7 +77,7 @@ class DeviceWindowPlan:
             key = (id(checks[k]), id(priors[k]), k == nwin - 1)    # the phenomenological windows share one matrix
             if key not in cache:
                 graph = WindowGraph(checks[k], priors[k])
-                cache[key] = (graph, BatchDecoder(graph, **kw))
+                cache[key] = (graph, _new_decoder(graph, kw))
             graph, dec = cache[key]
             Lk = csr_matrix(commits[k])
             if Lk.shape[1] < graph.n:     # L_k only spans the committed columns (base.py:170)
@@ -131,12 +140,11 @@ class DeviceWindowPlan:
     def lane_decoders(self):
         """Per window, the decoders of the two-stream driver's `self.lanes` lanes, each with its own workspaces; windows that share a
         decoder share its lanes' decoders.  Lanes that are missing are built here."""
-        from .device import BatchDecoder
         if any(len(lst) < self.lanes for lst in self._lane_decs.values()):
             for w in self.windows:
                 lst = self._lane_decs[id(w["dec"])]
                 while len(lst) < self.lanes:
-                    lst.append(BatchDecoder(w["graph"], **w["kw"]))
+                    lst.append(_new_decoder(w["graph"], w["kw"]))
             if any(d.info()["edge_kernel"] for d in self.decoders()):
                 set_workspace_limits([d for lst in self._lane_decs.values() for d in lst], self.env.general_ws_gb)
         return [self._lane_decs[id(w["dec"])] for w in self.windows]
@@ -272,6 +280,9 @@ def _kwargs_for_device(d, cls):
     options and unknown names raise TypeError naming the device path (ldpc's own classes take **kwargs and may ignore them:
     refusing is the safe side of "never a silent change of algorithm")."""
     from .bplsd import BpLsdDecoder, lsd_to_device_method
+    from .relaybp import RelayBpDecoder, relay_device_kwargs
+    if isinstance(cls, type) and issubclass(cls, RelayBpDecoder):        # its own keywords: the RelayConfig fields and the post-processor
+        return relay_device_kwargs(d)
     common = ("bp_method", "schedule", "max_iter", "ms_scaling_factor")
     rates = ("error_rate", "channel_probs", "error_channel")
     d = dict(d)

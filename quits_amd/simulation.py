@@ -6,6 +6,7 @@
   get_circuit_mem_pL                            a whole memory experiment on the device: sampler -> sliding-window BP-OSD -> tallies; what
                                                 the reference's users write around the two calls above (tests/test_sliding_window.py:72-83),
                                                 without a host array per shot
+  get_relay_mem_pL                              the same experiment with the sliding-window Relay-BP decoder
   replay_shots                                  the samples of given shot indices again (both samplers are counter-based)
   get_fault_spectrum                            the same experiment on DEM-sampled shots with the faults in view: shots and failures by the
                                                 number of sampled faults, the residual E xor C of the failing shots, the lightest one seen
@@ -217,11 +218,31 @@ def get_circuit_mem_pL(circuit, hz, lz, W, F, num_trials, max_iter=2, osd_order=
         all-reduce; failing_shots stay this rank's.  With max_errors each rank stops on ceil(max_errors / world) of its own.
 
     Returns a MemExperimentResult.  `replay_shots(circuit, result.failing_shots, seed, sampler)` regenerates the failing shots."""
+    from .decoder.bposd import BpOsdDecoder
+    opts = {'bp_method': bp_method, 'max_iter': max_iter, 'schedule': schedule, 'osd_method': osd_method, 'osd_order': osd_order}
+    return _mem_experiment(circuit, hz, lz, W, F, num_trials, BpOsdDecoder, opts, seed=seed, sampler=sampler, batch=batch, max_errors=max_errors,
+                           keep_failures=keep_failures, shard=shard, distributed=distributed)
+
+
+def get_relay_mem_pL(circuit, hz, lz, W, F, num_trials, relay=None, osd_method='osd_off', osd_order=0, *, seed=0, sampler='circuit', batch=None,
+                     max_errors=None, keep_failures=4096, shard=None, distributed=False):
+    """`get_circuit_mem_pL` with the sliding-window Relay-BP decoder (decoder.sliding_window_relaybp_circuit_mem: same cached plan): `relay` is a
+    quits_amd.relay.RelayConfig (default RelayConfig()), `osd_method` / `osd_order` the post-processor of the shots no leg solves
+    ('osd_off': they keep their last hard decision).  Every other argument, the early-stop rule and the result are that function's; the
+    'post' flag counts the shots some window of which went to the post-processor."""
+    from .decoder.relaybp import RelayBpDecoder, relay_options
+    opts = relay_options(relay, osd_method, osd_order)
+    return _mem_experiment(circuit, hz, lz, W, F, num_trials, RelayBpDecoder, opts, seed=seed, sampler=sampler, batch=batch, max_errors=max_errors,
+                           keep_failures=keep_failures, shard=shard, distributed=distributed)
+
+
+def _mem_experiment(circuit, hz, lz, W, F, num_trials, decoder, opts, *, seed, sampler, batch, max_errors, keep_failures, shard, distributed):
+    """The experiment loop of get_circuit_mem_pL and get_relay_mem_pL: `decoder` is the plug-in class of both window kinds, `opts` its
+    keyword dict (the cached plan's key)."""
     import time
     import warnings
     from . import _lib
     from .decoder.base import window_count
-    from .decoder.bposd import BpOsdDecoder
     from .decoder.plan import cached_circuit_plan
     if F == 0:
         raise ValueError("Input parameter F cannot be zero.")
@@ -246,8 +267,7 @@ def get_circuit_mem_pL(circuit, hz, lz, W, F, num_trials, max_iter=2, osd_order=
     num_rounds = smp.m // nz - 2
     if window_count(num_rounds, W, F)[2]:
         warnings.warn("Window size larger than the syndrome extraction rounds: Doing whole history correction")
-    opts = {'bp_method': bp_method, 'max_iter': max_iter, 'schedule': schedule, 'osd_method': osd_method, 'osd_order': osd_order}
-    plan = cached_circuit_plan(circ, hz, W, F, num_rounds, BpOsdDecoder, BpOsdDecoder, opts, opts)
+    plan = cached_circuit_plan(circ, hz, W, F, num_rounds, decoder, decoder, opts, opts)
     k = plan.nobs
     if smp.nobs != k or np.asarray(lz.shape)[0] != k:
         raise ValueError("the circuit has %d observables, lz %d rows, the window plan commits %d" % (smp.nobs, lz.shape[0], k))
