@@ -131,7 +131,7 @@ __global__ void __launch_bounds__(64 * G, 1) qd_bp_edge_kernel(GenGraphDev g, co
         if (wv == 0) {
             uint32_t *out = a.err_bits + shot * g.out_words;
             for (int x = 0; x < g.out_words; ++x) out[x] = 0u;
-            a.status[shot] = (1 << 16) | (1 << 19) | (CERT ? a.status_or : 0);
+            a.status[shot] = QD_STATUS_CONVERGED | QD_STATUS_ZERO | (CERT ? a.status_or : 0);
         }
         active = false;
     }
@@ -484,7 +484,7 @@ __global__ void __launch_bounds__(64 * G, 1) qd_bp_edge_kernel(GenGraphDev g, co
         out[x] = word;
     }
     if (wv != 0) return;
-    a.status[shot] = iters | (converged << 16) | status_or;
+    a.status[shot] = iters | (converged * QD_STATUS_CONVERGED) | status_or;
     if (!converged && a.want_llr) {
         const int slot = atomicAdd(a.fail_count, 1);
         a.fail_list[slot] = (int32_t)shot;
@@ -544,7 +544,7 @@ __global__ void __launch_bounds__(T) qd_bp_ps_lds_kernel(GenGraphDev g, const in
     uint32_t *out = a.err_bits + shot * g.out_words;
     if (!block_or(any, 0)) {   // bposd_decoder.pyx: an all-zero syndrome returns the zero vector without running BP
         for (int x = tid; x < g.out_words; x += T) out[x] = 0u;
-        if (tid == 0) a.status[shot] = (1 << 16) | (1 << 19);
+        if (tid == 0) a.status[shot] = QD_STATUS_CONVERGED | QD_STATUS_ZERO;
         return;
     }
     for (int j = tid; j < g.n; j += T) {
@@ -667,7 +667,7 @@ __global__ void __launch_bounds__(T) qd_bp_ps_lds_kernel(GenGraphDev g, const in
             for (int j = 32 * x; j < j1; ++j) word |= ((llr[j] <= 0.f) ? 1u : 0u) << (j & 31);
             out[x] = word;
         }
-    if (tid == 0) a.status[shot] = iters | (converged << 16);
+    if (tid == 0) a.status[shot] = iters | (converged * QD_STATUS_CONVERGED);
     if (!converged && a.want_llr) {
         if (tid == 0) { const int slot = atomicAdd(a.fail_count, 1); a.fail_list[slot] = (int32_t)shot; red[32] = (uint32_t)slot; }
         __syncthreads();

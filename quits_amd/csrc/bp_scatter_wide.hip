@@ -104,7 +104,7 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
     any = qd_block_or(any, misc, NW, 0);
     if (!any) {   // bposd_decoder.pyx: an all-zero syndrome returns the zero vector without running BP
         for (int w = tid; w < g.out_words; w += T) a.err_bits[shot * g.out_words + w] = 0u;
-        if (tid == 0) a.status[shot] = (1 << 16) | (1 << 19) | a.status_or;
+        if (tid == 0) a.status[shot] = QD_STATUS_CONVERGED | QD_STATUS_ZERO | a.status_or;
         return;
     }
 
@@ -379,7 +379,7 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
         for (int k1 = tid; k1 < g.n; k1 += T) dst[k1] = (float)(*QS_LDS(cur + 4u * sg.k1_slot[k1]) + 1) * x.grid_inv;
         if (tid == 0) a.fail_list[slot] = (int32_t)shot;
     }
-    if (tid == 0) a.status[shot] = t | (converged << 16) | a.status_or;
+    if (tid == 0) a.status[shot] = t | (converged * QD_STATUS_CONVERGED) | a.status_or;
 }
 
 // ---- the first-pass table: gather pass 0 of every check slot, once per decoder (qd_decoder_create).  One wavefront per 64 consecutive check slots,

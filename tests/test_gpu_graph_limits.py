@@ -1,8 +1,8 @@
 """The decoder at the two degree limits of its ABI: qd_graph_create takes any window of row weight <= 255 (QD_MAX_ROW_DEG) and column
 weight <= 16 (QD_MAX_COL_DEG), and code that is selected by those weights runs on no fixture window (rows <= 78, columns <= 9):
 
-  * qd_bp_minsum_kernel (bp_kernels.hip): launch_bp_t's NCH = rec_words / 4 with rec_words = pad4(1 + column weight) -- weight 12..15
-    falls into `default:` (NCH = 5 with bit_thr[15] = 0), weight 16 adds the lone r4.x group; sign mode 2 finds the sign words 1..7
+  * qd_bp_minsum_kernel (bp_kernels.hip): qd_gather_dispatch's NCH = rec_words / 4 with rec_words = pad4(1 + column weight) -- weight 12..15
+    falls into the last arm (NCH = 5 with bit_thr[15] = 0), weight 16 adds the lone r4.x group; sign mode 2 finds the sign words 1..7
     of a row through the 3-bit field ((rec >> 5) & 7) - 1 of the fault record; rows of 97..255 faults (4..8 sign words) take this
     kernel as their first choice, because no scatter kernel takes rows of more than 96;
   * the scatter kernels' certificate m2_limit = (2^23 - max|prior|) / max_cdeg - 1 at max_cdeg 12..16;

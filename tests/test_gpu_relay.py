@@ -151,11 +151,13 @@ def test_negative_zero_messages(gpu):
     assert_same(err, st, ref, "negative zero")
 
 
-def test_one_leg_without_memory_is_the_float_min_sum_kernel(gpu):
+@pytest.mark.parametrize("name", list(WINDOWS))
+def test_one_leg_without_memory_is_the_float_min_sum_kernel(gpu, name):
+    """The two kernels built on csrc/bp_gather_common.h against each other: every sign mode, 2 and 5 record chunks."""
     import torch
     from quits_amd.decoder.device import BatchDecoder, WindowGraph, unpack_bits
-    H, pri = window("bb72_whole")
-    syn = shots("bb72_whole")
+    H, pri = window(name)
+    syn = shots(name)
     err, st, _ = device_decode(H, pri, syn, RelayConfig(pre_iter=30, num_sets=0, gamma0=0.0))
     wg = WindowGraph(H, pri)
     old = BatchDecoder(wg, raw_llr=True, osd_method="osd_off", max_iter=30)
