@@ -99,7 +99,7 @@ typedef struct qd_params {
     double ms_scaling_factor;   /* not exposed by the reference wrapper -> ldpc default 1.0; 0 = 1-2^-it */
 } qd_params;
 
-int qd_version(void);                 /* 112 (112: qd_decoder_create_relay, QD_STATUS_RELAY_LEG_*; 111: qd_strata_create, qd_strata_destroy, qd_strata_info, qd_sample_dem_strata; 110: qd_sample_dem_faults, qd_commit_bits, qd_fault_stats_batch; 109: qd_unpack_b8, qd_pack_b8; 108: qd_shot_flags_fold, qd_tally_batch, qd_sample_circuit_shots, qd_sample_dem_shots; 107: off-chip windows decode, QD_FLAG_OFF_CHIP, QD_POST_OSD0_OFFCHIP, no new export; 106: qd_circuit_create accepts the biased-noise opcodes Y_ERROR / PAULI_CHANNEL_1 / PAULI_CHANNEL_2, no new export; 105: qd_decoder_fast_start; 104: qd_circuit_* + qd_sample_circuit; 103: qd_decoder_post_head_start; 101: qd_graph_info wrote 12 entries; 102: 10 again + qd_graph_info_ex) */
+int qd_version(void);                 /* 113 (113: qd_decoder_relay_info, QD_RELAY_FLAG_MARGINALS_DEVICE; 112: qd_decoder_create_relay, QD_STATUS_RELAY_LEG_*; 111: qd_strata_create, qd_strata_destroy, qd_strata_info, qd_sample_dem_strata; 110: qd_sample_dem_faults, qd_commit_bits, qd_fault_stats_batch; 109: qd_unpack_b8, qd_pack_b8; 108: qd_shot_flags_fold, qd_tally_batch, qd_sample_circuit_shots, qd_sample_dem_shots; 107: off-chip windows decode, QD_FLAG_OFF_CHIP, QD_POST_OSD0_OFFCHIP, no new export; 106: qd_circuit_create accepts the biased-noise opcodes Y_ERROR / PAULI_CHANNEL_1 / PAULI_CHANNEL_2, no new export; 105: qd_decoder_fast_start; 104: qd_circuit_* + qd_sample_circuit; 103: qd_decoder_post_head_start; 101: qd_graph_info wrote 12 entries; 102: 10 again + qd_graph_info_ex) */
 const char *qd_last_error(void);
 /* Number of visible HIP devices (0 if none): lets a host fail loudly before building anything. */
 int qd_device_count(void);
@@ -140,17 +140,30 @@ void qd_decoder_destroy(qd_decoder *d);
 typedef struct qd_relay_params {
     int32_t pre_iter, num_sets, set_max_iter, stop_nconv;   /* >= 1, 0 .. 1023, >= 1, >= 1; pre_iter + num_sets * set_max_iter <= 16383 */
     float gamma0;
-    int32_t reserved;                                       /* 0 */
+    int32_t reserved;                                       /* flag bits, QD_RELAY_FLAG_*; 0 for the default choice of form */
 } qd_relay_params;
+/* qd_relay_params.reserved: keep the marginals M_j in the decoder's device-memory workspace (bp_relay_device.hip) on a window whose
+ * marginals would fit in LDS too.  Same results as the LDS form, bit for bit.  Validation aid, like QD_FLAG_EDGE_MESSAGES. */
+#define QD_RELAY_FLAG_MARGINALS_DEVICE 1
 /* A decoder whose stage 1 is qd_bp_relay_kernel (bp_relay.hip) and whose stage 2 is params->osd_method's post-processor, unchanged, over the
  * shots that found no candidate (osd_off: they return their last hard decision).  `gammas`: HOST array [num_sets][n], fault order, copied
  * (may be NULL when num_sets = 0); every value finite and |gamma| < 1.5.  params must name QD_BP_MINIMUM_SUM + QD_SCHEDULE_PARALLEL and
  * no flag bits; params->max_iter is ignored; ms_scaling_factor keeps its meaning (0: 1 - 2^-t, t counted within the leg).  QD_EINVAL
- * otherwise.  QD_ECAPACITY: the relay state -- the gather kernel's LDS layout + 4 bytes per fault + the candidate's bits -- does not fit
- * the CU's LDS (off-chip windows included).  The channel LLRs stay float32(log((1 - p) / p)): qd_decoder_info reports grid -1.
+ * otherwise, and for a bit of relay->reserved that is no QD_RELAY_FLAG_*.
+ * Two forms of one kernel, the same results bit for bit.  The LDS form keeps a shot's whole state on the CU: the gather kernel's LDS layout
+ * (16 bytes per detector + 4 per fault) + 4 more bytes per fault for the marginals + the candidate's bits.  It is taken wherever it fits
+ * the CU's 160 KB.  Where it does not, the device-marginal form is: the marginals are a row of n_pad floats per shot in the decoder's
+ * workspace (reserved and released with it, 4 n_pad bytes per shot of the batch), touched by the lane that owns the fault only, and the
+ * LDS holds the gather layout + the candidate's bits (QLP [[1020,136]] W = 3: about 190 KB -> 115 KB).  QD_ECAPACITY: that does not fit
+ * either -- the message gives both byte counts -- or the window is off-chip (the gather layout itself does not fit: "LDS" in the message).
+ * qd_decoder_relay_info reports the form.  The channel LLRs stay float32(log((1 - p) / p)): qd_decoder_info reports grid -1.
  * Status word: iterations = the total over all legs; QD_STATUS_CONVERGED iff a candidate was found (or QD_STATUS_ZERO); the leg bits above;
  * QD_STATUS_COARSE_GRID and QD_STATUS_INEXACT are never set. */
 int qd_decoder_create_relay(const qd_graph *g, const qd_params *params, const qd_relay_params *relay, const float *gammas, qd_decoder **out);
+/* info[0] = where a Relay-BP decoder keeps its marginals: 1 = LDS, 2 = device memory (0: not a Relay-BP decoder, and the rest 0 too);
+ * info[1] = dynamic LDS bytes of its kernel; info[2] = what the LDS form takes on this window, whether it fits or not; info[3] = the
+ * CU's LDS bytes, the limit both are held against.  Exactly 4 entries are written.  (Since version 113.) */
+int qd_decoder_relay_info(const qd_decoder *d, int32_t *info);
 /* Arithmetic of this decoder.  info[0] = k: the channel LLRs log((1-p)/p) (computed in double, as ldpc does) are rounded to
  * the nearest multiple of 2^-k before BP starts; -1 = not rounded (product-sum, ms_scaling_factor != 1, QD_FLAG_RAW_LLR).
  * Flooding min-sum with ms_scaling_factor = 1 only adds, subtracts, negates and compares messages, so on such a grid

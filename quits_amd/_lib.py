@@ -29,6 +29,7 @@ SHOT_POST, SHOT_INCONSISTENT, SHOT_INEXACT, SHOT_COARSE = 1, 2, 4, 8     # QD_SH
 SHOT_FLAG_NAMES = ("post", "inconsistent", "inexact", "coarse")         # ... bit j <-> name j
 TALLY_HEAD = 10                                                         # QD_TALLY_HEAD
 FAULT_HIST = 256                                                        # QD_FAULT_HIST
+RELAY_FLAG_MARGINALS_DEVICE = 1                                         # QD_RELAY_FLAG_MARGINALS_DEVICE (qd_relay_params.reserved)
 
 
 class QdParams(C.Structure):
@@ -60,7 +61,7 @@ EXPORTS = [
     "qd_unpack_b8", "qd_pack_b8",
     "qd_sample_dem_faults", "qd_commit_bits", "qd_fault_stats_batch",
     "qd_strata_create", "qd_strata_destroy", "qd_strata_info", "qd_sample_dem_strata",
-    "qd_decoder_create_relay",
+    "qd_decoder_create_relay", "qd_decoder_relay_info",
 ]
 
 
@@ -145,6 +146,8 @@ def load():
         L.qd_sample_dem_strata.argtypes = [vp, vp, vp, u64, i64, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp]
     if hasattr(L, "qd_decoder_create_relay"):       # (library version 112; an older library named by QUITS_AMD_LIB decodes with BP + OSD / LSD as before)
         L.qd_decoder_create_relay.argtypes = [vp, C.POINTER(QdParams), C.POINTER(QdRelayParams), vp, C.POINTER(vp)]
+    if hasattr(L, "qd_decoder_relay_info"):         # (library version 113; an older library named by QUITS_AMD_LIB keeps every Relay-BP decoder's marginals in LDS)
+        L.qd_decoder_relay_info.argtypes = [vp, vp]
     _lib = L
     return L
 
@@ -186,6 +189,13 @@ def require_relay(L):
     """The entry point of library version 112 (Relay-BP): a clear error from an older library."""
     if not hasattr(L, "qd_decoder_create_relay"):
         raise RuntimeError("quits_amd: %s is version %d; Relay-BP needs >= 112 -- rebuild it" % (LIB_PATH, L.qd_version()))
+    return L
+
+
+def require_relay_forms(L):
+    """The entry point of library version 113 (Relay-BP with its marginals in device memory): a clear error from an older library."""
+    if not hasattr(L, "qd_decoder_relay_info"):
+        raise RuntimeError("quits_amd: %s is version %d; choosing where Relay-BP keeps its marginals needs >= 113 -- rebuild it" % (LIB_PATH, L.qd_version()))
     return L
 
 

@@ -204,10 +204,22 @@ __device__ __forceinline__ float4 qd_chk_reset(uint32_t synd)
 // word, and the function returns false -- the workgroup is done.
 // (g and a by value, here and in qd_gather_publish: taken by reference, the min-sum kernel's two scalar loads of the redo pass's shot list
 // become vector loads)
-template <int T>
-__device__ __forceinline__ bool qd_gather_prologue(const BpGraphDev g, const DecodeArgs a, int64_t shot, float4 *chk, float *llr, float *prior_dst,
+//
+// A row of one float per fault slot (`prior_dst` here, `vals` in qd_gather_publish) is in LDS or in device memory, by its pointer type:
+// qd_row<false>::ptr, a plain pointer into the kernel's LDS (the compiler follows it to ds_* accesses), or qd_row<true>::ptr, a pointer
+// into the global address space (global_* accesses, never flat).  A device-memory row is LANE-PRIVATE: both functions touch element b from
+// lane b mod T only (b = tid + k T), no barrier publishes it, and the prologue fills it only for a shot that goes on to run BP, behind the
+// all-zero test -- a shot that returns there leaves its row as it was.
+typedef __attribute__((address_space(1))) float qd_global_f32;
+template <bool DEVICE> struct qd_row { typedef float *ptr; };
+template <> struct qd_row<true> { typedef qd_global_f32 *ptr; };
+template <typename ROW> inline constexpr bool qd_row_in_device_memory = std::is_same<std::remove_cv_t<std::remove_pointer_t<ROW>>, qd_global_f32>::value;
+
+template <int T, typename ROW>
+__device__ __forceinline__ bool qd_gather_prologue(const BpGraphDev g, const DecodeArgs a, int64_t shot, float4 *chk, float *llr, ROW prior_dst,
                                                    uint32_t *outw, int *misc, float4 dummy_chk, int status_or)
 {
+    constexpr bool ROW_DEVICE = qd_row_in_device_memory<ROW>;
     const int tid = threadIdx.x;
     const uint8_t *det = a.det + shot * a.det_stride + a.det_offset;
     const uint8_t *upd = a.upd ? a.upd + shot * a.upd_stride : nullptr;
@@ -221,7 +233,8 @@ __device__ __forceinline__ bool qd_gather_prologue(const BpGraphDev g, const Dec
         any |= (int)s;
         chk[c] = qd_chk_reset(s);
     }
-    for (int b = tid; b < g.n; b += T) prior_dst[b] = __uint_as_float(rec4[b].x);
+    if constexpr (!ROW_DEVICE)
+        for (int b = tid; b < g.n; b += T) prior_dst[b] = __uint_as_float(rec4[b].x);
     for (int w = tid; w < g.out_words; w += T) outw[w] = 0u;
     if (tid == 0) {
         llr[g.dummy_bit] = __builtin_inff();        // padding edge of a short row: |b| = inf, never a minimum, never negative
@@ -232,14 +245,15 @@ __device__ __forceinline__ bool qd_gather_prologue(const BpGraphDev g, const Dec
     if (!any) {
         for (int w = tid; w < g.out_words; w += T) a.err_bits[shot * g.out_words + w] = 0u;
         if (tid == 0) a.status[shot] = QD_STATUS_CONVERGED | QD_STATUS_ZERO | status_or;
-    }
+    } else if constexpr (ROW_DEVICE)
+        for (int b = tid; b < g.n; b += T) prior_dst[b] = __uint_as_float(rec4[b].x);
     return any != 0;
 }
 
 // ---- epilogue of a shot that returns a hard decision: [vals <= 0] packed by fault index into err_bits; with `park`, the values
 // themselves go to a row of llr_ws and the shot onto fail_list for the post-processor.  misc[32] carries the fail slot.
-template <int T>
-__device__ __forceinline__ void qd_gather_publish(const BpGraphDev g, const DecodeArgs a, int64_t shot, const float *vals, uint32_t *outw,
+template <int T, typename ROW>
+__device__ __forceinline__ void qd_gather_publish(const BpGraphDev g, const DecodeArgs a, int64_t shot, const ROW vals, uint32_t *outw,
                                                   int *misc, bool park)
 {
     const int tid = threadIdx.x;

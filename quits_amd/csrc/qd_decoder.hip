@@ -150,7 +150,8 @@ extern "C" int qd_decoder_create_relay(const qd_graph *g, const qd_params *p, co
     *out = nullptr;
     if (p->bp_method != QD_BP_MINIMUM_SUM || p->schedule != QD_SCHEDULE_PARALLEL)
         return qd_fail(QD_EINVAL, "Relay-BP is flooding min-sum: bp_method %d / schedule %d are not QD_BP_MINIMUM_SUM / QD_SCHEDULE_PARALLEL", p->bp_method, p->schedule);
-    if (p->reserved != 0 || r->reserved != 0) return qd_fail(QD_EINVAL, "Relay-BP takes no flag bits (0x%x, 0x%x)", p->reserved, r->reserved);
+    if (p->reserved != 0 || (r->reserved & ~QD_RELAY_FLAG_MARGINALS_DEVICE))
+        return qd_fail(QD_EINVAL, "Relay-BP takes no flag bits but QD_RELAY_FLAG_MARGINALS_DEVICE in qd_relay_params (0x%x, 0x%x)", p->reserved, r->reserved);
     if (r->pre_iter < 1 || r->set_max_iter < 1 || r->stop_nconv < 1 || r->num_sets < 0 || r->num_sets > (QD_STATUS_RELAY_LEG_MASK >> QD_STATUS_RELAY_LEG_SHIFT))
         return qd_fail(QD_EINVAL, "relay budgets out of range: pre_iter %d, num_sets %d, set_max_iter %d, stop_nconv %d", r->pre_iter, r->num_sets, r->set_max_iter, r->stop_nconv);
     const long long total = (long long)r->pre_iter + (long long)r->num_sets * r->set_max_iter;
@@ -165,9 +166,12 @@ extern "C" int qd_decoder_create_relay(const qd_graph *g, const qd_params *p, co
     if (g->off_chip)
         return qd_fail(QD_ECAPACITY, "Relay-BP keeps a shot's state in LDS: the off-chip window %d x %d (16 bytes per detector + 8 per fault > %d) does not fit", g->m,
                        g->n, QD_LDS_BYTES);
-    if (qd_relay_layout(g->bp, &x) > QD_LDS_BYTES)
-        return qd_fail(QD_ECAPACITY, "Relay-BP state of window %d x %d: %d bytes of LDS (%d of them the min-sum layout), the CU has %d", g->m, g->n, x.lds_bytes,
-                       g->bp.lds_bytes, QD_LDS_BYTES);
+    // the form: marginals in LDS wherever that fits (unless QD_RELAY_FLAG_MARGINALS_DEVICE), else in a device-memory workspace
+    const int lds_form = qd_relay_layout(g->bp, false, &x);
+    const bool marg_device = (r->reserved & QD_RELAY_FLAG_MARGINALS_DEVICE) != 0 || lds_form > QD_LDS_BYTES;
+    if (qd_relay_layout(g->bp, marg_device, &x) > QD_LDS_BYTES)
+        return qd_fail(QD_ECAPACITY, "Relay-BP state of window %d x %d: %d bytes of LDS with the marginals in LDS, %d with them in device memory (%d of either the "
+                       "min-sum layout), the CU has %d", g->m, g->n, lds_form, x.lds_bytes, g->bp.lds_bytes, QD_LDS_BYTES);
     qd_params q = *p;
     q.reserved = QD_FLAG_RAW_LLR;                        // float LLRs as they are: no grid, nothing certified
     q.max_iter = (int32_t)total;
@@ -182,7 +186,20 @@ extern "C" int qd_decoder_create_relay(const qd_graph *g, const qd_params *p, co
     }
     d->bp = BP_RELAY;
     d->relay = x;
+    d->relay_marg_device = marg_device;
+    d->relay_lds_form = lds_form;
     *out = d;
+    return QD_OK;
+}
+
+extern "C" int qd_decoder_relay_info(const qd_decoder *d, int32_t *info)
+{
+    if (!d || !info) return qd_fail(QD_EINVAL, "null argument");
+    const bool relay = d->bp == BP_RELAY;
+    info[0] = relay ? (d->relay_marg_device ? 2 : 1) : 0;
+    info[1] = relay ? d->relay.lds_bytes : 0;
+    info[2] = relay ? d->relay_lds_form : 0;
+    info[3] = QD_LDS_BYTES;
     return QD_OK;
 }
 
@@ -243,6 +260,9 @@ extern "C" int qd_decoder_reserve(qd_decoder *d, int64_t max_batch)
             HIP_TRY(ws.dev.alloc((size_t)ws.recheck_cap, &ws.recheck_list));
         }
     }
+    // Relay-BP, marginals in device memory: a row per shot of the batch, reserved and released with llr_ws.  Never cleared: a shot that runs BP
+    // fills its row with the priors first, a shot that does not never reads it
+    if (d->bp == BP_RELAY && d->relay_marg_device) HIP_TRY(ws.dev.alloc((size_t)max_batch * g->bp.n_pad, &ws.marg_ws));
     int ncu = 256;
     hipDeviceProp_t prop;
     if (d->post != QD_POST_NONE && hipGetDeviceProperties(&prop, g->device) == hipSuccess && prop.multiProcessorCount > 0) ncu = prop.multiProcessorCount;
@@ -417,7 +437,14 @@ static int launch_bp(qd_decoder *d, const DecodeArgs &a, int64_t B, hipStream_t 
     switch (d->bp) {
     case BP_LDS_EDGE: HIP_TRY(qd_launch_bp_ps_lds(gg, g->bp, a, B, s)); break;
     case BP_GATHER_RAW: HIP_TRY(qd_launch_bp(g->bp, a, B, s)); break;
-    case BP_RELAY: HIP_TRY(qd_launch_bp_relay(g->bp, a, d->relay, B, s)); break;
+    case BP_RELAY:
+        if (d->relay_marg_device) {
+            RelayArgs x = d->relay;
+            x.marg_ws = d->ws.marg_ws;                   // (rows 0 .. B - 1 of the cap the workspace was cut for: decode_impl reserved B <= cap)
+            HIP_TRY(qd_launch_bp_relay_device(g->bp, a, x, B, s));
+        } else
+            HIP_TRY(qd_launch_bp_relay(g->bp, a, d->relay, B, s));
+        break;
     case BP_HBM_EDGE: {
         // edge_cert (off-chip decoder on the LLR grid): the first pass parks the shots whose exactness bound tripped, the redo pass decodes them
         // on the coarse grid -- the gather kernel's rule (BP_GATHER_GRID below), chunk by chunk of the message workspace

@@ -75,6 +75,7 @@ enum BpPath {
 struct Workspace {
     DevAllocs dev;              // every device array below
     float *llr_ws = nullptr;
+    float *marg_ws = nullptr;   // [cap][n_pad] Relay-BP with its marginals in device memory (qd_decoder::relay_marg_device): RelayArgs::marg_ws
     int32_t *fail_list = nullptr, *fail_count = nullptr;     // fail_count: the counter set of the call in flight = ctr_base + 64 * cset
     // Two sets of counters (fail / hard / redo / recheck counts), used by alternate calls.  A call's BP stage needs its set at zero; the set is zeroed by
     // the post-processing stage of the call BEFORE, on ITS stream (that set was last used two calls ago) -- not by fills at the head of the BP stage: in the
@@ -133,6 +134,8 @@ struct qd_decoder {
     float m2_limit = 0.f;
     const uint32_t *first_pass = nullptr;      // [m_pad][8] gather pass 0 of every check slot (ScatArgs::first_pass); null: the kernel runs it (QD_BP_NO_FAST_START=1)
     RelayArgs relay{};                         // BP_RELAY: budgets, the gamma table in slot order (owned by mem), the kernel's LDS layout
+    bool relay_marg_device = false;            // BP_RELAY: the marginals are rows of ws.marg_ws (bp_relay_device.hip), not LDS
+    int relay_lds_form = 0;                    // BP_RELAY: what the window's LDS form takes (it may not fit: qd_decoder_relay_info)
     DevAllocs mem;
     int profiling = 0;
     struct Span { int kind; hipEvent_t t0, t1; };   // kind 0 = BP kernel, 1 = OSD kernel(s)
@@ -168,7 +171,8 @@ hipError_t qd_launch_bp_first_pass(const BpGraphDev &g, const ScatGraphDev &sg, 
 hipError_t qd_launch_bp_general(const GenGraphDev &g, const BpGraphDev &bg, const DecodeArgs &a, const GenWs &w, int bp_method,
                                 int schedule, int64_t shot0, int nshots, hipStream_t s, GenStagePlan *plan);
 hipError_t qd_launch_bp_relay(const BpGraphDev &g, const DecodeArgs &a, const RelayArgs &x, int64_t B, hipStream_t s);
-int qd_relay_layout(const BpGraphDev &g, RelayArgs *x);        // fills the off_* members and lds_bytes, which it returns
+hipError_t qd_launch_bp_relay_device(const BpGraphDev &g, const DecodeArgs &a, const RelayArgs &x, int64_t B, hipStream_t s);   // bp_relay_device.hip
+int qd_relay_layout(const BpGraphDev &g, bool marg_device, RelayArgs *x);   // fills the off_* members and lds_bytes, which it returns
 hipError_t qd_launch_hold(const int32_t *count, int threshold, int microseconds, hipStream_t s);
 int qd_bp_ps_lds_bytes(const GenGraphDev &g, int max_rdeg);
 hipError_t qd_launch_bp_ps_lds(const GenGraphDev &g, const BpGraphDev &bg, const DecodeArgs &a, int64_t B, hipStream_t s);

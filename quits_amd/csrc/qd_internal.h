@@ -106,6 +106,7 @@ struct RelayArgs {
     float gamma0;
     const float *gammas;        // [num_sets][n_pad] memory strengths of legs 1.., by bit slot (null: num_sets = 0)
     int off_marg, off_best, off_wsum, lds_bytes;   // marginals [n_pad + 1] floats, best candidate [out_words], 64-bit weight sum
+    float *marg_ws;             // [cap][n_pad] the device-marginal form's M_j, row = shot, slot order (then off_marg = -1); null in the LDS form
 };
 
 // Workgroup-wide OR without static LDS (a static __shared__ object in front of the dynamic region can knock the

@@ -181,23 +181,31 @@ class BatchDecoder:
 class RelayBatchDecoder(BatchDecoder):
     """qd_decoder_create_relay: Relay-BP over a batch of shots for one window (csrc/bp_relay.hip; the definition is quits_amd/relay.py), then
     `osd_method`'s post-processor over the shots that found no candidate ("osd_off": they return their last hard decision).  `decode`,
-    `info`, `profile` and the rest are BatchDecoder's.  `gammas`: float32 [cfg.num_sets, n] in fault order; None = relay_gammas(n, cfg)."""
+    `info`, `profile` and the rest are BatchDecoder's.  `gammas`: float32 [cfg.num_sets, n] in fault order; None = relay_gammas(n, cfg).
+    `marginals`: where the kernel keeps the marginals M_j -- "auto": in LDS wherever the whole state fits the CU, else in the decoder's
+    device-memory workspace (4 bytes per fault and shot of a batch); "lds": in LDS or not at all (QdError -4 where that does not fit);
+    "device": in the workspace even where LDS would do (QD_RELAY_FLAG_MARGINALS_DEVICE, validation).  Same results, bit for bit."""
 
-    def __init__(self, graph: WindowGraph, cfg=None, osd_method="osd_off", osd_order=0, ms_scaling_factor=1.0, gammas=None):
+    def __init__(self, graph: WindowGraph, cfg=None, osd_method="osd_off", osd_order=0, ms_scaling_factor=1.0, gammas=None, marginals="auto"):
         from .. import relay as _relay
         cfg = _relay.RelayConfig() if cfg is None else cfg
         if not isinstance(cfg, _relay.RelayConfig):
             raise TypeError("cfg must be a RelayConfig, not %r" % type(cfg).__name__)
+        if _norm(marginals) not in ("auto", "lds", "device"):
+            raise ValueError("marginals must be 'auto', 'lds' or 'device', not %r" % (marginals,))
         self.graph = graph
         self.cfg = cfg
         L = _lib.require_relay(graph._L)
+        if _norm(marginals) != "auto":
+            _lib.require_relay_forms(L)
         try:
             prm = _lib.QdParams(_lib.QD_BP["minimum_sum"], _lib.QD_SCHEDULE["parallel"], 0, _lib.QD_OSD[_norm(osd_method)], int(osd_order), 0,
                                 float(ms_scaling_factor))
         except KeyError as exc:
             raise ValueError("unknown decoder option %s" % exc) from exc
         self.gammas = _relay.check_table(gammas, cfg, graph.n)
-        rp = _lib.QdRelayParams(cfg.pre_iter, cfg.num_sets, cfg.set_max_iter, cfg.stop_nconv, float(cfg.gamma0), 0)
+        rp = _lib.QdRelayParams(cfg.pre_iter, cfg.num_sets, cfg.set_max_iter, cfg.stop_nconv, float(cfg.gamma0),
+                                _lib.RELAY_FLAG_MARGINALS_DEVICE if _norm(marginals) == "device" else 0)
         h = C.c_void_p()
         rc = L.qd_decoder_create_relay(graph._h, C.byref(prm), C.byref(rp), self.gammas.ctypes.data_as(C.c_void_p) if cfg.num_sets else C.c_void_p(0), C.byref(h))
         if rc == -2:
@@ -206,9 +214,25 @@ class RelayBatchDecoder(BatchDecoder):
         self._h = h
         self._L = L
         self.params = prm
+        if _norm(marginals) == "lds" and self._relay_info()[0] != 1:
+            # the library chose the device-memory form because the LDS form does not fit: with "lds" that is the capacity error
+            _, used, lds_form, limit = self._relay_info()
+            L.qd_decoder_destroy(self._h)
+            self._h = None
+            raise _lib.QdError(-4, "Relay-BP state of window %d x %d with the marginals in LDS (marginals='lds'): %d bytes of LDS, the CU has %d "
+                                   "(%d bytes with the marginals in device memory: marginals='auto')" % (graph.m, graph.n, lds_form, limit, used))
+
+    def _relay_info(self):
+        if not hasattr(self._L, "qd_decoder_relay_info"):         # (a version 112 library named by QUITS_AMD_LIB: the LDS form is all it has)
+            return [1, 0, 0, 0]
+        arr = (C.c_int32 * 4)()
+        _lib.check(self._L.qd_decoder_relay_info(self._h, arr))
+        return [int(v) for v in arr]
 
     def info(self) -> dict:
-        return dict(super().info(), bp_kernel="qd_bp_relay_kernel", total_iter=self.cfg.total_iter)
+        form, lds, _, _ = self._relay_info()
+        return dict(super().info(), bp_kernel="qd_bp_relay_kernel", total_iter=self.cfg.total_iter, relay_marginals={1: "lds", 2: "device"}[form],
+                    relay_lds_bytes=lds)
 
 
 class GF2Matrix:

@@ -108,7 +108,7 @@ class DeviceWindowPlan:
         # large windows -- QLP [[1020,136]] W = 3: 18 decoders x 18 900 faults = 1.36 MB per shot and lane -- would not fit three lanes of
         # 65 536 shots (268 GB).  Lanes first, then the chunk, give way until the estimate fits QD_POST_WS_GB.
         if self.pipeline and self.env.chunk_shots is None:
-            per_shot = sum(4 * ((d.graph.n + 63) // 64 * 64) + 64 for d in decs)
+            per_shot = workspace_bytes_per_shot(decs)
             self.lanes, self.chunk = fit_lanes_and_chunk(per_shot, self.lanes, self.chunk, self.env.post_ws_gb * (1 << 30))
         self.host_piece = self.lanes * self.chunk   # shots per staged piece of decode_host (one group of the pipelined driver's lanes)
         self._lane_decs = {id(d): [d] for d in decs}     # per decoder of the plan, the decoders of the two-stream driver's lanes (lane 0: itself)
@@ -256,6 +256,19 @@ class DeviceWindowPlan:
                 self._ws_live = True             # (a concurrent cache lookup may have released them since this plan was handed out)
                 yield self
         return held()
+
+
+def workspace_bytes_per_shot(decs):
+    """The estimate fit_lanes_and_chunk is given: what one shot of a chunk takes in the workspaces of one lane's decoders `decs` -- the posterior
+    row, 4 bytes per padded fault (n_pad = n rounded up to 64), and the lists; a Relay-BP decoder whose marginals live in device memory
+    (info()["relay_marginals"] == "device") keeps a second such row per shot.  QLP [[1020,136]] W = 3: 18 decoders x 2 x 75.6 KB."""
+    total = 0
+    for d in decs:
+        row = 4 * ((d.graph.n + 63) // 64 * 64)
+        total += row + 64
+        if d.info().get("relay_marginals") == "device":
+            total += row
+    return total
 
 
 def fit_lanes_and_chunk(per_shot_bytes, lanes, chunk, budget_bytes, min_chunk=8192):
