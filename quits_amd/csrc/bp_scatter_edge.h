@@ -1,4 +1,4 @@
-// bp_scatter_edge.h -- the per-edge steps of the scatter form of flooding min-sum (gather pass: QS_EDGE_M, scatter pass: QS_SCAT) of
+// bp_scatter_edge.h -- the per-edge steps of the scatter form of flooding min-sum (gather pass: QS_EDGE_M / QS_EDGE_K, scatter pass: QS_SCAT) of
 // qd_bp_scatter_wide_kernel and qd_bp_first_pass_kernel (bp_scatter_wide.hip, bp_scatter_wide_walk.inc).
 // The macros work on the enclosing scope's names: s1, s2 (what the check sent last), a1, a2, ltw, neww, hp (what this pass
 // collects), dc (the check's degree), pdif, pxq, own, xw (scatter pass).
@@ -55,6 +55,60 @@ typedef __attribute__((address_space(3))) int32_t qs_lds_i32;
         a2 = __builtin_amdgcn_fmed3f(a1, a2, fabsf(bm_));                                                    \
         a1 = qs_min_abs(a1, bm_);                                                                            \
     }
+// Gather pass, one edge, key form (rows of at most 64 faults): `a1`, `a2` hold the two smallest KEYS, key = |bm| + (1 + k_ / 64): the position rides in
+// six fraction bits under the magnitude.  |bm| is an integer-valued float, so a key below 2^18 is exact (24 significant bits), its floor(key) - 1 is the
+// magnitude and 64 * its fraction the position; equal magnitudes order by position, so the smallest key is the minimum at its FIRST position -- the edge
+// of the last strict improvement -- and the second smallest carries min2, a tied one included.  One v_add_f32 (|bm| as a source modifier, the position
+// constant wave-uniform) in place of the compare form's v_cmp_lt_f32 + v_addc_co_u32; no `ltw`.  (The same keys times 64, |bm| * 64 + (64 + k_), would be
+// one v_fma_f32 -- but 64.0 is no inline constant, and a VOP3 reads one scalar register: the compiler moves the position constant into a vector
+// register first, and the edge costs what the compare form costs.)  A key of 2^18 or more may have been rounded, but only to a value of 2^18 or more:
+// the walk ends by testing the second key against QS_KEY_LIMIT (QS_KEYS_DECODE) and the caller walks the round again in the compare form where that
+// fails.  1 + k / 64 for k = 0..63 lies in one binade: its bits are QS_KEY_POS0 + (k << 17), which the scalar unit steps with integer adds.
+__device__ __forceinline__ float qs_min_f32(float a, float b)       // no canonicalising v_max in front of the v_min (the keys are never NaN)
+{
+    float r;
+    asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+#define QS_KEY_POS0 0x3F800000u           // 1.0f
+#define QS_KEY_LIMIT 262144.0f            // 2^18
+#define QS_EDGE_K(off, k_, SGN_, TAILFIX, HP, MAG_)                                                          \
+    {                                                                                                        \
+        const int A_ = QS_ACC(off);                                                                          \
+        const float mag_ = MAG_;                                                                             \
+        const float prev_ = __uint_as_float((SGN_) | __float_as_uint(mag_));                                 \
+        float d_ = (float)A_ - prev_;                                                                        \
+        TAILFIX(d_, k_)                                                                                      \
+        const float bm_ = d_ + 1.0f;                                                                         \
+        HP(A_)                                                                                               \
+        neww = __builtin_amdgcn_alignbit(neww, __float_as_uint(d_), 31);                                     \
+        const float key_ = fabsf(bm_) + __uint_as_float(QS_KEY_POS0 + ((uint32_t)(k_) << 17));               \
+        a2 = __builtin_amdgcn_fmed3f(a1, a2, key_);                                                          \
+        a1 = qs_min_f32(a1, key_);                                                                           \
+    }
+// The end of a key-form walk: keys -> a1, a2, kst, and `keys_ok_` (wave-uniform: every lane's second key is below the limit, hence exact, hence
+// both keys are the true two smallest).  The position is clamped below the trip count: a key that is not exact belongs to a pass that is walked
+// again, but its position must never address the adjacency table or the LDS beyond the check's row.
+#define QS_KEYS_DECODE(trip_)                                                                                \
+    const bool keys_ok_ = __builtin_amdgcn_ballot_w64(!(a2 < QS_KEY_LIMIT)) == 0ull;                         \
+    {                                                                                                        \
+        const float f1_ = __builtin_floorf(a1), f2_ = __builtin_floorf(a2);                                  \
+        kst = min((uint32_t)((a1 - f1_) * 64.0f), (uint32_t)max((trip_) - 1, 0));                            \
+        a1 = f1_ - 1.0f; a2 = f2_ - 1.0f;                                                                    \
+    }
+// The two forms of the walk, part by part (bp_scatter_wide_walk.inc asks for QS_WALK(part); its includer says which family answers).
+// Compare form: `ltw` per sign word, shifted at pad positions too; a later word's improvement overrides an earlier one's.
+#define QS_CMP_EDGE QS_EDGE_M
+#define QS_CMP_PAD { neww <<= 1; ltw <<= 1; }
+#define QS_CMP_WORD_BEGIN uint32_t ltw = 0u;
+#define QS_CMP_WORD_END(k0_, kend_) if (ltw) kst = (uint32_t)((k0_) + (kend_) - 1 - (int)__builtin_ctz(ltw));
+#define QS_CMP_END(trip_)
+// Key form: nothing per word, the decode at the end.
+#define QS_KEY_EDGE QS_EDGE_K
+#define QS_KEY_PAD { neww <<= 1; }
+#define QS_KEY_WORD_BEGIN
+#define QS_KEY_WORD_END(k0_, kend_)
+#define QS_KEY_END(trip_) QS_KEYS_DECODE(trip_)
 #define QS_NOFIX(x_, k_)
 // beyond this lane's degree the walk reads the trash slot (0 for ever: no hard decision); the difference must be neither negative
 // nor a minimum

@@ -119,6 +119,7 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
     // outgoing signs: edge k of a word of kend edges at bit kend - 1 - k) and what the gather pass of this iteration found
     float S1[CPL], S2[CPL], A1[CPL], A2[CPL], mx2 = 0.f;
     uint32_t KOLD[CPL], KST[CPL], O[CPL][NSW], Q[CPL][NSW];
+    [[maybe_unused]] uint32_t cmpf = 0u;                // bit j: round j of this wavefront walks in the compare form from now on (two-word shapes; see the gather pass)
     uint32_t FOFF[CPL];                                 // where and what the last scatter pass added for its argmin edge (min2 - min1, signed): given back by the next
     int FVAL[CPL];
 #pragma unroll
@@ -184,15 +185,46 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
             float a1 = FLT_MAX, a2 = FLT_MAX;
             uint32_t kst = 0u;
             QSW_GATHER_PRIO(j)          // the later gather rounds of a wavefront run at a higher priority
+            // what a walk leaves behind (hp, par, neg[]) becomes the check's new state
+            // outgoing sign on edge k = syndrome ^ (parity of all incoming signs) ^ incoming sign k
+#define QSW_WALKED                                                                                     \
+                {                                                                                      \
+                    const uint32_t flip = 0u - ((synd[j] ^ (uint32_t)__popc(par)) & 1u);               \
+                    _Pragma("unroll")                                                                  \
+                    for (int w = 0; w < NSW; ++w) Q[j][w] = neg[w] ^ flip;                             \
+                    mx2 = fmaxf(mx2, a2);                                                              \
+                    us = us || (((synd[j] ^ (hp >> 31)) & 1u) != 0u);                                  \
+                }
+            // Rows of at most 64 faults walk in the key form (bp_scatter_edge.h: QS_EDGE_K), which is exact where every check's second key stays below
+            // 2^18, i.e. min2 < 2^18 - 1.  Where a round's walk ends at or above that (late iterations of shots that do not converge: 2.1 % of the headline's
+            // round-passes, profiles/bp_argmin_keys_ab.txt) the round is walked again in the compare form -- the accumulators do not move during a gather
+            // pass and a walk writes only locals -- and the round's bit in `cmpf` sends its later passes there at once.
+            bool cmpw = true;
+            if constexpr (NSW == 2) cmpw = __builtin_amdgcn_ballot_w64((cmpf >> j) & 1u) != 0ull;       // (wave-uniform: set for all of a round's lanes or none)
+#ifdef QSW_STATS
+            if ((tid & 63) == 0 && __ballot(act[j])) atomicAdd(&a.dbg[14], 1ull);
+#endif
             if (act[j]) {
+                if constexpr (NSW == 2) {
+                    if (!cmpw) {
+#define QS_WALK(p_) QS_KEY_##p_
 #include "bp_scatter_wide_walk.inc"
-                // outgoing sign on edge k = syndrome ^ (parity of all incoming signs) ^ incoming sign k
-                const uint32_t flip = 0u - ((synd[j] ^ (uint32_t)__popc(par)) & 1u);
-#pragma unroll
-                for (int w = 0; w < NSW; ++w) Q[j][w] = neg[w] ^ flip;
-                mx2 = fmaxf(mx2, a2);
-                us = us || (((synd[j] ^ (hp >> 31)) & 1u) != 0u);
+#undef QS_WALK
+                        if (keys_ok_) QSW_WALKED
+                        else { cmpw = true; cmpf |= 1u << j; a1 = FLT_MAX; a2 = FLT_MAX; kst = 0u; }
+                    }
+                }
+                if (cmpw) {
+#ifdef QSW_STATS
+                    if ((tid & 63) == 0) atomicAdd(&a.dbg[15], 1ull);        // (lane 0 is on wherever a round has a check: slots fill from the bottom)
+#endif
+#define QS_WALK(p_) QS_CMP_##p_
+#include "bp_scatter_wide_walk.inc"
+#undef QS_WALK
+                    QSW_WALKED
+                }
             }
+#undef QSW_WALKED
             A1[j] = a1; A2[j] = a2; KST[j] = kst;
         }
         __builtin_amdgcn_s_setprio(0);
@@ -406,7 +438,9 @@ __global__ void __launch_bounds__(64) qd_bp_first_pass_kernel(BpGraphDev g, Scat
     uint4 r0 = make_uint4(__float_as_uint(FLT_MAX), __float_as_uint(FLT_MAX), 0u, 0u);      // (a slot beyond the window: what the kernel's own pass leaves there)
     uint4 r1 = make_uint4(0u, 0u, 0u, (uint32_t)sg.offA + (uint32_t)(sg.nslots - 32 + (int)(threadIdx.x & 31)) * 4u);
     if (actv) {
+#define QS_WALK(p_) QS_CMP_##p_
 #include "bp_scatter_wide_walk.inc"
+#undef QS_WALK
         (void)hp;
         r0 = make_uint4(__float_as_uint(a1), __float_as_uint(a2), kst, neg[0]);
         r1 = make_uint4(neg[1], neg[2], (uint32_t)__popc(par) & 1u,

@@ -1,6 +1,10 @@
 // bp_scatter_wide_walk.inc -- the edge walk of one gather pass of one check (bp_scatter_wide.hip), as program text: included by
 // qd_bp_scatter_wide_kernel for every pass and by qd_bp_first_pass_kernel, which runs pass 0 once per decoder -- the same QS_EDGE_M
 // steps (bp_scatter_edge.h, with QS_MAG_MASK and QS_SIGN_TOP), trip counts, tail rules and argmin rule, so the table cannot drift from what the loop would have found.
+// Two forms of one text, chosen by the includer's QS_WALK(part) (bp_scatter_edge.h: #define QS_WALK(p_) QS_CMP_##p_ or QS_KEY_##p_).  The compare form
+// (QS_EDGE_M: a bit history `ltw` of the strict improvements, a1 / a2 the minima) and the key form for rows of at most 64 faults (QS_EDGE_K: a1 / a2 collect
+// position-carrying keys, there is no `ltw`, and the walk ends with QS_KEYS_DECODE, which leaves a1, a2, kst as the compare form would and `keys_ok_` --
+// false where some lane's second key is too large to be exact; the includer then walks the round again in the compare form: the walk writes locals only).
 // In scope at the point of inclusion: j, dws, cs, S1, S2, KOLD, dcs, O, pf, a1, a2, kst, adj_row, QS_ADJ, QS_ACC.  Leaves hp, par, neg[].
 // "Is this the edge my last minimum came from" (min2 goes back on that edge, min1 on the others) is asked through lane masks in scalar registers, not per edge
 // on the vector ALU: lq[q] once per check and pass, gsel_ once per group of four edges (the group index is wave-uniform in all four loop forms), their AND
@@ -35,7 +39,8 @@
                         // kend - 1 of O (all ones for a check with syndrome ^ parity = 1), which the pre-shift already dropped; the 32 - kend zeros the
                         // pre-shift brought in at the bottom are the bits above kend - 1 now.  The result is bit for bit the word that started from 0.
                         // (Lanes past their degree collect QS_BIG's sign, 0, whatever they read as the sent sign; the first-pass table walks with O = 0.)
-                        uint32_t neww = O[j][w] << ((32 - kend) & 31), ltw = 0u;
+                        uint32_t neww = O[j][w] << ((32 - kend) & 31);
+                        QS_WALK(WORD_BEGIN)
                         const int kplain = min(max(wmin4 - k0, 0), kend);     // groups every lane of the wavefront has in full
                         const int row0 = k0 >> 2;
                         uint4 nx = (j == 0 && w == 0) ? pf : QS_ADJ(row0);
@@ -48,15 +53,15 @@
                                 {
                                     const int k = k0 + kk;
                                     QS_GSEL(k)
-                                    QS_EDGE_M(nx.x, k, QS_SIGN_TOP, QS_NOFIX, QS_HPA, QS_MAG_MASK(0)) QS_EDGE_M(nx.y, k + 1, QS_SIGN_TOP, QS_NOFIX, QS_HPB, QS_MAG_MASK(1))
-                                    QS_EDGE_M(nx.z, k + 2, QS_SIGN_TOP, QS_NOFIX, QS_HPA, QS_MAG_MASK(2)) QS_EDGE_M(nx.w, k + 3, QS_SIGN_TOP, QS_NOFIX, QS_HPB, QS_MAG_MASK(3))
+                                    QS_WALK(EDGE)(nx.x, k, QS_SIGN_TOP, QS_NOFIX, QS_HPA, QS_MAG_MASK(0)) QS_WALK(EDGE)(nx.y, k + 1, QS_SIGN_TOP, QS_NOFIX, QS_HPB, QS_MAG_MASK(1))
+                                    QS_WALK(EDGE)(nx.z, k + 2, QS_SIGN_TOP, QS_NOFIX, QS_HPA, QS_MAG_MASK(2)) QS_WALK(EDGE)(nx.w, k + 3, QS_SIGN_TOP, QS_NOFIX, QS_HPB, QS_MAG_MASK(3))
                                 }
                                 nx = QS_ADJ(row0 + (kk >> 2) + 2);
                                 {
                                     const int k = k0 + kk + 4;
                                     QS_GSEL(k)
-                                    QS_EDGE_M(eb.x, k, QS_SIGN_TOP, QS_NOFIX, QS_HPA, QS_MAG_MASK(0)) QS_EDGE_M(eb.y, k + 1, QS_SIGN_TOP, QS_NOFIX, QS_HPB, QS_MAG_MASK(1))
-                                    QS_EDGE_M(eb.z, k + 2, QS_SIGN_TOP, QS_NOFIX, QS_HPA, QS_MAG_MASK(2)) QS_EDGE_M(eb.w, k + 3, QS_SIGN_TOP, QS_NOFIX, QS_HPB, QS_MAG_MASK(3))
+                                    QS_WALK(EDGE)(eb.x, k, QS_SIGN_TOP, QS_NOFIX, QS_HPA, QS_MAG_MASK(0)) QS_WALK(EDGE)(eb.y, k + 1, QS_SIGN_TOP, QS_NOFIX, QS_HPB, QS_MAG_MASK(1))
+                                    QS_WALK(EDGE)(eb.z, k + 2, QS_SIGN_TOP, QS_NOFIX, QS_HPA, QS_MAG_MASK(2)) QS_WALK(EDGE)(eb.w, k + 3, QS_SIGN_TOP, QS_NOFIX, QS_HPB, QS_MAG_MASK(3))
                                 }
                             }
                         }
@@ -66,17 +71,17 @@
                             nx = QS_ADJ(row0 + (kk >> 2) + 1);
                             const int k = k0 + kk;
                             QS_GSEL(k)
-                            QS_EDGE_M(e4.x, k, QS_SIGN_TOP, QS_NOFIX, QS_HPA, QS_MAG_MASK(0))
-                            QS_EDGE_M(e4.y, k + 1, QS_SIGN_TOP, QS_NOFIX, QS_HPB, QS_MAG_MASK(1))
-                            QS_EDGE_M(e4.z, k + 2, QS_SIGN_TOP, QS_NOFIX, QS_HPA, QS_MAG_MASK(2))
-                            QS_EDGE_M(e4.w, k + 3, QS_SIGN_TOP, QS_NOFIX, QS_HPB, QS_MAG_MASK(3))
+                            QS_WALK(EDGE)(e4.x, k, QS_SIGN_TOP, QS_NOFIX, QS_HPA, QS_MAG_MASK(0))
+                            QS_WALK(EDGE)(e4.y, k + 1, QS_SIGN_TOP, QS_NOFIX, QS_HPB, QS_MAG_MASK(1))
+                            QS_WALK(EDGE)(e4.z, k + 2, QS_SIGN_TOP, QS_NOFIX, QS_HPA, QS_MAG_MASK(2))
+                            QS_WALK(EDGE)(e4.w, k + 3, QS_SIGN_TOP, QS_NOFIX, QS_HPB, QS_MAG_MASK(3))
                         }
                         // an edge below the smallest degree of the wavefront is real on every lane (no fix), one at or beyond the largest is
                         // nobody's; only in between does a lane have to ask (wave-uniform tests; k < wmax: a group starts below the largest degree)
 #define QS_TAIL_EDGE(off, q_)                                                                                     \
-                            if (k + (q_) < wmin) QS_EDGE_M(off, k + (q_), QS_SIGN_TOP, QS_NOFIX, QS_HP1, QS_MAG_MASK(q_))         \
-                            else if (k + (q_) < wmax) QS_EDGE_M(off, k + (q_), QS_SIGN_TOP, QS_TAILFIX, QS_HP1, QS_MAG_MASK(q_))  \
-                            else { neww <<= 1; ltw <<= 1; }
+                            if (k + (q_) < wmin) QS_WALK(EDGE)(off, k + (q_), QS_SIGN_TOP, QS_NOFIX, QS_HP1, QS_MAG_MASK(q_))         \
+                            else if (k + (q_) < wmax) QS_WALK(EDGE)(off, k + (q_), QS_SIGN_TOP, QS_TAILFIX, QS_HP1, QS_MAG_MASK(q_))  \
+                            else QS_WALK(PAD)
 #pragma unroll 1
                         for (; kk + 4 < kend; kk += 4) {
                             const uint4 e4 = nx;
@@ -93,7 +98,8 @@
 #undef QS_TAIL_EDGE
                         neg[w] = neww;
                         par ^= neww;
-                        if (ltw) kst = (uint32_t)(k0 + kend - 1 - (int)__builtin_ctz(ltw));   // a later word's improvement overrides an earlier one's
+                        QS_WALK(WORD_END)(k0, kend)
                     }
                 }
 #undef QS_GSEL
+                QS_WALK(END)(trip)

@@ -17,3 +17,5 @@ print(name, "wave-round-iterations", c[0], "with no change", c[1], "= %.3f" % (c
 for b in range(5):
     print("  iterations %d..%d: %d, unchanged share %.3f" % (10 * b, 10 * b + 9, c[2 + b], c[7 + b] / max(c[2 + b], 1)))
 print("  checks unchanged share %.3f" % (c[12] / max(c[13], 1)))
+# gather round-passes of the loop (two-sign-word shapes walk in the key form) and those that ended in the compare form: second key over the bound, or the round's sticky bit
+print("  gather round-passes %d, walked in the compare form %d = %.4f" % (c[14], c[15], c[15] / max(c[14], 1)))
