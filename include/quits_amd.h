@@ -99,7 +99,7 @@ typedef struct qd_params {
     double ms_scaling_factor;   /* not exposed by the reference wrapper -> ldpc default 1.0; 0 = 1-2^-it */
 } qd_params;
 
-int qd_version(void);                 /* 113 (113: qd_decoder_relay_info, QD_RELAY_FLAG_MARGINALS_DEVICE; 112: qd_decoder_create_relay, QD_STATUS_RELAY_LEG_*; 111: qd_strata_create, qd_strata_destroy, qd_strata_info, qd_sample_dem_strata; 110: qd_sample_dem_faults, qd_commit_bits, qd_fault_stats_batch; 109: qd_unpack_b8, qd_pack_b8; 108: qd_shot_flags_fold, qd_tally_batch, qd_sample_circuit_shots, qd_sample_dem_shots; 107: off-chip windows decode, QD_FLAG_OFF_CHIP, QD_POST_OSD0_OFFCHIP, no new export; 106: qd_circuit_create accepts the biased-noise opcodes Y_ERROR / PAULI_CHANNEL_1 / PAULI_CHANNEL_2, no new export; 105: qd_decoder_fast_start; 104: qd_circuit_* + qd_sample_circuit; 103: qd_decoder_post_head_start; 101: qd_graph_info wrote 12 entries; 102: 10 again + qd_graph_info_ex) */
+int qd_version(void);                 /* 114 (114: qd_shrink_begin, qd_shrink_step; 113: qd_decoder_relay_info, QD_RELAY_FLAG_MARGINALS_DEVICE; 112: qd_decoder_create_relay, QD_STATUS_RELAY_LEG_*; 111: qd_strata_create, qd_strata_destroy, qd_strata_info, qd_sample_dem_strata; 110: qd_sample_dem_faults, qd_commit_bits, qd_fault_stats_batch; 109: qd_unpack_b8, qd_pack_b8; 108: qd_shot_flags_fold, qd_tally_batch, qd_sample_circuit_shots, qd_sample_dem_shots; 107: off-chip windows decode, QD_FLAG_OFF_CHIP, QD_POST_OSD0_OFFCHIP, no new export; 106: qd_circuit_create accepts the biased-noise opcodes Y_ERROR / PAULI_CHANNEL_1 / PAULI_CHANNEL_2, no new export; 105: qd_decoder_fast_start; 104: qd_circuit_* + qd_sample_circuit; 103: qd_decoder_post_head_start; 101: qd_graph_info wrote 12 entries; 102: 10 again + qd_graph_info_ex) */
 const char *qd_last_error(void);
 /* Number of visible HIP devices (0 if none): lets a host fail loudly before building anything. */
 int qd_device_count(void);
@@ -358,6 +358,38 @@ int qd_commit_bits(const uint32_t *d_err_bits, int64_t err_stride_words, int32_t
 int qd_fault_stats_batch(const uint32_t *d_faults, const uint32_t *d_corr, int64_t stride_words, int32_t nbits, const uint8_t *d_residual,
                          int64_t res_stride, int32_t m, const uint64_t *d_fail_mask, int64_t B, int64_t shot0, int64_t *d_hist,
                          int64_t *d_counts, uint64_t *d_best, void *stream);
+
+/* ---- shrinking failing fault sets to 1-minimal ones (version 114).  quits_amd/shrink.py states the walk: a parent set S loses fault j whenever
+ *      the decoder still fails on S \ {j}, j running cyclically over the members, until |S| trials in a row change nothing.  These two calls are the
+ *      whole step between two decodes; the caller decodes the trial rows like sampled shots (qd_decode_batch ... qd_tally_batch) and hands back
+ *      qd_tally_batch's fail mask.  Stateless: every array is the caller's, on the device of Ht.  No reference counterpart.
+ *        Ht, Lt            the TRANSPOSES of H (m x n) and L (k x n) as CSR, qd_sample_dem's: row j = the detectors / observables fault j flips
+ *        d_sets            P rows of set_stride_words >= ceil(n / 32) words: bit (j & 31) of word (j >> 5) = fault j is in the set; shrunk in place
+ *        d_state           int32 [P][QD_SHRINK_STATE]: last, quiet, w = |S|, trials so far, QD_SHRINK_* flags, the pending trial's fault (-1: trial
+ *                          0, the set itself), the start weight |E|, 0
+ *        d_hs, d_ls        P rows of m / k bytes (strides >= m, k): H S and L S of the CURRENT sets, kept incrementally -- an accepted trial flips
+ *                          the bytes of column j, nothing recomputes the product.  The caller fills them for the start sets (qd_gf2_spmv_batch).
+ *        d_live            int32 [P]: the parents still walking, ascending; d_count[0] their number A (the only word a host reads per round)
+ *        d_det, d_obs      row i < A (strides >= m, k): the trial of parent d_live[i] -- H (S \ {j}), L (S \ {j}), every byte written once by one
+ *                          lane; bytes outside the first m / k of a row keep their values; d_fault[i] = j, d_parent[i] = d_live[i]
+ *      QD_EINVAL with a message: a null argument, Ht / Lt of different row counts or devices, a stride too small, P > 2^31 - 1, A > P,
+ *      d_live_next == d_live.  Asynchronous on `stream`. */
+#define QD_SHRINK_STATE 8
+#define QD_SHRINK_FAILS 1       /* trial 0 failed: the parent is a failing set                              */
+#define QD_SHRINK_MINIMAL 2     /* the walk ended with quiet >= w: the set in d_sets is 1-minimal           */
+#define QD_SHRINK_ENDED 4       /* the parent left the live list (minimal, or trial 0 did not fail)         */
+/* Start: clears the padding bits of every set's last word, counts w, writes the state before trial 0, d_live = 0 .. P - 1, d_count[0] = P, and
+ * emits trial 0 of every parent (d_det = d_hs, d_obs = d_ls, d_fault = -1).  Two launches. */
+int qd_shrink_begin(const qd_spmat *Ht, const qd_spmat *Lt, uint32_t *d_sets, int64_t set_stride_words, int64_t P, int32_t *d_state,
+                    int32_t *d_live, int32_t *d_count, const uint8_t *d_hs, int64_t hs_stride, const uint8_t *d_ls, int64_t ls_stride,
+                    uint8_t *d_det, int64_t det_stride, uint8_t *d_obs, int64_t obs_stride, int32_t *d_fault, int32_t *d_parent, void *stream);
+/* One round: bit i of d_fail_mask (ceil(A / 64) words, qd_tally_batch's mask of the A trial rows) is the verdict of parent d_live[i].  Applies
+ * it (one wavefront per parent), writes the surviving parents in the same order to d_live_next (!= d_live) and their number to d_count[0] (one
+ * workgroup), and emits their next trials into rows 0 .. d_count[0] - 1.  Three launches.  A = 0: d_count[0] = 0. */
+int qd_shrink_step(const qd_spmat *Ht, const qd_spmat *Lt, uint32_t *d_sets, int64_t set_stride_words, int64_t P, int32_t *d_state,
+                   const int32_t *d_live, int64_t A, const uint64_t *d_fail_mask, int32_t *d_live_next, int32_t *d_count, uint8_t *d_hs,
+                   int64_t hs_stride, uint8_t *d_ls, int64_t ls_stride, uint8_t *d_det, int64_t det_stride, uint8_t *d_obs, int64_t obs_stride,
+                   int32_t *d_fault, int32_t *d_parent, void *stream);
 
 /* ---- stratified input: shots of the detector error model CONDITIONED on exactly k faults firing (subset sampling).  Stands in for
  *      rejection -- drawing `sampler.sample(shots)` (simulation.py:23-27) until a shot happens to hold k faults, which Stim could not even

@@ -30,6 +30,8 @@ SHOT_FLAG_NAMES = ("post", "inconsistent", "inexact", "coarse")         # ... bi
 TALLY_HEAD = 10                                                         # QD_TALLY_HEAD
 FAULT_HIST = 256                                                        # QD_FAULT_HIST
 RELAY_FLAG_MARGINALS_DEVICE = 1                                         # QD_RELAY_FLAG_MARGINALS_DEVICE (qd_relay_params.reserved)
+SHRINK_STATE = 8                                                        # QD_SHRINK_STATE
+SHRINK_FAILS, SHRINK_MINIMAL, SHRINK_ENDED = 1, 2, 4                    # QD_SHRINK_*: the flag word of a parent's state
 
 
 class QdParams(C.Structure):
@@ -62,6 +64,7 @@ EXPORTS = [
     "qd_sample_dem_faults", "qd_commit_bits", "qd_fault_stats_batch",
     "qd_strata_create", "qd_strata_destroy", "qd_strata_info", "qd_sample_dem_strata",
     "qd_decoder_create_relay", "qd_decoder_relay_info",
+    "qd_shrink_begin", "qd_shrink_step",
 ]
 
 
@@ -148,6 +151,9 @@ def load():
         L.qd_decoder_create_relay.argtypes = [vp, C.POINTER(QdParams), C.POINTER(QdRelayParams), vp, C.POINTER(vp)]
     if hasattr(L, "qd_decoder_relay_info"):         # (library version 113; an older library named by QUITS_AMD_LIB keeps every Relay-BP decoder's marginals in LDS)
         L.qd_decoder_relay_info.argtypes = [vp, vp]
+    if hasattr(L, "qd_shrink_begin"):               # (library version 114; an older library named by QUITS_AMD_LIB samples and decodes as before)
+        L.qd_shrink_begin.argtypes = [vp, vp, vp, i64, i64, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, vp]
+        L.qd_shrink_step.argtypes = [vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, vp]
     _lib = L
     return L
 
@@ -196,6 +202,13 @@ def require_relay_forms(L):
     """The entry point of library version 113 (Relay-BP with its marginals in device memory): a clear error from an older library."""
     if not hasattr(L, "qd_decoder_relay_info"):
         raise RuntimeError("quits_amd: %s is version %d; choosing where Relay-BP keeps its marginals needs >= 113 -- rebuild it" % (LIB_PATH, L.qd_version()))
+    return L
+
+
+def require_shrink(L):
+    """The entry points of library version 114 (shrinking failing fault sets): a clear error from an older library."""
+    if not hasattr(L, "qd_shrink_begin"):
+        raise RuntimeError("quits_amd: %s is version %d; shrinking fault sets needs >= 114 -- rebuild it" % (LIB_PATH, L.qd_version()))
     return L
 
 

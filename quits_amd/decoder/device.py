@@ -393,6 +393,115 @@ class FaultStats:
         return self.hist.cpu().numpy(), self.counts.cpu().numpy(), lightest
 
 
+class FaultShrinker:
+    """The step of the fault-set shrinker on the device (qd_shrink_begin, qd_shrink_step; csrc/shrink.hip): quits_amd/shrink.py's walk, every
+    live parent advancing one trial per round.  The decode is the caller's, so that any decoder -- or a scripted verdict -- drives it:
+
+        shr.begin(packed_sets)
+        while not shr.done:
+            det, obs, fault, parent = shr.trials()          # cuda uint8 [A, m], uint8 [A, k], int32 [A], int32 [A]: row i = H (S \\ {j}), L (S \\ {j})
+            shr.commit(fail_mask)                           # Tally.add's mask of those A rows: bit i = the decoder fails on row i
+        res = shr.result()                                  # a quits_amd.shrink.ShrinkResult with packed sets, on the host
+
+    Per round the host reads one number, the count of live parents, which sizes the next decode.  `sets`, `kept_det`, `kept_obs` are the
+    current sets (cuda int32 [P, ceil(n / 32)]) and their H S and L S (cuda uint8), final once `done`."""
+
+    def __init__(self, check_matrix, observable_matrix, device: Optional[int] = None):
+        from scipy.sparse import csr_matrix
+        H, Lm = csr_matrix(check_matrix), csr_matrix(observable_matrix)
+        if H.shape[1] != Lm.shape[1]:
+            raise ValueError("the check matrix has %d columns, the observable matrix %d" % (H.shape[1], Lm.shape[1]))
+        self.H, self.L = GF2Matrix(H, device), GF2Matrix(Lm, device)
+        self.Ht, self.Lt = GF2Matrix(H.T.tocsr(), device), GF2Matrix(Lm.T.tocsr(), device)
+        self.m, self.n, self.k = int(H.shape[0]), int(H.shape[1]), int(Lm.shape[0])
+        self.words = (self.n + 31) // 32
+        self._L = _lib.require_shrink(self.Ht._L)
+        self.P = self._A = 0
+        self.rounds = 0
+        self.sets = None
+
+    def begin(self, packed_sets):
+        """packed_sets: int32 [P, >= ceil(n / 32)] words, a cuda tensor or a host array; copied, the caller's rows stay as they are."""
+        torch = _torch()
+        if isinstance(packed_sets, torch.Tensor):
+            t = packed_sets.to("cuda")
+        else:
+            t = torch.from_numpy(np.ascontiguousarray(packed_sets, dtype=np.int32)).to("cuda")
+        if t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] < self.words:
+            raise ValueError("packed sets must be int32 [parents, >= %d] words" % self.words)
+        self.sets = t[:, :self.words].clone().contiguous()
+        P = self.P = int(t.shape[0])
+        dev = self.sets.device
+        self.state = torch.zeros((P, _lib.SHRINK_STATE), dtype=torch.int32, device=dev)
+        self._live = [torch.empty((max(P, 1),), dtype=torch.int32, device=dev) for _ in range(2)]
+        self._count = torch.zeros((1,), dtype=torch.int32, device=dev)
+        self.kept_det = torch.zeros((P, self.m), dtype=torch.uint8, device=dev)
+        self.kept_obs = torch.zeros((P, self.k), dtype=torch.uint8, device=dev)
+        self._det = torch.empty((P, self.m), dtype=torch.uint8, device=dev)
+        self._obs = torch.empty((P, self.k), dtype=torch.uint8, device=dev)
+        self._fault = torch.empty((max(P, 1),), dtype=torch.int32, device=dev)
+        self._parent = torch.empty((max(P, 1),), dtype=torch.int32, device=dev)
+        self.rounds = 0
+        if P:
+            self.H.xor_apply(self.sets, self.kept_det, accumulate=False)
+            self.L.xor_apply(self.sets, self.kept_obs, accumulate=False)
+            _lib.check(self._L.qd_shrink_begin(self.Ht._h, self.Lt._h, _ptr(self.sets), self.words, P, _ptr(self.state), _ptr(self._live[0]),
+                                               _ptr(self._count), _ptr(self.kept_det), self.kept_det.stride(0), _ptr(self.kept_obs), self.kept_obs.stride(0),
+                                               _ptr(self._det), self._det.stride(0), _ptr(self._obs), self._obs.stride(0), _ptr(self._fault),
+                                               _ptr(self._parent), _stream_ptr()))
+        self._A = P
+        return self
+
+    @property
+    def done(self) -> bool:
+        return self._A == 0
+
+    @property
+    def live(self) -> int:
+        """The number of parents still walking = rows of the next `trials()`."""
+        return self._A
+
+    def trials(self):
+        """(det uint8 [A, m], obs uint8 [A, k], fault int32 [A], parent int32 [A]) of this round, views into the shrinker's buffers: row i is the
+        trial of parent[i] (ascending), the set without fault[i]; fault -1 is trial 0, the set itself."""
+        A = self._A
+        return self._det[:A], self._obs[:A], self._fault[:A], self._parent[:A]
+
+    def commit(self, fail_mask):
+        """The verdicts of this round's trials: a cuda int64 tensor of >= ceil(A / 64) words (Tally.add's fail mask of the A rows), or a bool
+        sequence of length A.  Applies them, compacts the live list and emits the next round's trials; then reads the live count."""
+        torch = _torch()
+        A = self._A
+        if A == 0:
+            return 0
+        if not (isinstance(fail_mask, torch.Tensor) and fail_mask.dtype == torch.int64):
+            v = np.asarray(fail_mask.cpu().numpy() if isinstance(fail_mask, torch.Tensor) else fail_mask).astype(bool).reshape(-1)
+            if v.shape[0] != A:
+                raise ValueError("%d verdicts for %d trials" % (v.shape[0], A))
+            pad = np.zeros(((A + 63) // 64) * 64, np.uint8)
+            pad[:A] = v
+            fail_mask = torch.from_numpy(np.packbits(pad, bitorder="little").view("<i8").copy()).to("cuda")
+        assert fail_mask.is_cuda and fail_mask.dim() == 1 and fail_mask.is_contiguous() and fail_mask.shape[0] >= (A + 63) // 64
+        _lib.check(self._L.qd_shrink_step(self.Ht._h, self.Lt._h, _ptr(self.sets), self.words, self.P, _ptr(self.state), _ptr(self._live[0]), A,
+                                          _ptr(fail_mask), _ptr(self._live[1]), _ptr(self._count), _ptr(self.kept_det), self.kept_det.stride(0),
+                                          _ptr(self.kept_obs), self.kept_obs.stride(0), _ptr(self._det), self._det.stride(0), _ptr(self._obs),
+                                          self._obs.stride(0), _ptr(self._fault), _ptr(self._parent), _stream_ptr()))
+        self._live.reverse()
+        self.rounds += 1
+        self._A = int(self._count.cpu()[0])          # the round's one host read: it sizes the next decode
+        return self._A
+
+    def result(self):
+        """quits_amd.shrink.ShrinkResult on the host (synchronises), `sets` as packed int32 [P, ceil(n / 32)] words."""
+        from ..shrink import ShrinkResult
+        if self.sets is None:
+            raise RuntimeError("begin() has not been called")
+        st = self.state.cpu().numpy().astype(np.int64)
+        flags = st[:, 4]
+        return ShrinkResult(self.sets.cpu().numpy(), (flags & _lib.SHRINK_FAILS) != 0, (flags & _lib.SHRINK_MINIMAL) != 0, st[:, 6].copy(),
+                            st[:, 2].copy(), st[:, 3].copy())
+
+
 def _shot_indices(indices):
     """int64 cuda tensor of shot indices from a tensor or any integer sequence."""
     torch = _torch()

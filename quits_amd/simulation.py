@@ -14,6 +14,10 @@
   get_stratified_pL                             the same experiment on shots with a prescribed number of faults (subset sampling): f(k) where
                                                 independent faults put no mass, pL = sum_k P(|E| = k) f(k) with an explicit truncation bound
   replay_strata_faults                          the fault sets of given shots of a stratum
+  shrink_fault_sets                             given fault sets shrunk to 1-minimal failing ones on the device (quits_amd/shrink.py has the definition)
+  get_minimal_failures                          the failing shots of such an experiment shrunk in one run: the lightest failing set (the exponent of
+                                                pL ~ p^t for this decoder) and the lightest undetectable residual (a bound on the distance)
+  get_relay_minimal_failures                    the same with the sliding-window Relay-BP decoder
 
 `get_codecap_pL` keeps the reference's signature and its random stream (`np.random.seed(seed)` followed by one
 `np.random.binomial(1, p, n)` per trial), so a given seed produces the same noise vectors as the reference.  With a plug-in
@@ -619,3 +623,303 @@ def replay_strata_faults(circuit, k, shot_indices, seed):
     smp = StratifiedDemSampler(H, L, priors, int(k))
     bits = smp.sample_shots_faults(shot_indices, int(k), int(seed))[2].cpu().numpy()
     return np.unpackbits(np.ascontiguousarray(bits).view(np.uint8), axis=1, bitorder="little")[:, :smp.nfaults].astype(bool)
+
+
+# ---- failing fault sets shrunk to 1-minimal ones ------------------------------------------------------------------------------------------
+@dataclasses.dataclass
+class MinimalFailuresResult:
+    """What `get_minimal_failures` returns.  shots, errors: decoded shots and failing ones, `get_fault_spectrum`'s numbers (with
+    shots_per_weight: `get_stratified_pL`'s, summed over the strata).  parents: failing shots that were shrunk -- the first `max_parents` in
+    shot order -- and parents_truncated: failing shots beyond them, counted only.  Per parent, in that order: parent_shots (global shot
+    index; with strata the index inside the stratum parent_strata[i]), start_weights = |E|, weights = |S| of the 1-minimal set S it ended on,
+    minimal (the walk of quits_amd/shrink.py ended: True for every parent of a finished run), trials (decodes spent on it).
+    start_weight_hist[w], weight_hist[w] (int64 [256], bin 255: >= 255): parents by |E| and by |S|.  lightest: (|S|, shot) of the lightest final
+    set, ties to the earlier parent, or None: the decoder fails on a set of that many faults, so pL falls no faster than p^|S|.
+    sets, set_shots, set_weights (set_strata): the `keep_sets` lightest final sets, packed int32 [., ceil(nfaults / 32)] words (bit j & 31 of
+    word j >> 5 = column j of detector_error_model_to_matrix), lightest first.  residual_weight_hist[w]: final sets whose correction C
+    reproduces the syndrome, by the weight of S xor C -- an undetectable logical fault; lightest_residual: (weight, shot) of the lightest, or
+    None: an upper bound on the circuit-level distance.  rounds: decode rounds of the shrink (the longest walk), decodes: trial rows it
+    decoded; seconds: the whole call, timing: its parts -- "find" (sample, decode, gather), "shrink", "final" (the final sets decoded once with
+    their corrections), and with profile=True "shrink_decode", the part of "shrink" inside plan.decode (a device synchronise around every
+    call: a profiling mode, it slows the run)."""
+    shots: int
+    errors: int
+    parents: int
+    parents_truncated: int
+    start_weight_hist: np.ndarray
+    weight_hist: np.ndarray
+    lightest: object
+    sets: np.ndarray
+    set_shots: np.ndarray
+    set_weights: np.ndarray
+    residual_weight_hist: np.ndarray
+    lightest_residual: object
+    rounds: int
+    decodes: int
+    seconds: float
+    parent_shots: np.ndarray = None
+    start_weights: np.ndarray = None
+    weights: np.ndarray = None
+    minimal: np.ndarray = None
+    trials: np.ndarray = None
+    parent_strata: object = None
+    set_strata: object = None
+    seed: int = 0
+    batch: int = 0
+    timing: dict = dataclasses.field(default_factory=dict)
+
+
+def _decoder_choice(relay, max_iter, osd_order, bp_method, schedule, osd_method):
+    """(plug-in class, its keyword dict -- the cached plan's key) of the BP + OSD / LSD keywords, or of Relay-BP where `relay` is a RelayConfig."""
+    if relay is None:
+        from .decoder.bposd import BpOsdDecoder
+        return BpOsdDecoder, {'bp_method': bp_method, 'max_iter': max_iter, 'schedule': schedule,
+                              'osd_method': 'osd_cs' if osd_method is None else osd_method, 'osd_order': osd_order}
+    from .decoder.relaybp import RelayBpDecoder, relay_options
+    return RelayBpDecoder, relay_options(relay, 'osd_off' if osd_method is None else osd_method, osd_order)
+
+
+def _fault_model_plan(circuit, hz, lz, W, F, decoder, opts):
+    """(Circuit, H, L, priors, cached plan) of a circuit's detector error model, checked as get_fault_spectrum checks them."""
+    import warnings
+    from .decoder.base import detector_error_model_to_matrix, window_count
+    from .decoder.plan import cached_circuit_plan
+    if F == 0:
+        raise ValueError("Input parameter F cannot be zero.")
+    circ = _as_circuit(circuit)
+    H, L, priors = detector_error_model_to_matrix(circ.detector_error_model())
+    nz = hz.shape[0]
+    num_rounds = H.shape[0] // nz - 2
+    if window_count(num_rounds, W, F)[2]:
+        warnings.warn("Window size larger than the syndrome extraction rounds: Doing whole history correction")
+    plan = cached_circuit_plan(circ, hz, W, F, num_rounds, decoder, decoder, opts, opts)
+    if L.shape[0] != plan.nobs or np.asarray(lz.shape)[0] != plan.nobs:
+        raise ValueError("the circuit has %d observables, lz %d rows, the window plan commits %d" % (L.shape[0], lz.shape[0], plan.nobs))
+    if plan.nfaults != H.shape[1]:
+        raise ValueError("the windows commit %d faults, the detector error model has %d" % (plan.nfaults, H.shape[1]))
+    return circ, H, L, priors, plan
+
+
+def _shrink_on_plan(plan, shr, sets, batch, timing=None):
+    """The one loop of shrink_fault_sets and get_minimal_failures (inside plan.in_use()): `shr`, a decoder.device.FaultShrinker, walks the packed
+    `sets`; every round's trial rows are decoded by `plan` in pieces of `batch` rows and tallied, and the fail mask goes back to the shrinker.
+    Per round the host learns the number of live parents, nothing else.  Returns the number of trial rows decoded.  timing: a dict that
+    receives "shrink_decode", the seconds inside plan.decode, measured with a device synchronise on either side of every call, and what the
+    status words say of the trial rows: "trial_mean_iterations" (BP iterations per row and window), "trial_unconverged_share" (rows of a
+    window BP did not solve: the post-processor's, or with 'osd_off' returned as they were) and "trial_later_leg_share" (rows whose status
+    word has a bit of the Relay-BP leg field set: with Relay-BP the rows whose output came from a leg after the first; other decoders do not
+    define the field)."""
+    import time
+    import torch
+    from . import _lib
+    from .decoder.device import Tally
+    step = _batch_step(batch)
+    tally = Tally(plan.nobs)
+    decodes = 0
+    inside = 0.0
+    seen = torch.zeros((4,), dtype=torch.int64, device="cuda") if timing is not None else None      # status words, iterations, converged, leg >= 1
+    shr.begin(sets)
+    while not shr.done:
+        det, obs, _, _ = shr.trials()
+        A = det.shape[0]
+        mask = torch.empty(((A + 63) // 64,), dtype=torch.int64, device=det.device)
+        for c0 in range(0, A, step):
+            n = min(step, A - c0)
+            if timing is not None:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+            stats = None if timing is None else []
+            pred = plan.decode(det[c0:c0 + n], stats)
+            if timing is not None:
+                torch.cuda.synchronize()
+                inside += time.perf_counter() - t0
+                for _, st in stats:
+                    seen += torch.stack([torch.tensor(st.numel(), device=st.device), (st & _lib.STATUS_ITER_MASK).sum(),
+                                         ((st & _lib.STATUS_CONVERGED) != 0).sum(), ((st & _lib.STATUS_RELAY_LEG_MASK) != 0).sum()])
+            tally.add(pred, obs[c0:c0 + n], None, mask[c0 // 64:c0 // 64 + (n + 63) // 64])
+        shr.commit(mask)
+        decodes += A
+    if timing is not None:
+        timing["shrink_decode"] = inside
+        words, iters, conv, later = (int(x) for x in seen.cpu())
+        if words:
+            timing.update(trial_mean_iterations=iters / words, trial_unconverged_share=1.0 - conv / words, trial_later_leg_share=later / words)
+    return decodes
+
+
+def _default_batch(plan):
+    return max(2, int(plan.lanes) if plan.pipeline else 2) * int(plan.chunk)
+
+
+def shrink_fault_sets(circuit, hz, lz, W, F, fault_sets, max_iter=2, osd_order=0, bp_method='product_sum', schedule='serial', osd_method=None,
+                      *, relay=None, batch=None):
+    """Shrink fault sets of the circuit's detector error model to 1-minimal failing ones (quits_amd/shrink.py states the walk): a set S fails
+    iff the sliding-window decoder's prediction for the detector bits H S differs from L S.  The decoder keywords are
+    `sliding_window_bposd_circuit_mem`'s (same cached plan); relay=RelayConfig switches to the Relay-BP plan of
+    `sliding_window_relaybp_circuit_mem`.  osd_method None: 'osd_cs', with `relay` 'osd_off'.  The trial rows are made, decoded and judged on
+    the device (decoder.device.FaultShrinker); the host reads one count per round.
+
+    fault_sets: bool [P, nfaults] (column j = column j of detector_error_model_to_matrix), or packed int32 [P, ceil(nfaults / 32)] words (numpy
+    or a cuda tensor; bit j & 31 of word j >> 5).  batch: rows per decode call (default: as in get_fault_spectrum); no result depends on it.
+
+    Returns a quits_amd.shrink.ShrinkResult: sets in the form they came in (packed ones as numpy), fails, minimal, start_weight, weight,
+    trials per parent.  A parent that does not fail comes back unchanged with fails = False."""
+    from . import _lib
+    from . import shrink as sk
+    decoder, opts = _decoder_choice(relay, max_iter, osd_order, bp_method, schedule, osd_method)
+    _lib.require_shrink(_lib.require_faults(_lib.require_experiment(_lib.require_gpu())))
+    import torch
+    from .decoder.device import FaultShrinker
+    circ, H, L, priors, plan = _fault_model_plan(circuit, hz, lz, W, F, decoder, opts)
+    n, words = plan.nfaults, (plan.nfaults + 31) // 32
+    packed_in = isinstance(fault_sets, torch.Tensor) or (np.asarray(fault_sets).dtype != np.bool_ and np.asarray(fault_sets).ndim == 2
+                                                         and np.asarray(fault_sets).shape[1] != n)
+    if packed_in:
+        sets = fault_sets if isinstance(fault_sets, torch.Tensor) else np.ascontiguousarray(fault_sets, dtype=np.int32)
+        if sets.ndim != 2 or sets.shape[1] < words:
+            raise ValueError("packed fault sets must be int32 [parents, >= %d] words" % words)
+    else:
+        bits = np.asarray(fault_sets)
+        if bits.ndim != 2 or bits.shape[1] != n:
+            raise ValueError("fault_sets must be a [parents, %d] array, one column per fault of the detector error model" % n)
+        sets = sk.pack_sets(bits != 0)
+    shr = FaultShrinker(H, L)
+    with plan.in_use():
+        _shrink_on_plan(plan, shr, sets, _default_batch(plan) if batch is None else batch)
+        res = shr.result()
+    if not packed_in:
+        res.sets = sk.unpack_sets(res.sets, n)
+    return res
+
+
+def _failing_rows(mask, n):
+    """Ascending row indices (cuda int64) of the set bits of a fail mask over n rows."""
+    import torch
+    bits = (mask[:(n + 63) // 64, None] >> torch.arange(64, device=mask.device, dtype=torch.int64)[None, :]) & 1
+    return torch.nonzero(bits.reshape(-1)[:n], as_tuple=False).reshape(-1)
+
+
+def get_minimal_failures(circuit, hz, lz, W, F, num_trials, max_iter=2, osd_order=0, bp_method='product_sum', schedule='serial',
+                         osd_method='osd_cs', *, seed=0, batch=None, shots_per_weight=None, max_parents=1 << 16, keep_sets=256, profile=False):
+    """`get_fault_spectrum`, and then every failing shot's fault set shrunk to a 1-minimal failing set: the same `num_trials` DEM-sampled shots
+    of `seed` (same rows, same decoder keywords, same cached plan, so `shots` and `errors` are that function's), the failing rows gathered on
+    the device, shrunk there in one run (quits_amd/shrink.py; decoder.device.FaultShrinker; a trial is one decode), and the final sets decoded
+    once more with their space-time corrections for the residuals S xor C.  With shots_per_weight (k -> N_k) the shots are
+    `get_stratified_pL`'s instead -- N_k rows of exactly k faults per stratum, same rows for the same seed -- and `num_trials` is ignored.
+
+    max_parents: failing shots beyond the first `max_parents` are counted (parents_truncated), not shrunk.  keep_sets: how many of the
+    lightest final sets to return.  batch: as in get_fault_spectrum; the result does not depend on it.  profile: see MinimalFailuresResult.
+
+    Returns a MinimalFailuresResult.  `replay_faults(circuit, [shot], seed)` (`replay_strata_faults` with strata) regenerates the parent of a
+    set; `shrink_fault_sets` shrinks given sets."""
+    decoder, opts = _decoder_choice(None, max_iter, osd_order, bp_method, schedule, osd_method)
+    return _minimal_failures(circuit, hz, lz, W, F, num_trials, decoder, opts, seed=seed, batch=batch, shots_per_weight=shots_per_weight,
+                             max_parents=max_parents, keep_sets=keep_sets, profile=profile)
+
+
+def get_relay_minimal_failures(circuit, hz, lz, W, F, num_trials, relay=None, osd_method='osd_off', osd_order=0, *, seed=0, batch=None,
+                               shots_per_weight=None, max_parents=1 << 16, keep_sets=256, profile=False):
+    """`get_minimal_failures` with the sliding-window Relay-BP decoder (the plan of `get_relay_mem_pL`): `relay` is a quits_amd.relay.RelayConfig
+    (default RelayConfig()), `osd_method` / `osd_order` the post-processor of the shots no leg solves.  Every other argument and the result are
+    that function's."""
+    from .relay import RelayConfig
+    decoder, opts = _decoder_choice(RelayConfig() if relay is None else relay, 0, osd_order, None, None, osd_method)
+    return _minimal_failures(circuit, hz, lz, W, F, num_trials, decoder, opts, seed=seed, batch=batch, shots_per_weight=shots_per_weight,
+                             max_parents=max_parents, keep_sets=keep_sets, profile=profile)
+
+
+def _minimal_failures(circuit, hz, lz, W, F, num_trials, decoder, opts, *, seed, batch, shots_per_weight, max_parents, keep_sets, profile):
+    """The loop of get_minimal_failures and get_relay_minimal_failures: `decoder` is the plug-in class of both window kinds, `opts` its keyword
+    dict (the cached plan's key)."""
+    import time
+    from . import _lib
+    from . import strata as st
+    t_start = time.perf_counter()
+    todo = None if shots_per_weight is None else _strata_plan(shots_per_weight)
+    if int(max_parents) < 0 or int(keep_sets) < 0:
+        raise ValueError("max_parents and keep_sets must not be negative")
+    _lib.require_shrink(_lib.require_faults(_lib.require_experiment(_lib.require_gpu())))
+    if todo is not None:
+        _lib.require_strata(_lib.load())
+    import torch
+    from .decoder.device import DemSampler, FaultShrinker, FaultStats, StratifiedDemSampler, Tally
+    circ, H, L, priors, plan = _fault_model_plan(circuit, hz, lz, W, F, decoder, opts)
+    nobs, nfaults, words = plan.nobs, plan.nfaults, (plan.nfaults + 31) // 32
+    if batch is None:
+        batch = _default_batch(plan)
+    step = _batch_step(batch)
+    if todo is None:
+        smp = DemSampler(H, L, priors)
+        work = [(None, shot0, n) for shot0, n in experiment_batches(num_trials, batch)]
+    else:
+        smp = StratifiedDemSampler(H, L, priors, max([k for k, _ in todo], default=0))
+        if todo:
+            st.check_ks(np.array([k for k, _ in todo]), len(todo), priors, smp.kmax)
+        work = [(k, shot0, n) for k, nk in todo for shot0, n in experiment_batches(nk, batch)]
+    if work and max(shot0 + n for _, shot0, n in work) > 1 << 40:
+        raise ValueError("shot indices must stay below 2^40")
+    shr = FaultShrinker(H, L)
+    timing = {}
+    with plan.in_use():
+        tally = Tally(nobs)
+        got_sets, got_shots, got_strata = [], [], []
+        kept = 0
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for k, shot0, n in work:
+            det, obs, faults = smp.sample_faults(n, seed, shot0) if k is None else smp.sample_faults(k, seed, shot0, shots=n)
+            pred = plan.decode(det)
+            mask = torch.empty(((n + 63) // 64,), dtype=torch.int64, device="cuda")
+            tally.add(pred, obs, None, mask)
+            if kept < max_parents:
+                rows = _failing_rows(mask, n)[:max_parents - kept]
+                if rows.numel():
+                    got_sets.append(faults[:, :words].index_select(0, rows))
+                    got_shots.append(rows + shot0)
+                    got_strata.append(torch.full_like(rows, -1 if k is None else k))
+                    kept += int(rows.numel())
+        sets = torch.cat(got_sets) if got_sets else torch.zeros((0, words), dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        decodes = _shrink_on_plan(plan, shr, sets, batch, timing if profile else None)
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        P = int(sets.shape[0])
+        fstats, final = FaultStats(), Tally(nobs)
+        for c0 in range(0, P, step):
+            n = min(step, P - c0)
+            det = shr.kept_det[c0:c0 + n].clone()
+            corr = torch.empty((n, words), dtype=torch.int32, device="cuda")
+            pred = plan.decode(det, None, corr)
+            mask = torch.empty(((n + 63) // 64,), dtype=torch.int64, device="cuda")
+            final.add(pred, shr.kept_obs[c0:c0 + n], None, mask)
+            shr.H.xor_apply(corr, det, accumulate=True)            # det becomes the residual H C xor H S in place
+            fstats.add(shr.sets[c0:c0 + n], corr, nfaults, det, mask, c0)
+        torch.cuda.synchronize()
+        t3 = time.perf_counter()
+        tc = tally.counts()
+        res = shr.result()
+        hist, counts, best = fstats.result()
+        parent_shots = torch.cat(got_shots).cpu().numpy() if got_shots else np.zeros((0,), np.int64)
+        parent_strata = torch.cat(got_strata).cpu().numpy() if got_strata else np.zeros((0,), np.int64)
+    timing.update(find=t1 - t0, shrink=t2 - t1, final=t3 - t2)
+    shots, errors = int(tc[0]), int(tc[1])
+    if not res.fails.all() or P != min(errors, int(max_parents)):
+        raise RuntimeError("%d failing shots, %d parents gathered, %d of them fail when decoded again: the decoder does not return the same "
+                           "bits for a row whatever batch it sits in" % (errors, P, int(res.fails.sum())))
+    if int(counts[1]) != P:
+        raise RuntimeError("%d final sets, %d of them fail when decoded with their corrections" % (P, int(counts[1])))
+    clip = lambda w: np.bincount(np.minimum(w, _lib.FAULT_HIST - 1), minlength=_lib.FAULT_HIST).astype(np.int64)
+    weight_hist = clip(res.weight)
+    if not np.array_equal(weight_hist, hist[1]):
+        raise RuntimeError("the final sets' weights disagree: the shrinker's state %s, the sets %s" % (np.flatnonzero(weight_hist).tolist(), np.flatnonzero(hist[1]).tolist()))
+    order = np.lexsort((np.arange(P), res.weight))                 # lightest first, ties to the earlier parent
+    top = order[:int(keep_sets)]
+    strata_of = (lambda a: None) if todo is None else (lambda a: a.copy())
+    return MinimalFailuresResult(
+        shots, errors, P, errors - P, clip(res.start_weight), weight_hist,
+        (int(res.weight[order[0]]), int(parent_shots[order[0]])) if P else None,
+        res.sets[top].copy(), parent_shots[top].copy(), res.weight[top].copy(), hist[2].copy(),
+        None if best is None else (int(best[0]), int(parent_shots[int(best[1])])),
+        int(shr.rounds), int(decodes), time.perf_counter() - t_start, parent_shots, res.start_weight, res.weight, res.minimal, res.trials,
+        strata_of(parent_strata), strata_of(parent_strata[top]), int(seed), step, timing)
