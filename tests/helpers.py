@@ -161,3 +161,29 @@ def oracle_decode_batch_parallel(H, pri, synd, prm, device_grid_max_iter=None):
     with mp.get_context("fork").Pool(min(n, len(parts))) as pool:
         res = pool.map(_batch_worker, [(H, pri, p, prm, device_grid_max_iter) for p in parts])
     return np.concatenate([r[0] for r in res], axis=0), np.concatenate([r[1] for r in res], axis=0)
+
+
+def _osd_w_worker(args):
+    import oracle as orc
+    H, pri, synd, llr, method, order = args
+    g = orc.Graph(H, pri)
+    err = np.zeros((len(synd), g.n), np.uint8)
+    st = np.zeros((len(synd), 3), np.int64)
+    for b in range(len(synd)):
+        err[b], s = g.osd_w(synd[b], llr[b].astype(np.float64), method, order, fixed=True)
+        st[b] = s["pivots"], s["winner"], s["candidates"]
+    return err, st
+
+
+def oracle_osd_w_parallel(H, pri, synd, llr, method, order):
+    """Graph.osd_w(.., fixed=True) -- higher-order OSD alone on given soft information, integer candidate costs -- shot by shot in a fork
+    pool.  Returns (corrections [B, n], stats [B, 3] = pivots, 1 + index of the winning candidate (0: OSD-0 kept), candidates)."""
+    import multiprocessing as mp
+    synd, llr = np.ascontiguousarray(synd), np.ascontiguousarray(llr)
+    n = min(12, _oracle_procs(), len(synd))
+    if n <= 1:
+        return _osd_w_worker((H, pri, synd, llr, method, order))
+    parts = [p for p in np.array_split(np.arange(len(synd)), n) if len(p)]
+    with mp.get_context("fork").Pool(len(parts)) as pool:
+        res = pool.map(_osd_w_worker, [(H, pri, synd[p], llr[p], method, order) for p in parts])
+    return np.concatenate([r[0] for r in res], axis=0), np.concatenate([r[1] for r in res], axis=0)
