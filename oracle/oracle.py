@@ -199,11 +199,12 @@ class Graph:
         costs (the HIP kernel's arithmetic)."""
         s = np.ascontiguousarray(np.asarray(syndrome) % 2, dtype=np.uint8)
         err = np.zeros(self.n, np.uint8)
-        st = np.zeros(8, np.int32)
+        st = np.zeros(10, np.int32)
         lib().oq_lsd(self._h, s, np.ascontiguousarray(llr, dtype=np.float64), OSD_METHOD[lsd_method], int(lsd_order),
                      int(bool(fixed)), err, st)
         return err, {"pivots": int(st[0]), "added": int(st[1]), "inconsistent": bool(st[2]), "rounds": int(st[3]),
-                     "grown": int(st[4]), "swept": int(st[5]), "replaced": int(st[6])}
+                     "grown": int(st[4]), "swept": int(st[5]), "replaced": int(st[6]), "clusters": int(st[7]), "merges": int(st[8]),
+                     "max_candidates": int(st[9])}
 
     def osd_w(self, syndrome, llr, osd_method="osd_cs", osd_order=1, fixed=False):
         """OSD-CS / OSD-E.  fixed=True: integer candidate costs (the HIP kernel's arithmetic); returns (err, stats)."""

@@ -503,7 +503,7 @@ typedef struct {
     oq_elim E;
     uint8_t *t, *added, *state, *ispiv;
     int *owner, *nbits, *addlist;
-    int nadded, inconsistent;
+    int nadded, inconsistent, merges;
 } oq_lsd_ctx;
 
 /* one growth step of cluster c; 0 if the cluster has no fault left to add (an invalid cluster is then retired: it can
@@ -531,7 +531,7 @@ static int lsd_grow(oq_lsd_ctx *x, int c, int retire)
         if (d == c) continue;
         if (d < 0) { x->owner[i] = c; continue; }
         for (int r = 0; r < m; r++) if (x->owner[r] == d) x->owner[r] = c;     /* absorb cluster d */
-        x->nbits[c] += x->nbits[d]; x->state[d] = 3;
+        x->nbits[c] += x->nbits[d]; x->state[d] = 3; x->merges++;
     }
     x->ispiv[best] = (uint8_t)elim_add_column(g, &x->E, best, x->t);
     int bad = 0;
@@ -547,14 +547,15 @@ static int lsd_cluster_dimension(const oq_lsd_ctx *x, int c)
     return x->nbits[c] - piv;
 }
 
-/* stats: pivots, faults added, inconsistent flag, growth rounds; [4..6] (if order > 0): faults added by the growth stage,
- * clusters swept, clusters whose LSD-0 solution was replaced */
+/* stats (ten entries): pivots, faults added, inconsistent flag, growth rounds; [4..6] (zero at order 0): faults added by the
+ * growth stage, clusters swept, clusters whose LSD-0 solution was replaced; [7..9]: valid clusters at the end, clusters
+ * absorbed by another (merges), the largest number of candidate positions in one swept cluster */
 int oq_lsd(oq_graph *g, const uint8_t *synd, const double *llr, int lsd_method, int lsd_order, int fixed, uint8_t *err,
            int32_t *stats)
 {
     const int m = g->m, n = g->n;
     oq_lsd_ctx x;
-    x.g = g; x.llr = llr; x.nadded = 0; x.inconsistent = 0;
+    x.g = g; x.llr = llr; x.nadded = 0; x.inconsistent = 0; x.merges = 0;
     elim_init(g, synd, &x.E);
     x.t = (uint8_t *)malloc((size_t)m + 1);
     x.added = (uint8_t *)calloc((size_t)n + 1, 1);
@@ -564,7 +565,7 @@ int oq_lsd(oq_graph *g, const uint8_t *synd, const double *llr, int lsd_method, 
     x.state = (uint8_t *)calloc((size_t)m + 1, 1);                /* per cluster id: 0 none, 1 active+invalid, 2 active+valid, 3 gone */
     x.addlist = (int *)malloc(sizeof(int) * (size_t)(n + 1));
     int *round = (int *)malloc(sizeof(int) * (size_t)(m + 1));
-    int rounds = 0, grown = 0, swept = 0, replaced = 0;
+    int rounds = 0, grown = 0, swept = 0, replaced = 0, nvalid = 0, maxcand = 0;
     for (int i = 0; i < m; i++) { x.owner[i] = (synd[i] & 1) ? i : -1; x.state[i] = (synd[i] & 1) ? 1 : 0; }
     for (;;) {
         int nr = 0;
@@ -612,6 +613,7 @@ int oq_lsd(oq_graph *g, const uint8_t *synd, const double *llr, int lsd_method, 
             }
             if (!kk) continue;
             swept++;
+            if (kk > maxcand) maxcand = kk;
             qsort(np, (size_t)kk, sizeof(oq_sortrec), cmp_sortrec);
             for (int k = 0; k < x.E.npiv; k++) if (x.owner[x.E.prow[k]] == c) cpk[npk++] = k;
             double base = 0;
@@ -665,8 +667,10 @@ int oq_lsd(oq_graph *g, const uint8_t *synd, const double *llr, int lsd_method, 
         free(wd); free(np); free(cpk); free(flip); free(bestflip);
     }
     if (stats) {
+        for (int c = 0; c < m; c++) nvalid += x.state[c] == 2;
         stats[0] = x.E.npiv; stats[1] = x.nadded; stats[2] = x.inconsistent; stats[3] = rounds;
-        if (order > 0) { stats[4] = grown; stats[5] = swept; stats[6] = replaced; }
+        stats[4] = grown; stats[5] = swept; stats[6] = replaced;
+        stats[7] = nvalid; stats[8] = x.merges; stats[9] = maxcand;
     }
     elim_free(&x.E); free(x.t); free(x.added); free(x.ispiv); free(x.owner); free(x.nbits); free(x.state); free(x.addlist); free(round);
     return 0;
@@ -674,7 +678,10 @@ int oq_lsd(oq_graph *g, const uint8_t *synd, const double *llr, int lsd_method, 
 
 int oq_lsd0(oq_graph *g, const uint8_t *synd, const double *llr, uint8_t *err, int32_t *stats)
 {
-    return oq_lsd(g, synd, llr, OQ_LSD_0, 0, 0, err, stats);
+    int32_t st[10];
+    const int rc = oq_lsd(g, synd, llr, OQ_LSD_0, 0, 0, err, st);
+    if (stats) memcpy(stats, st, 4 * sizeof(int32_t));
+    return rc;
 }
 
 /* Candidate cost.  ldpc sums log(1/p_j) in double (osd.hpp).  `fixed` != 0 switches to the integer weights the HIP
@@ -805,9 +812,9 @@ int oq_bposd_decode(oq_graph *g, const oq_params *prm, const uint8_t *synd, uint
     if (!conv && prm->osd_method != OQ_OSD_OFF) {
         const int dev_costs = prm->form == OQ_FORM_COMPRESSED_F32 || prm->form == OQ_FORM_LDPC_F32 || g->llr_frac_bits >= 0;
         if (prm->osd_method == OQ_LSD_0 || prm->osd_method == OQ_LSD_E || prm->osd_method == OQ_LSD_CS) {
-            int32_t st7[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            oq_lsd(g, synd, llr, prm->osd_method, prm->osd_order, dev_costs, err, st7);
-            st[0] = st7[0]; st[2] = st7[2];
+            int32_t stl[10] = {0};
+            oq_lsd(g, synd, llr, prm->osd_method, prm->osd_order, dev_costs, err, stl);
+            st[0] = stl[0]; st[2] = stl[2];
         }
         else if (prm->osd_method == OQ_OSD_0 || prm->osd_order == 0) oq_osd0(g, synd, llr, 1, err, st);
         else osd_w_impl(g, synd, llr, prm->osd_method, prm->osd_order,

@@ -187,3 +187,43 @@ def oracle_osd_w_parallel(H, pri, synd, llr, method, order):
     with mp.get_context("fork").Pool(len(parts)) as pool:
         res = pool.map(_osd_w_worker, [(H, pri, synd[p], llr[p], method, order) for p in parts])
     return np.concatenate([r[0] for r in res], axis=0), np.concatenate([r[1] for r in res], axis=0)
+
+
+def _lsd_worker(args):
+    import oracle as orc
+    H, pri, synd, llr, method, order = args
+    g = orc.Graph(H, pri)
+    err = np.zeros((len(synd), g.n), np.uint8)
+    st = np.zeros((len(synd), len(LSD_STATS)), np.int64)
+    for b in range(len(synd)):
+        err[b], s = g.lsd(synd[b], llr[b].astype(np.float64), method, order, fixed=True)
+        st[b] = [int(s[k]) for k in LSD_STATS]
+    return err, st
+
+
+LSD_STATS = ("pivots", "added", "inconsistent", "rounds", "grown", "swept", "replaced", "clusters", "merges", "max_candidates")
+
+
+def oracle_lsd_parallel(H, pri, synd, llr, method, order):
+    """Graph.lsd(.., fixed=True) -- BP-LSD's post-processing alone on given soft information, integer candidate costs; method 'lsd_0' or
+    order 0 is LSD-0 -- shot by shot in a fork pool.  Returns (corrections [B, n], stats [B, 10] in the order of LSD_STATS)."""
+    import gc
+    import multiprocessing as mp
+    synd, llr = np.ascontiguousarray(synd), np.ascontiguousarray(llr)
+    n = min(16, _oracle_procs(), len(synd))          # the children inherit the parent's open device: no more of them than a GPU machine lets hold one
+    if n <= 1:
+        return _lsd_worker((H, pri, synd, llr, method, order))
+    parts = [np.arange(k, len(synd), n) for k in range(n)]             # strided: heavy shots often come in runs
+    # what a failed test left behind (frames that hold device handles) must not be destroyed by a child's collector after the fork: the children
+    # inherit it in the permanent generation, which their collector leaves alone
+    gc.freeze()
+    try:
+        with mp.get_context("fork").Pool(n) as pool:
+            res = pool.map(_lsd_worker, [(H, pri, synd[p], llr[p], method, order) for p in parts])
+    finally:
+        gc.unfreeze()
+    err = np.zeros((len(synd), res[0][0].shape[1]), np.uint8)
+    st = np.zeros((len(synd), len(LSD_STATS)), np.int64)
+    for p, (e, s) in zip(parts, res):
+        err[p], st[p] = e, s
+    return err, st

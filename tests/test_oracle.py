@@ -391,6 +391,34 @@ def test_higher_order_lsd_small_case_by_brute_force():
     assert e2.tolist() == [0, 0, 1, 0, 0, 0] and st2["replaced"] == 0
 
 
+def test_lsd_cluster_counters_on_the_small_case():
+    """oq_lsd's counters of valid clusters, absorbed clusters and candidate positions on the chain of the test above, by hand; lsd0 keeps its four."""
+    from scipy.sparse import csc_matrix
+    H = csc_matrix(np.array([[1, 1, 0, 0, 0, 0],
+                             [0, 1, 1, 1, 0, 0],
+                             [0, 0, 1, 1, 1, 0],
+                             [0, 0, 0, 0, 1, 1]], dtype=np.uint8))
+    g = orc.Graph(H, np.array([0.01, 0.01, 0.001, 0.2, 0.01, 0.01]))
+    count = lambda st: (st["clusters"], st["merges"], st["max_candidates"])
+    # checks 1 and 2: the cluster of check 1 takes fault 2 (lowest LLR), whose other check is the seed of the second cluster: one absorbed, one left
+    s, llr = np.array([0, 1, 1, 0], np.uint8), np.array([3.0, 3.0, 0.5, 1.0, 3.0, 3.0])
+    assert count(g.lsd(s, llr, "lsd_0", 0)[1]) == (1, 1, 0)
+    assert count(g.lsd(s, llr, "lsd_cs", 1)[1]) == (1, 1, 1)              # the growth stage adds fault 3, the twin of fault 2: one candidate position
+    assert sorted(g.lsd0(s, llr)[1]) == ["added", "inconsistent", "pivots", "rounds"]
+    # checks 0 and 3 with the end faults 0 and 5 likely: two clusters of one fault each, valid after one round, nothing absorbed
+    s, llr = np.array([1, 0, 0, 1], np.uint8), np.array([0.5, 3.0, 3.0, 3.0, 3.0, 0.5])
+    e, st = g.lsd(s, llr, "lsd_0", 0)
+    assert e.tolist() == [1, 0, 0, 0, 0, 1] and count(st) == (2, 0, 0) and st["rounds"] == 1
+    # order 2: cluster 0 grows by faults 1 and 2 (both pivots, two additions: its share), then cluster 3 takes fault 4, whose check 2 belongs to
+    # cluster 0 by now -- absorbed -- and fault 3; faults 4 and 3 depend on the pivots: two candidate positions in the one cluster left
+    e, st = g.lsd(s, llr, "lsd_cs", 2)
+    assert count(st) == (1, 1, 2) and st["grown"] == 4 and st["swept"] == 1 and st["pivots"] == 4 and st["added"] == 6
+    # an inconsistent syndrome: the retired cluster is neither valid nor absorbed
+    g3 = orc.Graph(csc_matrix(np.array([[1, 1, 0], [0, 1, 1], [1, 0, 1]], dtype=np.uint8)), np.array([0.01, 0.02, 0.03]))
+    e, st = g3.lsd(np.array([1, 0, 0], np.uint8), np.zeros(3), "lsd_cs", 2)
+    assert st["inconsistent"] and count(st) == (0, 0, 0) and st["added"] == 3
+
+
 def test_native_build_matches_portable(tmp_path):
     """bench.py's cpu_baseline leg times a `-O3 -march=native` build of the port made on the host it runs on (oracle/_native/, never
     shipped).  With -ffp-contract=off the two builds must agree bit for bit: decode the same shots with both (the native one in a
