@@ -391,6 +391,43 @@ int qd_shrink_step(const qd_spmat *Ht, const qd_spmat *Lt, uint32_t *d_sets, int
                    int64_t hs_stride, uint8_t *d_ls, int64_t ls_stride, uint8_t *d_det, int64_t det_stride, uint8_t *d_obs, int64_t obs_stride,
                    int32_t *d_fault, int32_t *d_parent, void *stream);
 
+/* ---- the directed search for light undetectable logical faults (version 115).  quits_amd/search.py states the search: a breadth-first search
+ *      over states (S, o), S a sorted set of at most K <= 8 detectors, o a mask of at most 64 observables; a level-(l + 1) state is a level-l
+ *      state xor an admitted fault that contains its smallest detector.  Stands in for Stim's search_for_undetectable_logical_errors, which
+ *      the reference's examples/circuit_distance_search.py calls.  A state is a record of QD_SEARCH_RECORD bytes: two 64-bit words of eight
+ *      16-bit detectors (ascending from bit 0 of the first word, 0xFFFF = empty), the 64-bit mask, the 32-bit pool index of its parent
+ *      (0xFFFFFFFF at level 1) and the 32-bit fault that led to it.  The pool holds the states in level order; logical_search.hip describes
+ *      the visited table and the staging area.  One level per call; the host reads the counters after each and decides. */
+typedef struct qd_search qd_search;
+#define QD_SEARCH_RECORD 32
+#define QD_SEARCH_COUNTERS 8
+#define QD_SEARCH_OVER_POOL 1   /* counters[3]: more distinct states than max_states (the outcome `capacity`)   */
+#define QD_SEARCH_OVER_TABLE 2  /* ... the visited table is full                                                */
+#define QD_SEARCH_OVER_STAGE 4  /* ... a chunk staged more candidates than stage_states                         */
+#define QD_SEARCH_OVER_FOUND 8  /* ... more than 65536 states (empty, o) in one level                           */
+/* row_ptr [ndet + 1], row_faults: the admitted faults of every detector, CSR; fault_dets [n][D]: the detectors of every fault, ascending,
+ * 0xFFFF-padded (all 0xFFFF: not admitted); fault_obs [n]: its mask.  1 <= ndet <= 65535, 1 <= K <= 8, 1 <= D <= 16.  Allocates everything a
+ * search touches -- 32 max_states + 4 table_size (a power of two) + 40 stage_states bytes and the tables -- and clears the visited table:
+ * QD_EHIP when that does not fit, before any launch.  QD_ECAPACITY: max_states + stage_states > 2^32 - 2 (they share the 32-bit index). */
+int qd_search_create(int32_t ndet, int32_t n, const int64_t *row_ptr, const int32_t *row_faults, const uint16_t *fault_dets,
+                     const uint64_t *fault_obs, int32_t K, int32_t D, int32_t no_increase, int64_t max_states, int64_t table_size,
+                     int64_t stage_states, int32_t device, qd_search **out);
+void qd_search_destroy(qd_search *s);
+/* Back to the state after qd_search_create: empty pool, empty table, counters zero. */
+int qd_search_reset(qd_search *s);
+/* Level 1: `count` host records (duplicates allowed) are looked up and the new ones appended.  Two launches per stage_states records. */
+int qd_search_seed(qd_search *s, const void *records, int64_t count, void *stream);
+/* One level: expands the states the previous level appended, chunk_states at a time (chunk_states times the longest row must not exceed
+ * stage_states); two launches per chunk, no kernel waits for another workgroup.  The counters of the previous level must have been read. */
+int qd_search_level(qd_search *s, int64_t chunk_states, void *stream);
+/* Waits for the level and reads counters[QD_SEARCH_COUNTERS] = {states in the pool (counted on past max_states), staged candidates of the
+ * last chunk, states (empty, o) of the last level, QD_SEARCH_OVER_* flags, candidates looked up so far, 0, 0, 0}. */
+int qd_search_counters(qd_search *s, uint64_t *counters);
+/* The last level's states (empty, o): `max` (= counters[2]) masks and pool indices, in no fixed order. */
+int qd_search_found(qd_search *s, int64_t max, uint64_t *masks, uint32_t *indices);
+/* The faults along the parents of pool state `index` back to level 1: faults[0 .. *len - 1].  QD_EINVAL beyond max_len. */
+int qd_search_chain(qd_search *s, uint32_t index, int32_t max_len, int32_t *faults, int32_t *len);
+
 /* ---- stratified input: shots of the detector error model CONDITIONED on exactly k faults firing (subset sampling).  Stands in for
  *      rejection -- drawing `sampler.sample(shots)` (simulation.py:23-27) until a shot happens to hold k faults, which Stim could not even
  *      tell -- where P(|E| = k) is 1e-14.  No reference counterpart.

@@ -8,6 +8,13 @@ by the sliding-window decoder (quits_amd.decoder.sliding_window_bposd_circuit_me
 --corrections_out FILE (--corrections_format b8 | 01 | hits, default b8) also writes every shot's correction, one bit per fault of the model
 in the column order of detector_error_model_to_matrix (quits_amd.decoder.sliding_window_corrections / decode_dem_corrections).
 Exit status: 0 done, 1 unreadable input, 2 bad arguments, or no GPU / no library (the decoder has no CPU fallback).
+
+`python -m quits_amd search`: the directed search for light undetectable logical faults (quits_amd/search.py states it) on the device; one
+JSON object on stdout: outcome, weight, levels_completed, level_sizes, total_states, logical_masks, witnesses and the limits used.
+
+    python -m quits_amd search --circuit memory.stim --max_event_set 4 --max_fault_degree 4
+
+--mirror runs the numpy mirror of the kernels on the CPU instead (small models only); nothing else falls back to it.
 """
 from __future__ import annotations
 
@@ -46,7 +53,37 @@ def _parser():
     p.add_argument("--corrections_out", metavar="FILE",
                    help="also write every shot's correction, one bit per fault of the model (the columns of detector_error_model_to_matrix)")
     p.add_argument("--corrections_format", choices=("b8", "01", "hits"), default="b8")
+    q = sub.add_parser("search", help="search for light undetectable logical faults",
+                       description="Breadth-first search over small detection-event sets for an undetectable logical fault (quits_amd/search.py).")
+    model = q.add_mutually_exclusive_group(required=True)
+    model.add_argument("--dem", metavar="FILE", help="detector error model, Stim's .dem text")
+    model.add_argument("--circuit", metavar="FILE", help="Stim circuit text (its detector error model is extracted here)")
+    q.add_argument("--max_event_set", type=int, default=6, metavar="K", help="detectors a state may hold (1 .. 8)")
+    q.add_argument("--max_fault_degree", type=int, default=6, metavar="D", help="detectors an admitted fault may flip (1 .. 16)")
+    q.add_argument("--no_increase", action="store_true", help="do not follow faults that enlarge the detection-event set")
+    q.add_argument("--max_weight", type=int, help="stop after this many levels")
+    q.add_argument("--max_states", type=int, help="distinct states the search may hold (default: what half of the free device memory holds)")
+    q.add_argument("--keep", type=int, default=16, help="witnesses to return")
+    q.add_argument("--observables", metavar="I,J,..", help="rows of the observable matrix to search (at most 64; default: all)")
+    q.add_argument("--mirror", action="store_true", help="run the numpy mirror on the CPU instead of the device")
     return ap
+
+
+def search(args, ap) -> int:
+    from .dem import Circuit
+    from . import search as ls
+    with open(args.dem or args.circuit, "r") as fh:
+        text = fh.read()
+    model = text if args.dem else Circuit(text)
+    obs = None if args.observables is None else [int(x) for x in args.observables.split(",") if x.strip()]
+    opts = dict(max_event_set=args.max_event_set, max_fault_degree=args.max_fault_degree, no_increase=args.no_increase, max_weight=args.max_weight,
+                max_states=args.max_states, keep=args.keep, observables=obs)
+    if args.mirror:
+        res = ls.search_mirror(*ls._matrices(model), **opts)
+    else:
+        res = ls.find_undetectable_logical_errors(model, **opts)
+    print(json.dumps(res.to_json()))
+    return 0
 
 
 def predict(args, ap) -> int:
@@ -105,12 +142,12 @@ def main(argv=None) -> int:
     ap = _parser()
     args = ap.parse_args(argv)
     try:
-        return predict(args, ap)
+        return search(args, ap) if args.command == "search" else predict(args, ap)
     except RuntimeError as exc:                      # no GPU, no library, a library error: the package's own text
         print(str(exc), file=sys.stderr)
         return 2
     except (ValueError, OSError, NotImplementedError) as exc:
-        print("quits_amd predict: %s" % exc, file=sys.stderr)
+        print("quits_amd %s: %s" % (args.command, exc), file=sys.stderr)
         return 1
 
 

@@ -65,6 +65,8 @@ EXPORTS = [
     "qd_strata_create", "qd_strata_destroy", "qd_strata_info", "qd_sample_dem_strata",
     "qd_decoder_create_relay", "qd_decoder_relay_info",
     "qd_shrink_begin", "qd_shrink_step",
+    "qd_search_create", "qd_search_destroy", "qd_search_reset", "qd_search_seed", "qd_search_level", "qd_search_counters", "qd_search_found",
+    "qd_search_chain",
 ]
 
 
@@ -154,6 +156,16 @@ def load():
     if hasattr(L, "qd_shrink_begin"):               # (library version 114; an older library named by QUITS_AMD_LIB samples and decodes as before)
         L.qd_shrink_begin.argtypes = [vp, vp, vp, i64, i64, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, vp]
         L.qd_shrink_step.argtypes = [vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, vp]
+    if hasattr(L, "qd_search_create"):              # (library version 115; an older library named by QUITS_AMD_LIB samples and decodes as before)
+        L.qd_search_create.argtypes = [i32, i32, vp, vp, vp, vp, i32, i32, i32, i64, i64, i64, i32, C.POINTER(vp)]
+        L.qd_search_destroy.argtypes = [vp]
+        L.qd_search_destroy.restype = None
+        L.qd_search_reset.argtypes = [vp]
+        L.qd_search_seed.argtypes = [vp, vp, i64, vp]
+        L.qd_search_level.argtypes = [vp, i64, vp]
+        L.qd_search_counters.argtypes = [vp, vp]
+        L.qd_search_found.argtypes = [vp, i64, vp, vp]
+        L.qd_search_chain.argtypes = [vp, C.c_uint32, i32, vp, C.POINTER(i32)]
     _lib = L
     return L
 
@@ -209,6 +221,13 @@ def require_shrink(L):
     """The entry points of library version 114 (shrinking failing fault sets): a clear error from an older library."""
     if not hasattr(L, "qd_shrink_begin"):
         raise RuntimeError("quits_amd: %s is version %d; shrinking fault sets needs >= 114 -- rebuild it" % (LIB_PATH, L.qd_version()))
+    return L
+
+
+def require_search(L):
+    """The entry points of library version 115 (the search for undetectable logical faults): a clear error from an older library."""
+    if not hasattr(L, "qd_search_create"):
+        raise RuntimeError("quits_amd: %s is version %d; the logical-fault search needs >= 115 -- rebuild it" % (LIB_PATH, L.qd_version()))
     return L
 
 

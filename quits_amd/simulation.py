@@ -18,6 +18,8 @@
   get_minimal_failures                          the failing shots of such an experiment shrunk in one run: the lightest failing set (the exponent of
                                                 pL ~ p^t for this decoder) and the lightest undetectable residual (a bound on the distance)
   get_relay_minimal_failures                    the same with the sliding-window Relay-BP decoder
+  find_undetectable_logical_errors              a directed search for a light undetectable logical fault on the device, without decoder or
+                                                sampler (quits_amd/search.py has the definition; re-exported from there)
 
 `get_codecap_pL` keeps the reference's signature and its random stream (`np.random.seed(seed)` followed by one
 `np.random.binomial(1, p, n)` per trial), so a given seed produces the same noise vectors as the reference.  With a plug-in
@@ -30,6 +32,8 @@ import dataclasses
 import math
 
 import numpy as np
+
+from .search import LogicalSearchResult, find_undetectable_logical_errors, search_mirror  # noqa: F401  (re-exported)
 
 
 def get_stim_mem_result(circuit, num_trials, seed=-1):
