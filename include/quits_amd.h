@@ -359,6 +359,37 @@ int qd_fault_stats_batch(const uint32_t *d_faults, const uint32_t *d_corr, int64
                          int64_t res_stride, int32_t m, const uint64_t *d_fail_mask, int64_t B, int64_t shot0, int64_t *d_hist,
                          int64_t *d_counts, uint64_t *d_best, void *stream);
 
+/* ---- soft outputs per shot (version 116).  quits_amd/soft.py states them: a record of QD_SOFT_FIELDS int64 per shot -- [0] weight = the sum of
+ *      w_j over the faults of the committed correction, [1] faults = its size, [2] events = the detector bytes with the low bit set, [3] iters,
+ *      [4] post, [5] tail = what the windows' status words say -- and a histogram of every field from which the host reads the logical error rate
+ *      that remains when the least certain shots are discarded.  The reference returns predictions only (sliding_window.py:171-186 keeps nothing
+ *      else of a window's decode).  Rows of d_soft are soft_stride >= QD_SOFT_FIELDS int64 apart; columns past the sixth are never touched. */
+#define QD_SOFT_FIELDS 6
+#define QD_SOFT_BINS 1024
+
+/* One window's status words (qd_decode_batch) added into rows the caller zeroed, b < B: [3] += status & QD_STATUS_ITER_MASK, [4] += 1 if
+ * QD_STATUS_OSD is set, [5] += bits 20 .. 31 of the word (the post-processors' pivot count, saturated at 4095, or Relay-BP's leg).  Bits 14 .. 19
+ * enter nothing but [4] (bit 17).  Call once per window, stream-ordered; fields 0 .. 2 stay.  Stands in for summing the fields of the status
+ * tensors with torch, window by window.  No reference counterpart (ldpc reports `converge` and `iter` per call and the reference drops both). */
+int qd_soft_fold(const int32_t *d_status, int64_t B, int64_t *d_soft, int64_t soft_stride, void *stream);
+
+/* Fields 0 .. 2 of rows b < B, WRITTEN: C = row b of d_corr (qd_commit_bits: nbits bits in rows of stride_words words; bits >= nbits of the last
+ * word and the words past it are ignored), d_weights int32 [nbits] on the device (quits_amd.soft.fault_weights: rint(2^16 log((1 - p) / p)), made
+ * by the host -- the device computes no logarithm), row b of d_det m bytes with row stride det_stride >= m, of which only the low bit counts, as
+ * in qd_tally_batch.  [0] = sum of d_weights[j] over the set bits j, in 64 bits; [1] = |C|; [2] = the number of set detector bits.  One
+ * wavefront per shot, coalesced word loads, one gathered weight per set bit.  Stands in for unpacking C on the host and `C @ w`.  No reference
+ * counterpart. */
+int qd_soft_weigh(const uint32_t *d_corr, int64_t stride_words, int32_t nbits, const int32_t *d_weights, const uint8_t *d_det, int64_t det_stride,
+                  int32_t m, int64_t B, int64_t *d_soft, int64_t soft_stride, void *stream);
+
+/* d_hist (int64 [QD_SOFT_FIELDS][2][QD_SOFT_BINS] on the device, accumulated): for every field f and shot b < B the bin
+ * min(max(soft[b][f], 0) >> shifts6[f], QD_SOFT_BINS - 1) of plane [f][0] += 1, and of plane [f][1] too if bit b of d_fail_mask is set
+ * (qd_tally_batch's mask of the same batch; NULL: plane 1 is not touched).  shifts6: six shifts 0 .. 62 on the HOST.  One launch, a field per
+ * blockIdx.y with its two planes in LDS; the number of global atomics does not depend on B.  Stands in for np.bincount of the records on the
+ * host, which would need them there.  No reference counterpart. */
+int qd_soft_tally(const int64_t *d_soft, int64_t soft_stride, int64_t B, const int32_t *shifts6, const uint64_t *d_fail_mask, int64_t *d_hist,
+                  void *stream);
+
 /* ---- shrinking failing fault sets to 1-minimal ones (version 114).  quits_amd/shrink.py states the walk: a parent set S loses fault j whenever
  *      the decoder still fails on S \ {j}, j running cyclically over the members, until |S| trials in a row change nothing.  These two calls are the
  *      whole step between two decodes; the caller decodes the trial rows like sampled shots (qd_decode_batch ... qd_tally_batch) and hands back

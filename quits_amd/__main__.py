@@ -7,6 +7,8 @@ Without --checks_per_round / --window / --commit the model is decoded over its w
 by the sliding-window decoder (quits_amd.decoder.sliding_window_bposd_circuit_mem), the detectors being rounds of --checks_per_round.
 --corrections_out FILE (--corrections_format b8 | 01 | hits, default b8) also writes every shot's correction, one bit per fault of the model
 in the column order of detector_error_model_to_matrix (quits_amd.decoder.sliding_window_corrections / decode_dem_corrections).
+--soft_out FILE also writes every shot's soft record (quits_amd/soft.py: weight faults events iters post tail), six decimal integers on one
+line per shot (quits_amd.decoder.sliding_window_soft_outputs / decode_dem_soft_outputs).
 Exit status: 0 done, 1 unreadable input, 2 bad arguments, or no GPU / no library (the decoder has no CPU fallback).
 
 `python -m quits_amd search`: the directed search for light undetectable logical faults (quits_amd/search.py states it) on the device; one
@@ -53,6 +55,8 @@ def _parser():
     p.add_argument("--corrections_out", metavar="FILE",
                    help="also write every shot's correction, one bit per fault of the model (the columns of detector_error_model_to_matrix)")
     p.add_argument("--corrections_format", choices=("b8", "01", "hits"), default="b8")
+    p.add_argument("--soft_out", metavar="FILE",
+                   help="also write every shot's soft record: weight faults events iters post tail, six decimal integers per line (quits_amd/soft.py)")
     q = sub.add_parser("search", help="search for light undetectable logical faults",
                        description="Breadth-first search over small detection-event sets for an undetectable logical fault (quits_amd/search.py).")
     model = q.add_mutually_exclusive_group(required=True)
@@ -111,20 +115,33 @@ def predict(args, ap) -> int:
     opts = dict(max_iter=args.max_iter, osd_order=args.osd_order, bp_method=args.bp_method, schedule=args.schedule, osd_method=args.osd_method)
     if args.window is not None:
         import warnings
-        from .decoder import sliding_window_bposd_circuit_mem, sliding_window_corrections
+        from .decoder import sliding_window_bposd_circuit_mem, sliding_window_corrections, sliding_window_soft_outputs
         nz = args.checks_per_round
         if ndet % nz:
             raise ValueError("the model's %d detectors are not whole rounds of %d" % (ndet, nz))
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")           # (whole-history notice of the reference: not an error here)
             decode = sliding_window_corrections if args.corrections_out else sliding_window_bposd_circuit_mem
+            if args.soft_out:
+                opts["corrections"] = bool(args.corrections_out)
+                decode = sliding_window_soft_outputs
             pred = decode(det, model, np.zeros((nz, 1), np.uint8), np.zeros((nobs, 1), np.uint8), args.window, args.commit, **opts)
+    elif args.soft_out:
+        from .decoder import decode_dem_soft_outputs
+        pred = decode_dem_soft_outputs(model, det, corrections=bool(args.corrections_out), **opts)
     else:
         from .decoder import decode_dem, decode_dem_corrections
         pred = (decode_dem_corrections if args.corrections_out else decode_dem)(model, det, **opts)
-    if args.corrections_out:
+    soft = None
+    if args.soft_out:
+        pred, soft, corrections = pred if args.corrections_out else (pred + (None,))
+    elif args.corrections_out:
         pred, corrections = pred
+    if args.corrections_out:
         write_shots(args.corrections_out, corrections, args.corrections_format)
+    if soft is not None:
+        with open(args.soft_out, "w") as fh:
+            fh.writelines("%d %d %d %d %d %d\n" % tuple(int(v) for v in row) for row in soft)
     write_shots(args.out, pred.astype(np.uint8), args.out_format, num_detectors=0)
     if actual is not None:
         import torch

@@ -32,6 +32,7 @@ FAULT_HIST = 256                                                        # QD_FAU
 RELAY_FLAG_MARGINALS_DEVICE = 1                                         # QD_RELAY_FLAG_MARGINALS_DEVICE (qd_relay_params.reserved)
 SHRINK_STATE = 8                                                        # QD_SHRINK_STATE
 SHRINK_FAILS, SHRINK_MINIMAL, SHRINK_ENDED = 1, 2, 4                    # QD_SHRINK_*: the flag word of a parent's state
+SOFT_FIELDS, SOFT_BINS = 6, 1024                                        # QD_SOFT_FIELDS, QD_SOFT_BINS
 
 
 class QdParams(C.Structure):
@@ -67,6 +68,7 @@ EXPORTS = [
     "qd_shrink_begin", "qd_shrink_step",
     "qd_search_create", "qd_search_destroy", "qd_search_reset", "qd_search_seed", "qd_search_level", "qd_search_counters", "qd_search_found",
     "qd_search_chain",
+    "qd_soft_fold", "qd_soft_weigh", "qd_soft_tally",
 ]
 
 
@@ -166,6 +168,10 @@ def load():
         L.qd_search_counters.argtypes = [vp, vp]
         L.qd_search_found.argtypes = [vp, i64, vp, vp]
         L.qd_search_chain.argtypes = [vp, C.c_uint32, i32, vp, C.POINTER(i32)]
+    if hasattr(L, "qd_soft_fold"):                  # (library version 116; an older library named by QUITS_AMD_LIB returns predictions and corrections as before)
+        L.qd_soft_fold.argtypes = [vp, i64, vp, i64, vp]
+        L.qd_soft_weigh.argtypes = [vp, i64, i32, vp, vp, i64, i32, i64, vp, i64, vp]
+        L.qd_soft_tally.argtypes = [vp, i64, i64, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -228,6 +234,13 @@ def require_search(L):
     """The entry points of library version 115 (the search for undetectable logical faults): a clear error from an older library."""
     if not hasattr(L, "qd_search_create"):
         raise RuntimeError("quits_amd: %s is version %d; the logical-fault search needs >= 115 -- rebuild it" % (LIB_PATH, L.qd_version()))
+    return L
+
+
+def require_soft(L):
+    """The entry points of library version 116 (soft outputs per shot): a clear error from an older library."""
+    if not hasattr(L, "qd_soft_fold"):
+        raise RuntimeError("quits_amd: %s is version %d; soft outputs need >= 116 -- rebuild it" % (LIB_PATH, L.qd_version()))
     return L
 
 

@@ -7,6 +7,7 @@ from .bplsd import BpLsdDecoder, sliding_window_bplsd_circuit_mem, sliding_windo
 from .relaybp import RelayBpDecoder, sliding_window_relaybp_circuit_mem, sliding_window_relaybp_phenom_mem
 from .whole_history import decode_dem
 from .corrections import decode_dem_corrections, sliding_window_corrections
+from .soft_outputs import decode_dem_soft_outputs, sliding_window_soft_outputs
 
 __all__ = [
     "dict_to_csc_matrix_column_row",
@@ -24,6 +25,8 @@ __all__ = [
     "decode_dem",              # beyond the reference's names: any detector error model over its whole history (whole_history.py)
     "sliding_window_corrections",   # ... and the corrections themselves next to the predictions (corrections.py)
     "decode_dem_corrections",
+    "sliding_window_soft_outputs",  # ... and a soft record per shot: how sure the decoder was (soft_outputs.py, quits_amd/soft.py)
+    "decode_dem_soft_outputs",
     "RelayBpDecoder",          # Relay-BP (relaybp.py, quits_amd/relay.py): a decoder that needs no elimination
     "sliding_window_relaybp_phenom_mem",
     "sliding_window_relaybp_circuit_mem",

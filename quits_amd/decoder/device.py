@@ -393,6 +393,92 @@ class FaultStats:
         return self.hist.cpu().numpy(), self.counts.cpu().numpy(), lightest
 
 
+def _check_soft(soft, B):
+    torch = _torch()
+    assert soft.is_cuda and soft.dtype == torch.int64 and soft.dim() == 2 and soft.shape[0] == B and soft.shape[1] >= _lib.SOFT_FIELDS
+    assert B == 0 or soft.stride(1) == 1            # (an empty tensor's strides say nothing)
+    return soft.stride(0) if B > 1 else max(soft.stride(0), soft.shape[1])
+
+
+def soft_fold(status, soft, stream=None):
+    """soft[b, 3:6] += (iterations, post-processed, bits 20 .. 31) of one window's status words (qd_soft_fold; quits_amd/soft.py).  status: cuda
+    int32 [B], contiguous; soft: cuda int64 [B, >= 6] with unit stride inside a row, zeroed before the first window.  Asynchronous on `stream`."""
+    torch = _torch()
+    L = _lib.require_soft(_lib.load())
+    assert status.is_cuda and status.dtype == torch.int32 and status.dim() == 1 and status.is_contiguous()
+    B = status.shape[0]
+    ss = _check_soft(soft, B)
+    sp = _stream_ptr() if stream is None else C.c_void_p(stream.cuda_stream)
+    _lib.check(L.qd_soft_fold(_ptr(status), B, _ptr(soft), ss, sp))
+    return soft
+
+
+def soft_weigh(corr, nbits: int, weights, det, soft, stream=None):
+    """soft[b, 0:3] = (sum of weights over the set bits of corr[b], their number, the detector bytes of det[b] with the low bit set)
+    (qd_soft_weigh).  corr: cuda int32 [B, >= ceil(nbits / 32)]; weights: cuda int32 [nbits] (soft.fault_weights); det: cuda uint8 [B, m]; soft:
+    cuda int64 [B, >= 6]; rows with unit stride inside.  Asynchronous on `stream` (default: the current one)."""
+    torch = _torch()
+    L = _lib.require_soft(_lib.load())
+    assert corr.is_cuda and corr.dtype == torch.int32 and corr.dim() == 2 and det.is_cuda and det.dtype == torch.uint8 and det.dim() == 2
+    assert corr.shape[0] == 0 or ((corr.shape[1] <= 1 or corr.stride(1) == 1) and (det.shape[1] <= 1 or det.stride(1) == 1))
+    assert weights.is_cuda and weights.dtype == torch.int32 and weights.dim() == 1 and weights.is_contiguous() and weights.shape[0] >= nbits
+    B, m = corr.shape[0], det.shape[1]
+    assert det.shape[0] == B
+    if 32 * corr.shape[1] < nbits:
+        raise ValueError("rows of %d words cannot hold %d bits" % (corr.shape[1], nbits))
+    ss = _check_soft(soft, B)
+    if B == 0:
+        return soft
+    cs = corr.stride(0) if B > 1 else max(corr.stride(0), corr.shape[1])
+    ds = det.stride(0) if B > 1 else max(det.stride(0), m)
+    sp = _stream_ptr() if stream is None else C.c_void_p(stream.cuda_stream)
+    _lib.check(L.qd_soft_weigh(_ptr(corr), cs, int(nbits), _ptr(weights), _ptr(det), ds, m, B, _ptr(soft), ss, sp))
+    return soft
+
+
+def soft_tally(soft, shifts, fail_mask, hist, stream=None):
+    """hist[f, 0, bin] += 1 for every row of `soft` and field f, hist[f, 1, bin] += 1 for the rows whose bit is set in fail_mask
+    (qd_soft_tally; bin = soft.bin_of(value, shifts[f])).  soft: cuda int64 [B, >= 6]; shifts: six ints on the host; fail_mask: cuda int64
+    [>= ceil(B / 64)] (Tally.add's) or None: plane 1 stays; hist: cuda int64 [6, 2, 1024], contiguous."""
+    torch = _torch()
+    L = _lib.require_soft(_lib.load())
+    B = soft.shape[0]
+    ss = _check_soft(soft, B)
+    sh = np.ascontiguousarray(np.asarray(shifts, dtype=np.int32).reshape(-1))
+    if sh.shape[0] != _lib.SOFT_FIELDS or sh.min() < 0 or sh.max() > 62:
+        raise ValueError("shifts must be %d integers in 0 .. 62" % _lib.SOFT_FIELDS)
+    assert hist.is_cuda and hist.dtype == torch.int64 and hist.shape == (_lib.SOFT_FIELDS, 2, _lib.SOFT_BINS) and hist.is_contiguous()
+    mp = C.c_void_p(0)
+    if fail_mask is not None:
+        assert fail_mask.is_cuda and fail_mask.dtype == torch.int64 and fail_mask.dim() == 1 and fail_mask.is_contiguous()
+        assert fail_mask.shape[0] >= (B + 63) // 64
+        mp = _ptr(fail_mask)
+    sp = _stream_ptr() if stream is None else C.c_void_p(stream.cuda_stream)
+    _lib.check(L.qd_soft_tally(_ptr(soft), ss, B, sh.ctypes.data_as(C.c_void_p), mp, _ptr(hist), sp))
+    return hist
+
+
+class SoftTally:
+    """Histograms of the soft records of a memory experiment, on the device (qd_soft_tally): per field, the shots and the failing shots by bin
+    of width 2^shift.  `add` accumulates and returns nothing to the host; `result` does."""
+
+    def __init__(self, shifts, device=None):
+        torch = _torch()
+        self._L = _lib.require_soft(_lib.require_gpu())
+        self.shifts = np.ascontiguousarray(np.asarray(shifts, dtype=np.int32).reshape(-1))
+        if self.shifts.shape[0] != _lib.SOFT_FIELDS or self.shifts.min() < 0 or self.shifts.max() > 62:
+            raise ValueError("shifts must be %d integers in 0 .. 62" % _lib.SOFT_FIELDS)
+        self.hist = torch.zeros((_lib.SOFT_FIELDS, 2, _lib.SOFT_BINS), dtype=torch.int64, device="cuda" if device is None else device)
+
+    def add(self, soft, fail_mask=None):
+        """soft: cuda int64 [B, >= 6]; fail_mask: Tally.add's mask of the same batch, or None (plane 1 is left alone)."""
+        soft_tally(soft, self.shifts, fail_mask, self.hist)
+
+    def result(self):
+        """numpy int64 [6, 2, 1024] (synchronises)."""
+        return self.hist.cpu().numpy()
+
+
 class FaultShrinker:
     """The step of the fault-set shrinker on the device (qd_shrink_begin, qd_shrink_step; csrc/shrink.hip): quits_amd/shrink.py's walk, every
     live parent advancing one trial per round.  The decode is the caller's, so that any decoder -- or a scripted verdict -- drives it:

@@ -76,7 +76,7 @@ class TwoStreams:
         self.s_post.synchronize()
 
 
-def decode_pipelined(plan, det, stats, ready=None, correction=None):
+def decode_pipelined(plan, det, stats, ready=None, correction=None, soft=None):
     """Calls of two or more chunks: the BP stages run on one side stream, the post-processing (OSD / LSD over the shots BP
     parked, acc ^= L e, the hand-off U e) on a second one, so that a chunk's post-processing runs beside the BP of the other
     chunks of its group -- the post-processors are chains of dependent steps that leave most issue slots of a CU idle, BP fills
@@ -98,7 +98,10 @@ def decode_pipelined(plan, det, stats, ready=None, correction=None):
     queued everything, and then calls end() (profiles/r06_host_chain_ab.txt).
 
     `correction`: DeviceWindowPlan.decode's; zero-filled on the caller's stream ahead of the side streams' start, then every window's
-    committed bits are laid into it on the post stream, behind that window's acc ^= L e."""
+    committed bits are laid into it on the post stream, behind that window's acc ^= L e.
+
+    `soft`: DeviceWindowPlan.decode's (it needs `correction`); zero-filled like it, then every window's status words are folded into it on the
+    post stream behind that window's stage 2, and the chunk's correction is weighed behind its last window's committed bits."""
     import torch
     lane_decs = plan.lane_decoders()
     ts = plan.two_streams(det.device)
@@ -110,6 +113,11 @@ def decode_pipelined(plan, det, stats, ready=None, correction=None):
         from .device import commit_bits
         plan.check_correction(correction, N, det.device)
         correction.zero_()
+    if soft is not None:
+        from .device import soft_fold, soft_weigh
+        plan.check_soft(soft, correction, N, det.device)
+        weights = plan.commit_weights()
+        soft.zero_()
     if ready is None:
         ts.begin(plan, det.device, N if stats is not None else None)
     else:
@@ -143,9 +151,13 @@ def decode_pipelined(plan, det, stats, ready=None, correction=None):
                     d.post_head_start(s_bp)            # (heavy post-processing gets onto the CUs before the next BP kernel fills them; decided on the device)
                     s_post.wait_event(bp_done)
                     d.decode(chunk, w["row0"], upd, err_bits=err, status=st, stage=2, stream=s_post)
+                    if soft is not None:
+                        soft_fold(st, soft[c0:c0 + C], stream=s_post)
                     w["L"].xor_apply(err, acc, accumulate=True, stream=s_post)
                     if correction is not None:
                         commit_bits(err, w["ncommit"], correction[c0:c0 + C], w["col0"], stream=s_post)
+                        if soft is not None and k == len(plan.windows) - 1:
+                            soft_weigh(correction[c0:c0 + C], plan.nfaults, weights, chunk, soft[c0:c0 + C], stream=s_post)
                     if w["U"] is not None:
                         w["U"].xor_apply(err, ts.upd[lane][:B], accumulate=False, stream=s_post)
                     post_done[lane] = torch.cuda.Event()

@@ -87,7 +87,7 @@ class DeviceWindowPlan:
                 Uk = csr_matrix(updates[k])
                 Uk = csr_matrix((Uk.data, Uk.indices, Uk.indptr), shape=(Uk.shape[0], graph.n))
                 U = GF2Matrix(Uk)
-            self.windows.append({"dec": dec, "graph": graph, "L": GF2Matrix(Lk), "U": U, "row0": int(row0[k]), "H": checks[k], "kw": kw,
+            self.windows.append({"dec": dec, "graph": graph, "L": GF2Matrix(Lk), "U": U, "row0": int(row0[k]), "H": checks[k], "kw": kw, "priors": priors[k],
                                  "col0": self.commit_ranges[k][0], "ncommit": self.commit_ranges[k][1]})
         self.env = driver_env()
         decs = self.decoders()
@@ -114,6 +114,7 @@ class DeviceWindowPlan:
         self._lane_decs = {id(d): [d] for d in decs}     # per decoder of the plan, the decoders of the two-stream driver's lanes (lane 0: itself)
         self._two_streams = None                         # pipeline.TwoStreams and pipeline.HostStaging, made at first use
         self._staging = None
+        self._commit_weights = None                      # commit_weights(): the committed columns' log-likelihood weights, on the device
         self.device = _current_device()      # graphs, decoders and workspaces were created on this device
         self._lock = threading.RLock()       # one decode_host at a time per plan (staging buffers, side streams and workspaces are per plan);
                                              # re-entrant, and the plan cache takes it (non-blocking) before releasing an idle plan's workspaces
@@ -164,13 +165,42 @@ class DeviceWindowPlan:
         if correction.device != device:
             raise ValueError("correction lives on %s, the samples on %s" % (correction.device, device))
 
-    def decode(self, det, stats=None, correction=None):
+    def commit_priors(self):
+        """float64 [nfaults] on the host: the priors of the committed columns, laid end to end like the correction."""
+        pri = [np.broadcast_to(np.asarray(w["priors"], dtype=np.float64), (w["graph"].n,))[:w["ncommit"]] for w in self.windows]
+        return np.concatenate(pri) if pri else np.zeros((0,))
+
+    def commit_weights(self):
+        """cuda int32 [nfaults]: quits_amd.soft.fault_weights of the committed columns' priors, laid end to end like the correction -- window k
+        contributes priors_k[:ncommit_k].  Made once per plan and kept on its device."""
+        if self._commit_weights is None:
+            import torch
+            from ..soft import fault_weights
+            host = fault_weights(self.commit_priors())
+            dev = torch.device("cuda", self.device) if self.device >= 0 else torch.device("cuda")
+            self._commit_weights = torch.from_numpy(np.ascontiguousarray(host)).to(dev)
+        return self._commit_weights
+
+    def check_soft(self, soft, correction, N, device):
+        import torch
+        if correction is None:
+            raise ValueError("soft records are computed from the committed correction: pass `correction` along with `soft`")
+        if not (isinstance(soft, torch.Tensor) and soft.is_cuda and soft.dtype == torch.int64 and soft.dim() == 2 and soft.shape[0] == N
+                and soft.shape[1] == 6 and soft.stride(1) == 1):
+            raise ValueError("soft must be a cuda int64 [%d, 6] tensor with unit stride inside a row" % N)
+        if soft.device != device:
+            raise ValueError("soft lives on %s, the samples on %s" % (soft.device, device))
+
+    def decode(self, det, stats=None, correction=None, soft=None):
         """det: cuda uint8 [N, ndet]  ->  cuda uint8 [N, nobs] logical predictions.
 
         Chunks of `self.chunk` shots, windows inner.  `stats`, if given, receives (window index, status tensor) pairs.
         `correction`, if given, is a cuda int32 [N, >= ceil(nfaults / 32)] tensor that the call zero-fills and then fills with the space-time
         correction: bit j & 31 of word j >> 5 of row b = fault j of the whole model is in shot b's correction -- every window's committed
         columns at `commit_ranges[k]` (qd_commit_bits next to the window's acc ^= L_k e, on its stream).  Without it no launch is added.
+        `soft`, if given (it needs `correction`), is a cuda int64 [N, 6] tensor that the call zero-fills and then fills with the shots' soft
+        records (quits_amd/soft.py): qd_soft_fold behind every window's decode, qd_soft_weigh behind a chunk's last qd_commit_bits, with
+        `commit_weights()`.  Without it no launch is added either.
         A call of two or more chunks runs a chunk's post-processing on a second stream beside the BP of the other chunks of its
         group (pipeline.decode_pipelined: headline 1.21 -> 1.30 M shots/s, BP-LSD order 1 690 k -> 866 k, p = 6e-3 320 k -> 355 k,
         W = 3 / F = 1 windows 511 k -> 539 k, identical outputs; profiles/r03x_pipelined_driver_ab.txt,
@@ -180,13 +210,22 @@ class DeviceWindowPlan:
         N = det.shape[0]
         if self.pipeline and N >= 2 * self.chunk:
             if correction is None:
+                if soft is not None:
+                    self.check_soft(soft, correction, N, det.device)
                 return pipeline.decode_pipelined(self, det, stats)
-            return pipeline.decode_pipelined(self, det, stats, correction=correction)
+            if soft is None:
+                return pipeline.decode_pipelined(self, det, stats, correction=correction)
+            return pipeline.decode_pipelined(self, det, stats, correction=correction, soft=soft)
         pred = torch.zeros((N, self.nobs), dtype=torch.uint8, device=det.device)
         if correction is not None:
             from .device import commit_bits
             self.check_correction(correction, N, det.device)
             correction.zero_()
+        if soft is not None:
+            from .device import soft_fold, soft_weigh
+            self.check_soft(soft, correction, N, det.device)
+            weights = self.commit_weights()
+            soft.zero_()
         for c0 in range(0, N, self.chunk):
             chunk = det[c0:c0 + self.chunk]
             acc = pred[c0:c0 + self.chunk]
@@ -196,6 +235,10 @@ class DeviceWindowPlan:
                 w["L"].xor_apply(err_bits, acc, accumulate=True)
                 if correction is not None:
                     commit_bits(err_bits, w["ncommit"], correction[c0:c0 + self.chunk], w["col0"])
+                if soft is not None:
+                    soft_fold(status, soft[c0:c0 + self.chunk])
+                    if k == len(self.windows) - 1:
+                        soft_weigh(correction[c0:c0 + self.chunk], self.nfaults, weights, chunk, soft[c0:c0 + self.chunk])
                 if w["U"] is not None:
                     upd = torch.empty((chunk.shape[0], self.nz), dtype=torch.uint8, device=det.device)
                     w["U"].xor_apply(err_bits, upd, accumulate=False)

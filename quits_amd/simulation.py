@@ -8,6 +8,8 @@
                                                 without a host array per shot
   get_relay_mem_pL                              the same experiment with the sliding-window Relay-BP decoder
   replay_shots                                  the samples of given shot indices again (both samplers are counter-based)
+  get_postselected_pL                           the same experiment with a soft record per shot kept on the device (quits_amd/soft.py): the logical
+                                                error rate that remains when the least certain fraction of the shots is discarded
   get_fault_spectrum                            the same experiment on DEM-sampled shots with the faults in view: shots and failures by the
                                                 number of sampled faults, the residual E xor C of the failing shots, the lightest one seen
   replay_faults                                 which faults fired in given shots of the DEM sampler
@@ -348,6 +350,135 @@ def replay_shots(circuit, shot_indices, seed, sampler='circuit'):
     _lib.require_experiment(_lib.require_gpu())
     det, obs = _make_sampler(_as_circuit(circuit), sampler).sample_shots(shot_indices, int(seed))
     return det.cpu().numpy().astype(bool), obs.cpu().numpy().astype(bool)
+
+
+# ---- the same experiment with the decoder's confidence in view ----------------------------------------------------------------------------
+@dataclasses.dataclass
+class PostSelectionResult:
+    """What `get_postselected_pL` returns.  shots, errors, pL, sigma as in MemExperimentResult.  hist: int64 [6, 2, 1024], per field of
+    quits_amd.soft.FIELDS the shots (plane 0) and the failing shots (plane 1) by bin of width 2^shifts[field] (soft.bin_of: negative values in
+    bin 0, everything past the last bin in it).  `curve` and `at_rejection` read the acceptance curve of a field off it: the shots are
+    accepted in ascending order of the field, a whole bin at a time."""
+    shots: int
+    errors: int
+    pL: float
+    sigma: float
+    shifts: np.ndarray
+    hist: np.ndarray
+    seed: int = 0
+    sampler: str = "circuit"
+    batch: int = 0
+    seconds: float = 0.0
+
+    @classmethod
+    def from_counts(cls, counts, shifts, hist, seed=0, sampler="circuit", batch=0, seconds=0.0):
+        """From decoder.device.Tally's counters and decoder.device.SoftTally's histogram; every plane must add up to the counters."""
+        from .soft import BINS, FIELDS
+        c = np.asarray(counts, dtype=np.int64)
+        h = np.asarray(hist, dtype=np.int64)
+        shots, errors = int(c[0]), int(c[1])
+        if h.shape != (len(FIELDS), 2, BINS):
+            raise ValueError("the histogram must be [%d, 2, %d]" % (len(FIELDS), BINS))
+        if not (np.all(h[:, 0].sum(axis=1) == shots) and np.all(h[:, 1].sum(axis=1) == errors)):
+            raise ValueError("soft histograms and counters disagree: %s / %s shots in the planes, counters %d / %d"
+                             % (h[:, 0].sum(axis=1).tolist(), h[:, 1].sum(axis=1).tolist(), shots, errors))
+        pL = errors / shots if shots else float("nan")
+        sigma = math.sqrt(pL * (1.0 - pL) / shots) if shots else float("nan")
+        return cls(shots, errors, pL, sigma, np.asarray(shifts, dtype=np.int32).copy(), h.copy(), int(seed), str(sampler), int(batch), float(seconds))
+
+    def _field(self, field):
+        from .soft import FIELDS
+        if isinstance(field, str):
+            if field not in FIELDS:
+                raise ValueError("field must be one of %s" % (FIELDS,))
+            return FIELDS.index(field)
+        return int(field)
+
+    def curve(self, field):
+        """(edge, kept, errors, pL, sigma), arrays of 1024 entries: accepting the shots whose `field` is at most edge[t] = (t + 1) * 2^shift - 1
+        keeps kept[t] shots of which errors[t] fail (soft.selection_curve).  The last bin also holds every larger value, so the last entry is
+        (shots, errors) whatever edge says."""
+        from .soft import BINS, selection_curve
+        i = self._field(field)
+        edge = (np.arange(1, BINS + 1, dtype=np.int64) << np.int64(self.shifts[i])) - 1
+        return (edge,) + selection_curve(self.hist[i])
+
+    def at_rejection(self, field, fraction):
+        """The loosest threshold of `field` that discards at least `fraction` of the shots: a dict with threshold (accept value <= threshold; None
+        if even the first bin keeps too many, so that nothing is kept), kept, errors, pL, sigma and the fraction actually rejected -- whole bins
+        are kept or dropped, so that is `fraction` or more."""
+        if not 0.0 <= float(fraction) <= 1.0:
+            raise ValueError("fraction must lie in [0, 1]")
+        edge, kept, errors, pL, sigma = self.curve(field)
+        ok = np.flatnonzero((self.shots - kept) >= float(fraction) * self.shots)
+        if ok.size == 0:
+            return {"threshold": None, "kept": 0, "errors": 0, "pL": float("nan"), "sigma": float("nan"), "rejected": 1.0 if self.shots else float("nan")}
+        t = int(ok[-1])
+        return {"threshold": int(edge[t]), "kept": int(kept[t]), "errors": int(errors[t]), "pL": float(pL[t]), "sigma": float(sigma[t]),
+                "rejected": (self.shots - int(kept[t])) / self.shots if self.shots else float("nan")}
+
+
+def get_postselected_pL(circuit, hz, lz, W, F, num_trials, max_iter=2, osd_order=0, bp_method='product_sum', schedule='serial',
+                        osd_method=None, *, relay=None, seed=0, sampler='circuit', batch=None, shifts=None):
+    """`get_circuit_mem_pL` with the decoder's confidence in view: every batch (experiment_batches') is sampled, decoded with its space-time
+    correction and a soft record per shot (plan.decode(det, None, correction, soft); quits_amd/soft.py), tallied (Tally, whose fail mask
+    says which shots failed) and binned (SoftTally: qd_soft_tally).  Nothing per shot reaches the host; it reads the counters and the
+    [6, 2, 1024] histogram once at the end.  Same shots, same decoder, same cached plan as `get_circuit_mem_pL`: `shots`, `errors`, `pL`
+    and `sigma` are its numbers.
+
+    The decoder keywords are get_circuit_mem_pL's (osd_method None = its 'osd_cs'); relay: a quits_amd.relay.RelayConfig selects the
+    sliding-window Relay-BP decoder as in get_relay_mem_pL (osd_method None = 'osd_off', and `osd_order` its post-processor's).
+    sampler, seed, batch: as there.  shifts: six bin-width exponents (soft.FIELDS' order); default soft.default_shifts of the plan's committed
+    weights and priors, the detector count, the window count and max_iter (Relay-BP: the configuration's total_iter).
+
+    Returns a PostSelectionResult: `result.curve('weight')`, `result.at_rejection('iters', 0.05)`."""
+    import time
+    import warnings
+    from . import _lib
+    from . import soft as _soft
+    from .decoder.base import window_count
+    from .decoder.plan import cached_circuit_plan
+    if F == 0:
+        raise ValueError("Input parameter F cannot be zero.")
+    if sampler not in ("circuit", "dem"):
+        raise ValueError("sampler must be 'circuit' or 'dem'")
+    _lib.require_soft(_lib.require_faults(_lib.require_experiment(_lib.require_gpu())))
+    import torch
+    from .decoder.device import SoftTally, Tally
+    decoder, opts = _decoder_choice(relay, max_iter, osd_order, bp_method, schedule, osd_method)
+    circ = _as_circuit(circuit)
+    smp = _make_sampler(circ, sampler)
+    nz = hz.shape[0]
+    num_rounds = smp.m // nz - 2
+    if window_count(num_rounds, W, F)[2]:
+        warnings.warn("Window size larger than the syndrome extraction rounds: Doing whole history correction")
+    plan = cached_circuit_plan(circ, hz, W, F, num_rounds, decoder, decoder, opts, opts)
+    k = plan.nobs
+    if smp.nobs != k or np.asarray(lz.shape)[0] != k:
+        raise ValueError("the circuit has %d observables, lz %d rows, the window plan commits %d" % (smp.nobs, lz.shape[0], k))
+    if batch is None:
+        batch = max(2, int(plan.lanes) if plan.pipeline else 2) * int(plan.chunk)
+    batches = experiment_batches(num_trials, batch)
+    if shifts is None:
+        iters = relay.total_iter if relay is not None else (int(max_iter) if int(max_iter) > 0 else max(w["graph"].n for w in plan.windows))
+        shifts = _soft.default_shifts(plan.commit_weights().cpu().numpy(), plan.commit_priors(), smp.m, len(plan.windows), iters)
+    words = (plan.nfaults + 31) // 32
+    with plan.in_use():
+        tally, stally = Tally(k), SoftTally(shifts)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for shot0, n in batches:
+            det, obs = smp.sample(n, seed, shot0)
+            corr = torch.empty((n, words), dtype=torch.int32, device="cuda")
+            rec = torch.empty((n, len(_soft.FIELDS)), dtype=torch.int64, device="cuda")
+            pred = plan.decode(det, None, corr, rec)
+            mask = torch.empty(((n + 63) // 64,), dtype=torch.int64, device="cuda")
+            tally.add(pred, obs, None, mask)
+            stally.add(rec, mask)
+        torch.cuda.synchronize()
+        seconds = time.perf_counter() - t0
+        counts, hist = tally.counts(), stally.result()
+    return PostSelectionResult.from_counts(counts, stally.shifts, hist, seed, sampler, _batch_step(batch), seconds)
 
 
 # ---- the same experiment with the faults in view --------------------------------------------------------------------------------------
