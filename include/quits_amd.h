@@ -459,6 +459,34 @@ int qd_search_found(qd_search *s, int64_t max, uint64_t *masks, uint32_t *indice
 /* The faults along the parents of pool state `index` back to level 1: faults[0 .. *len - 1].  QD_EINVAL beyond max_len. */
 int qd_search_chain(qd_search *s, uint32_t index, int32_t max_len, int32_t *faults, int32_t *len);
 
+/* ---- the random information-set estimate of the distance (version 117).  quits_amd/distance.py states it: trial t puts the faults in the
+ *      order of (key, j), key = word (j & 3) of Philox4x32-10(key = (seed lo, seed hi), counter = (t lo, t hi, j >> 2, 4)), and eliminates along
+ *      it; every column that depends on the columns before it closes a kernel vector of weight 1 + the pivots it is a sum of, whose mask is
+ *      the XOR of fault_obs over it.  rec[t] = min over the vectors with a non-zero mask of weight * 2^32 + j (2^64 - 1: none): a function of
+ *      (model, seed, t) alone.  No reference counterpart (its compute_code_distance enumerates the kernel); Stim has none either.
+ *      distance.hip describes the kernel: one workgroup per trial, the row transform by detector in LDS. */
+typedef struct qd_isd qd_isd;
+#define QD_ISD_HIST 64
+/* col_ptr [n + 1], col_rows [nnz]: the detectors of every fault (CSC of H mod 2, every entry checked against ndet); fault_obs [n]: its mask.
+ * 1 <= ndet <= 65535, 1 <= n.  Allocates everything a run touches (the column orders of the trials in flight, the histogram).
+ * QD_ECAPACITY, with both byte counts in the message: the transform -- 4 (ndet + columns per block) (ceil(ndet / 32) + 2, made odd) bytes and
+ * a header -- or the order while it is sorted (8 bytes a fault, rounded up to a power of two: at most 16384 faults) exceeds the 160 KiB of
+ * LDS of a CU.  QD_EHIP: a failed allocation, before any launch. */
+int qd_isd_create(int32_t ndet, int32_t n, const int64_t *col_ptr, const int32_t *col_rows, const uint64_t *fault_obs, int32_t device,
+                  qd_isd **out);
+void qd_isd_destroy(qd_isd *s);
+/* info[8] = {LDS bytes of a workgroup, threads of a workgroup, workspace bytes (column orders), trials in flight per launch, pivots of the
+ * last trial run = the rank of H (-1 before the first run), columns per block, lanes per column, words sorted}.  Waits for the last run. */
+int qd_isd_info(qd_isd *s, int64_t *info);
+/* Trials trial0 .. trial0 + ntrials - 1 of `seed`: d_records[i] (device memory) = rec[trial0 + i]; the candidates with a non-zero mask are
+ * added to the device histogram by weight (bin 63: every weight >= 63).  One launch of min(ntrials, trials in flight) workgroups, each
+ * looping over its trials; asynchronous on `stream`. */
+int qd_isd_run(qd_isd *s, uint64_t seed, int64_t trial0, int64_t ntrials, uint64_t *d_records, void *stream);
+/* Waits for the last run and copies the histogram to hist[QD_ISD_HIST] (host memory). */
+int qd_isd_hist(qd_isd *s, uint64_t *hist);
+/* Waits for the last run and clears the histogram. */
+int qd_isd_reset(qd_isd *s);
+
 /* ---- stratified input: shots of the detector error model CONDITIONED on exactly k faults firing (subset sampling).  Stands in for
  *      rejection -- drawing `sampler.sample(shots)` (simulation.py:23-27) until a shot happens to hold k faults, which Stim could not even
  *      tell -- where P(|E| = k) is 1e-14.  No reference counterpart.

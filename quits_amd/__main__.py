@@ -17,6 +17,13 @@ JSON object on stdout: outcome, weight, levels_completed, level_sizes, total_sta
     python -m quits_amd search --circuit memory.stim --max_event_set 4 --max_fault_degree 4
 
 --mirror runs the numpy mirror of the kernels on the CPU instead (small models only); nothing else falls back to it.
+
+`python -m quits_amd distance`: the random information-set estimate of the distance (quits_amd/distance.py states it) on the device; one
+JSON object on stdout: weight (an upper bound), witnesses, masks, trials, first_trial, hist, rank, seed, observables, seconds.
+
+    python -m quits_amd distance --circuit memory.stim --trials 65536 --target 6
+
+--mirror as above.
 """
 from __future__ import annotations
 
@@ -70,7 +77,36 @@ def _parser():
     q.add_argument("--keep", type=int, default=16, help="witnesses to return")
     q.add_argument("--observables", metavar="I,J,..", help="rows of the observable matrix to search (at most 64; default: all)")
     q.add_argument("--mirror", action="store_true", help="run the numpy mirror on the CPU instead of the device")
+    d = sub.add_parser("distance", help="estimate the distance from random information sets",
+                       description="Random column orders of the check matrix, one elimination each; the lightest kernel vector that flips an "
+                                   "observable is an upper bound on the distance (quits_amd/distance.py).")
+    model = d.add_mutually_exclusive_group(required=True)
+    model.add_argument("--dem", metavar="FILE", help="detector error model, Stim's .dem text")
+    model.add_argument("--circuit", metavar="FILE", help="Stim circuit text (its detector error model is extracted here)")
+    d.add_argument("--trials", type=int, default=1 << 16, help="trials to run (default 65536)")
+    d.add_argument("--seed", type=int, default=0)
+    d.add_argument("--target", type=int, metavar="W", help="stop after the first batch that reaches this weight")
+    d.add_argument("--max_seconds", type=float, metavar="T", help="stop after the first batch that ends past this time")
+    d.add_argument("--keep", type=int, default=16, help="witnesses to return")
+    d.add_argument("--observables", metavar="I,J,..", help="rows of the observable matrix to watch (at most 64; default: all)")
+    d.add_argument("--mirror", action="store_true", help="run the numpy mirror on the CPU instead of the device")
     return ap
+
+
+def distance(args, ap) -> int:
+    from .dem import Circuit
+    from . import distance as qd
+    with open(args.dem or args.circuit, "r") as fh:
+        text = fh.read()
+    model = text if args.dem else Circuit(text)
+    obs = None if args.observables is None else [int(x) for x in args.observables.split(",") if x.strip()]
+    if args.mirror:
+        res = qd.estimate_distance_mirror(model, trials=args.trials, seed=args.seed, keep=args.keep, observables=obs)
+    else:
+        res = qd.estimate_distance(model, trials=args.trials, seed=args.seed, target=args.target, max_seconds=args.max_seconds, keep=args.keep,
+                                   observables=obs)
+    print(json.dumps(res.to_json()))
+    return 0
 
 
 def search(args, ap) -> int:
@@ -159,7 +195,7 @@ def main(argv=None) -> int:
     ap = _parser()
     args = ap.parse_args(argv)
     try:
-        return search(args, ap) if args.command == "search" else predict(args, ap)
+        return {"search": search, "distance": distance}.get(args.command, predict)(args, ap)
     except RuntimeError as exc:                      # no GPU, no library, a library error: the package's own text
         print(str(exc), file=sys.stderr)
         return 2

@@ -33,6 +33,7 @@ RELAY_FLAG_MARGINALS_DEVICE = 1                                         # QD_REL
 SHRINK_STATE = 8                                                        # QD_SHRINK_STATE
 SHRINK_FAILS, SHRINK_MINIMAL, SHRINK_ENDED = 1, 2, 4                    # QD_SHRINK_*: the flag word of a parent's state
 SOFT_FIELDS, SOFT_BINS = 6, 1024                                        # QD_SOFT_FIELDS, QD_SOFT_BINS
+QD_ECAPACITY = -4                                                       # a model beyond a kernel's limits
 
 
 class QdParams(C.Structure):
@@ -69,6 +70,7 @@ EXPORTS = [
     "qd_search_create", "qd_search_destroy", "qd_search_reset", "qd_search_seed", "qd_search_level", "qd_search_counters", "qd_search_found",
     "qd_search_chain",
     "qd_soft_fold", "qd_soft_weigh", "qd_soft_tally",
+    "qd_isd_create", "qd_isd_destroy", "qd_isd_info", "qd_isd_run", "qd_isd_hist", "qd_isd_reset",
 ]
 
 
@@ -172,6 +174,14 @@ def load():
         L.qd_soft_fold.argtypes = [vp, i64, vp, i64, vp]
         L.qd_soft_weigh.argtypes = [vp, i64, i32, vp, vp, i64, i32, i64, vp, i64, vp]
         L.qd_soft_tally.argtypes = [vp, i64, i64, vp, vp, vp, vp]
+    if hasattr(L, "qd_isd_create"):                 # (library version 117; an older library named by QUITS_AMD_LIB samples, decodes and searches as before)
+        L.qd_isd_create.argtypes = [i32, i32, vp, vp, vp, i32, C.POINTER(vp)]
+        L.qd_isd_destroy.argtypes = [vp]
+        L.qd_isd_destroy.restype = None
+        L.qd_isd_info.argtypes = [vp, vp]
+        L.qd_isd_run.argtypes = [vp, u64, i64, i64, vp, vp]
+        L.qd_isd_hist.argtypes = [vp, vp]
+        L.qd_isd_reset.argtypes = [vp]
     _lib = L
     return L
 
@@ -241,6 +251,13 @@ def require_soft(L):
     """The entry points of library version 116 (soft outputs per shot): a clear error from an older library."""
     if not hasattr(L, "qd_soft_fold"):
         raise RuntimeError("quits_amd: %s is version %d; soft outputs need >= 116 -- rebuild it" % (LIB_PATH, L.qd_version()))
+    return L
+
+
+def require_distance(L):
+    """The entry points of library version 117 (the random information-set estimate of the distance): a clear error from an older library."""
+    if not hasattr(L, "qd_isd_create"):
+        raise RuntimeError("quits_amd: %s is version %d; the distance estimate needs >= 117 -- rebuild it" % (LIB_PATH, L.qd_version()))
     return L
 
 

@@ -22,6 +22,8 @@
   get_relay_minimal_failures                    the same with the sliding-window Relay-BP decoder
   find_undetectable_logical_errors              a directed search for a light undetectable logical fault on the device, without decoder or
                                                 sampler (quits_amd/search.py has the definition; re-exported from there)
+  estimate_distance, estimate_code_distance     the random information-set estimate of the circuit-level or code distance on the device: an upper
+                                                bound with its witnesses (quits_amd/distance.py has the definition; re-exported from there)
 
 `get_codecap_pL` keeps the reference's signature and its random stream (`np.random.seed(seed)` followed by one
 `np.random.binomial(1, p, n)` per trial), so a given seed produces the same noise vectors as the reference.  With a plug-in
@@ -36,6 +38,7 @@ import math
 import numpy as np
 
 from .search import LogicalSearchResult, find_undetectable_logical_errors, search_mirror  # noqa: F401  (re-exported)
+from .distance import DistanceResult, distance_mirror, estimate_code_distance, estimate_distance  # noqa: F401  (re-exported)
 
 
 def get_stim_mem_result(circuit, num_trials, seed=-1):
