@@ -487,6 +487,29 @@ int qd_isd_hist(qd_isd *s, uint64_t *hist);
 /* Waits for the last run and clears the histogram. */
 int qd_isd_reset(qd_isd *s);
 
+/* ---- fitting a model's priors to detector samples (version 118).  quits_amd/calibrate.py states the fit; the device does the one part that
+ *      touches every shot: for every column of H with detectors d_0 < .. < d_{s-1} and every mask t = 1 .. 2^s - 1 (bit i = d_i), the number
+ *      of shots in which the XOR of the selected detectors is 1.  No reference counterpart (its priors come from the circuit's noise arguments);
+ *      the p_ij estimators of the repetition- and surface-code experiments are the pairwise special case.  calibrate.hip describes the kernels. */
+typedef struct qd_calib qd_calib;
+#define QD_CALIB_MAX_WEIGHT 10
+/* One byte per detector (rows b < B of in_stride >= ndet bytes, the low bit counts, as qd_pack_b8 reads them) to one bit plane per detector:
+ * bit b & 63 of word d * plane_stride + (b >> 6) of d_planes is detector d of shot b; bits at and beyond B of the last word are 0; words at
+ * and beyond ceil(B / 64) of a plane are not touched.  plane_stride >= ceil(B / 64), B <= 2^31.  One wavefront per 64 shots; asynchronous. */
+int qd_bit_planes(const uint8_t *d_in, int64_t in_stride, int32_t ndet, int64_t B, uint64_t *d_planes, int64_t plane_stride, void *stream);
+/* The column table (HOST arrays): col_ptr [ncols + 1] from 0, col_det the detectors of every column, ascending.  Checked here, before any
+ * launch: QD_EINVAL for a null pointer, a negative size, an empty column, detectors that do not ascend or a detector index >= ndet;
+ * QD_ECAPACITY for a column of more than QD_CALIB_MAX_WEIGHT detectors (the message names the column and its weight).  The counters of
+ * column j are count_ptr[j] .. count_ptr[j + 1] - 1, count_ptr[j + 1] - count_ptr[j] = 2^s_j - 1, mask t at count_ptr[j] + t - 1. */
+int qd_calib_create(int32_t ndet, int32_t ncols, const int64_t *col_ptr, const int32_t *col_det, int32_t device, qd_calib **out);
+void qd_calib_destroy(qd_calib *s);
+/* info[4] = {counters in a row (the sum of 2^s_j - 1), wavefront tasks of a launch, highest column weight, columns} */
+int qd_calib_info(const qd_calib *s, int64_t *info);
+/* d_counts (int64 [counters in a row] on the device) += the counts of the module text over the shots of the first nwords words of the planes
+ * (qd_bit_planes' layout; a partly filled last word must have zero pad bits).  Every counter is owned by one wavefront: no atomics, and the
+ * sums depend on neither the grid nor how the shots were batched.  nwords <= 2^25; nwords = 0 changes nothing.  Asynchronous. */
+int qd_parity_counts(const qd_calib *s, const uint64_t *d_planes, int64_t plane_stride, int64_t nwords, int64_t *d_counts, void *stream);
+
 /* ---- stratified input: shots of the detector error model CONDITIONED on exactly k faults firing (subset sampling).  Stands in for
  *      rejection -- drawing `sampler.sample(shots)` (simulation.py:23-27) until a shot happens to hold k faults, which Stim could not even
  *      tell -- where P(|E| = k) is 1e-14.  No reference counterpart.

@@ -24,6 +24,15 @@ JSON object on stdout: weight (an upper bound), witnesses, masks, trials, first_
     python -m quits_amd distance --circuit memory.stim --trials 65536 --target 6
 
 --mirror as above.
+
+`python -m quits_amd calibrate`: fit the priors of a model's hyperedges to a file of detector samples (quits_amd/calibrate.py states the fit);
+the counting runs on the device.  --out receives the model with the fitted priors as .dem text, which every command here takes as --dem;
+--stderr_out one line per column: prior, jackknife standard error, flag (ok, clipped or unidentified).  One JSON object on stdout: shots,
+columns, clipped, unidentified, median_rel_stderr and max_rel_stderr (stderr / prior), seconds.
+
+    python -m quits_amd calibrate --circuit memory.stim --in shots.b8 --in_format b8 --out fitted.dem
+
+--mirror as above.  Exit statuses as `predict`.
 """
 from __future__ import annotations
 
@@ -90,7 +99,49 @@ def _parser():
     d.add_argument("--keep", type=int, default=16, help="witnesses to return")
     d.add_argument("--observables", metavar="I,J,..", help="rows of the observable matrix to watch (at most 64; default: all)")
     d.add_argument("--mirror", action="store_true", help="run the numpy mirror on the CPU instead of the device")
+    c = sub.add_parser("calibrate", help="fit a model's priors to detector samples",
+                       description="Fit the prior of every hyperedge of a detector error model to detector samples, with jackknife standard "
+                                   "errors (quits_amd/calibrate.py).")
+    model = c.add_mutually_exclusive_group(required=True)
+    model.add_argument("--dem", metavar="FILE", help="detector error model, Stim's .dem text")
+    model.add_argument("--circuit", metavar="FILE", help="Stim circuit text (its detector error model is extracted here)")
+    c.add_argument("--in", dest="inp", metavar="FILE", required=True, help="detector samples")
+    c.add_argument("--in_format", choices=FORMATS, required=True)
+    c.add_argument("--in_includes_appended_observables", action="store_true",
+                   help="every shot of --in holds the observables after the detectors (they are not read)")
+    c.add_argument("--out", metavar="FILE", required=True, help="the model with the fitted priors, .dem text")
+    c.add_argument("--blocks", type=int, default=16, help="jackknife blocks (default 16)")
+    c.add_argument("--stderr_out", metavar="FILE", help="one line per column: prior stderr flag")
+    c.add_argument("--mirror", action="store_true", help="count with the numpy mirror on the CPU instead of the device")
     return ap
+
+
+def calibrate(args, ap) -> int:
+    from .dem import Circuit, as_dem
+    from . import calibrate as qc
+    from .samples import read_shots
+    if args.blocks < 1:
+        ap.error("--blocks must be positive")
+    with open(args.dem or args.circuit, "r") as fh:
+        text = fh.read()
+    model = text if args.dem else Circuit(text)
+    dem = as_dem(model)
+    ndet, nobs = dem.num_detectors, dem.num_observables
+    rec = read_shots(args.inp, args.in_format, ndet, nobs if args.in_includes_appended_observables else 0)
+    det = rec.field(0, ndet)
+    if args.mirror:
+        res = qc.estimate_priors_mirror(model, det, blocks=args.blocks)
+    else:
+        res = qc.estimate_priors(model, det, blocks=args.blocks)
+    with open(args.out, "w") as fh:
+        fh.write(res.dem_text())
+    if args.stderr_out:
+        flag = np.zeros(len(res.priors), np.int64)
+        flag[res.clipped], flag[res.unidentified] = 1, 2
+        with open(args.stderr_out, "w") as fh:
+            fh.writelines("%.17g %.17g %s\n" % (p, e, ("ok", "clipped", "unidentified")[f]) for p, e, f in zip(res.priors, res.stderr, flag))
+    print(json.dumps(res.to_json()))
+    return 0
 
 
 def distance(args, ap) -> int:
@@ -195,7 +246,7 @@ def main(argv=None) -> int:
     ap = _parser()
     args = ap.parse_args(argv)
     try:
-        return {"search": search, "distance": distance}.get(args.command, predict)(args, ap)
+        return {"search": search, "distance": distance, "calibrate": calibrate}.get(args.command, predict)(args, ap)
     except RuntimeError as exc:                      # no GPU, no library, a library error: the package's own text
         print(str(exc), file=sys.stderr)
         return 2

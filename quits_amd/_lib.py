@@ -71,6 +71,7 @@ EXPORTS = [
     "qd_search_chain",
     "qd_soft_fold", "qd_soft_weigh", "qd_soft_tally",
     "qd_isd_create", "qd_isd_destroy", "qd_isd_info", "qd_isd_run", "qd_isd_hist", "qd_isd_reset",
+    "qd_bit_planes", "qd_calib_create", "qd_calib_destroy", "qd_calib_info", "qd_parity_counts",
 ]
 
 
@@ -182,6 +183,13 @@ def load():
         L.qd_isd_run.argtypes = [vp, u64, i64, i64, vp, vp]
         L.qd_isd_hist.argtypes = [vp, vp]
         L.qd_isd_reset.argtypes = [vp]
+    if hasattr(L, "qd_calib_create"):               # (library version 118; an older library named by QUITS_AMD_LIB keeps the model's own priors as before)
+        L.qd_bit_planes.argtypes = [vp, i64, i32, i64, vp, i64, vp]
+        L.qd_calib_create.argtypes = [i32, i32, vp, vp, i32, C.POINTER(vp)]
+        L.qd_calib_destroy.argtypes = [vp]
+        L.qd_calib_destroy.restype = None
+        L.qd_calib_info.argtypes = [vp, vp]
+        L.qd_parity_counts.argtypes = [vp, vp, i64, i64, vp, vp]
     _lib = L
     return L
 
@@ -258,6 +266,13 @@ def require_distance(L):
     """The entry points of library version 117 (the random information-set estimate of the distance): a clear error from an older library."""
     if not hasattr(L, "qd_isd_create"):
         raise RuntimeError("quits_amd: %s is version %d; the distance estimate needs >= 117 -- rebuild it" % (LIB_PATH, L.qd_version()))
+    return L
+
+
+def require_calibrate(L):
+    """The entry points of library version 118 (fitting priors to detector samples): a clear error from an older library."""
+    if not hasattr(L, "qd_calib_create"):
+        raise RuntimeError("quits_amd: %s is version %d; fitting priors needs >= 118 -- rebuild it" % (LIB_PATH, L.qd_version()))
     return L
 
 

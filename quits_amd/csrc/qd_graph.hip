@@ -17,7 +17,7 @@ int qd_fail(int code, const char *fmt, ...)
     return code;
 }
 
-extern "C" int qd_version(void) { return 117; }      // 117: qd_isd_create, qd_isd_destroy, qd_isd_info, qd_isd_run, qd_isd_hist, qd_isd_reset (the random information-set estimate of the distance, distance.hip); 116: qd_soft_fold, qd_soft_weigh, qd_soft_tally (soft outputs per shot, soft.hip); 115: qd_search_create, qd_search_destroy, qd_search_reset, qd_search_seed, qd_search_level, qd_search_counters, qd_search_found, qd_search_chain (the search for undetectable logical faults, logical_search.hip); 114: qd_shrink_begin, qd_shrink_step (shrinking failing fault sets, shrink.hip); 113: qd_decoder_relay_info, QD_RELAY_FLAG_MARGINALS_DEVICE (Relay-BP with its marginals in device memory, bp_relay_device.hip); 112: qd_decoder_create_relay (Relay-BP, bp_relay.hip); 111: qd_strata_create, qd_strata_destroy, qd_strata_info, qd_sample_dem_strata (stratified DEM sampling, strata_sampler.hip); 110: qd_sample_dem_faults, qd_commit_bits, qd_fault_stats_batch (fault-level outputs, faults.hip); 109: qd_unpack_b8, qd_pack_b8 (Stim's bit-packed samples, bitpack.hip); 108: qd_shot_flags_fold, qd_tally_batch, qd_sample_circuit_shots, qd_sample_dem_shots (the device-resident memory experiment); 107: off-chip windows decode (qd_graph_create used to refuse them), QD_FLAG_OFF_CHIP, QD_POST_OSD0_OFFCHIP (no new export); 106: qd_circuit_create takes Y_ERROR / PAULI_CHANNEL_1 / PAULI_CHANNEL_2 programs (no new export); 105: qd_decoder_fast_start; 104: qd_circuit_* and qd_sample_circuit; 103: qd_decoder_post_head_start; 102: qd_graph_info fills 10 entries again, qd_graph_info_ex(g, info, n) the rest; 101: qd_decoder_postproc_kernel
+extern "C" int qd_version(void) { return 118; }      // 118: qd_bit_planes, qd_calib_create, qd_calib_destroy, qd_calib_info, qd_parity_counts (fitting priors to detector samples, calibrate.hip); 117: qd_isd_create, qd_isd_destroy, qd_isd_info, qd_isd_run, qd_isd_hist, qd_isd_reset (the random information-set estimate of the distance, distance.hip); 116: qd_soft_fold, qd_soft_weigh, qd_soft_tally (soft outputs per shot, soft.hip); 115: qd_search_create, qd_search_destroy, qd_search_reset, qd_search_seed, qd_search_level, qd_search_counters, qd_search_found, qd_search_chain (the search for undetectable logical faults, logical_search.hip); 114: qd_shrink_begin, qd_shrink_step (shrinking failing fault sets, shrink.hip); 113: qd_decoder_relay_info, QD_RELAY_FLAG_MARGINALS_DEVICE (Relay-BP with its marginals in device memory, bp_relay_device.hip); 112: qd_decoder_create_relay (Relay-BP, bp_relay.hip); 111: qd_strata_create, qd_strata_destroy, qd_strata_info, qd_sample_dem_strata (stratified DEM sampling, strata_sampler.hip); 110: qd_sample_dem_faults, qd_commit_bits, qd_fault_stats_batch (fault-level outputs, faults.hip); 109: qd_unpack_b8, qd_pack_b8 (Stim's bit-packed samples, bitpack.hip); 108: qd_shot_flags_fold, qd_tally_batch, qd_sample_circuit_shots, qd_sample_dem_shots (the device-resident memory experiment); 107: off-chip windows decode (qd_graph_create used to refuse them), QD_FLAG_OFF_CHIP, QD_POST_OSD0_OFFCHIP (no new export); 106: qd_circuit_create takes Y_ERROR / PAULI_CHANNEL_1 / PAULI_CHANNEL_2 programs (no new export); 105: qd_decoder_fast_start; 104: qd_circuit_* and qd_sample_circuit; 103: qd_decoder_post_head_start; 102: qd_graph_info fills 10 entries again, qd_graph_info_ex(g, info, n) the rest; 101: qd_decoder_postproc_kernel
 extern "C" const char *qd_last_error(void) { return g_err; }
 extern "C" int qd_device_count(void)
 {

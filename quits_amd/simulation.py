@@ -24,6 +24,8 @@
                                                 sampler (quits_amd/search.py has the definition; re-exported from there)
   estimate_distance, estimate_code_distance     the random information-set estimate of the circuit-level or code distance on the device: an upper
                                                 bound with its witnesses (quits_amd/distance.py has the definition; re-exported from there)
+  estimate_priors                               the priors of a model's hyperedges fitted to detector samples, counted on the device, with
+                                                jackknife standard errors (quits_amd/calibrate.py has the definition; re-exported from there)
 
 `get_codecap_pL` keeps the reference's signature and its random stream (`np.random.seed(seed)` followed by one
 `np.random.binomial(1, p, n)` per trial), so a given seed produces the same noise vectors as the reference.  With a plug-in
@@ -39,6 +41,7 @@ import numpy as np
 
 from .search import LogicalSearchResult, find_undetectable_logical_errors, search_mirror  # noqa: F401  (re-exported)
 from .distance import DistanceResult, distance_mirror, estimate_code_distance, estimate_distance  # noqa: F401  (re-exported)
+from .calibrate import CalibrationResult, estimate_priors  # noqa: F401  (re-exported)
 
 
 def get_stim_mem_result(circuit, num_trials, seed=-1):
