@@ -199,81 +199,36 @@ def check(rc):
         raise QdError(rc, load().qd_last_error().decode(errors="replace"))
 
 
-def require_experiment(L):
-    """The entry points of library version 108 (tallies, flag fold, list sampling): a clear error from an older library."""
-    if not hasattr(L, "qd_tally_batch"):
-        raise RuntimeError("quits_amd: %s is version %d; the device-resident memory experiment needs >= 108 -- rebuild it" % (LIB_PATH, L.qd_version()))
-    return L
+# One row per group of entry points newer than the oldest library load() accepts: the suffix of require_<suffix>, the symbol whose presence
+# stands for the group, the library version that brought it, and what needs it (the subject and verb of the error message).
+ENTRY_POINT_GROUPS = (
+    ("experiment", "qd_tally_batch", 108, "the device-resident memory experiment needs"),
+    ("bitpack", "qd_unpack_b8", 109, "bit-packed samples need"),
+    ("faults", "qd_commit_bits", 110, "fault-level outputs need"),
+    ("strata", "qd_strata_create", 111, "stratified sampling needs"),
+    ("relay", "qd_decoder_create_relay", 112, "Relay-BP needs"),
+    ("relay_forms", "qd_decoder_relay_info", 113, "choosing where Relay-BP keeps its marginals needs"),
+    ("shrink", "qd_shrink_begin", 114, "shrinking fault sets needs"),
+    ("search", "qd_search_create", 115, "the logical-fault search needs"),
+    ("soft", "qd_soft_fold", 116, "soft outputs need"),
+    ("distance", "qd_isd_create", 117, "the distance estimate needs"),
+    ("calibrate", "qd_calib_create", 118, "fitting priors needs"),
+)
 
 
-def require_bitpack(L):
-    """The entry points of library version 109 (bit-packed samples): a clear error from an older library."""
-    if not hasattr(L, "qd_unpack_b8"):
-        raise RuntimeError("quits_amd: %s is version %d; bit-packed samples need >= 109 -- rebuild it" % (LIB_PATH, L.qd_version()))
-    return L
+def _require(suffix, probe, version, phrase):
+    def require(L):
+        if not hasattr(L, probe):
+            raise RuntimeError("quits_amd: %s is version %d; %s >= %d -- rebuild it" % (LIB_PATH, L.qd_version(), phrase, version))
+        return L
+    require.__name__ = require.__qualname__ = "require_" + suffix
+    require.__doc__ = "`L`, if it has the entry points of library version %d (%s): a clear error from an older library." % (version, probe)
+    return require
 
 
-def require_faults(L):
-    """The entry points of library version 110 (sampled faults, committed corrections, fault statistics): a clear error from an older library."""
-    if not hasattr(L, "qd_commit_bits"):
-        raise RuntimeError("quits_amd: %s is version %d; fault-level outputs need >= 110 -- rebuild it" % (LIB_PATH, L.qd_version()))
-    return L
-
-
-def require_strata(L):
-    """The entry points of library version 111 (stratified DEM sampling): a clear error from an older library."""
-    if not hasattr(L, "qd_strata_create"):
-        raise RuntimeError("quits_amd: %s is version %d; stratified sampling needs >= 111 -- rebuild it" % (LIB_PATH, L.qd_version()))
-    return L
-
-
-def require_relay(L):
-    """The entry point of library version 112 (Relay-BP): a clear error from an older library."""
-    if not hasattr(L, "qd_decoder_create_relay"):
-        raise RuntimeError("quits_amd: %s is version %d; Relay-BP needs >= 112 -- rebuild it" % (LIB_PATH, L.qd_version()))
-    return L
-
-
-def require_relay_forms(L):
-    """The entry point of library version 113 (Relay-BP with its marginals in device memory): a clear error from an older library."""
-    if not hasattr(L, "qd_decoder_relay_info"):
-        raise RuntimeError("quits_amd: %s is version %d; choosing where Relay-BP keeps its marginals needs >= 113 -- rebuild it" % (LIB_PATH, L.qd_version()))
-    return L
-
-
-def require_shrink(L):
-    """The entry points of library version 114 (shrinking failing fault sets): a clear error from an older library."""
-    if not hasattr(L, "qd_shrink_begin"):
-        raise RuntimeError("quits_amd: %s is version %d; shrinking fault sets needs >= 114 -- rebuild it" % (LIB_PATH, L.qd_version()))
-    return L
-
-
-def require_search(L):
-    """The entry points of library version 115 (the search for undetectable logical faults): a clear error from an older library."""
-    if not hasattr(L, "qd_search_create"):
-        raise RuntimeError("quits_amd: %s is version %d; the logical-fault search needs >= 115 -- rebuild it" % (LIB_PATH, L.qd_version()))
-    return L
-
-
-def require_soft(L):
-    """The entry points of library version 116 (soft outputs per shot): a clear error from an older library."""
-    if not hasattr(L, "qd_soft_fold"):
-        raise RuntimeError("quits_amd: %s is version %d; soft outputs need >= 116 -- rebuild it" % (LIB_PATH, L.qd_version()))
-    return L
-
-
-def require_distance(L):
-    """The entry points of library version 117 (the random information-set estimate of the distance): a clear error from an older library."""
-    if not hasattr(L, "qd_isd_create"):
-        raise RuntimeError("quits_amd: %s is version %d; the distance estimate needs >= 117 -- rebuild it" % (LIB_PATH, L.qd_version()))
-    return L
-
-
-def require_calibrate(L):
-    """The entry points of library version 118 (fitting priors to detector samples): a clear error from an older library."""
-    if not hasattr(L, "qd_calib_create"):
-        raise RuntimeError("quits_amd: %s is version %d; fitting priors needs >= 118 -- rebuild it" % (LIB_PATH, L.qd_version()))
-    return L
+# require_experiment(L), require_bitpack(L), ..., require_calibrate(L)
+for _row in ENTRY_POINT_GROUPS:
+    globals()["require_" + _row[0]] = _require(*_row)
 
 
 def require_gpu():

@@ -25,9 +25,55 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr())
 
 
-class WindowGraph:
+class _Handle:
+    """Owner of one library object: `_h` is its handle, `_L` the library, `_destroy` the name of the function that frees it.  The object is
+    freed with its owner; at interpreter shutdown, when the library may be gone first, a failing call is swallowed."""
+    _destroy = None
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            try:
+                getattr(self._L, self._destroy)(self._h)
+            except Exception:
+                pass
+            self._h = None
+
+
+def _seed64(seed):
+    """A seed as the library takes it: any Python int, reduced mod 2^64."""
+    return C.c_uint64(int(seed) & (2 ** 64 - 1))
+
+
+def _sample_rows(shots, m, nobs):
+    """(det uint8 [shots, m], obs uint8 [shots, nobs]) for a sampler to fill, on the current device."""
+    torch = _torch()
+    return torch.empty((shots, m), dtype=torch.uint8, device="cuda"), torch.empty((shots, nobs), dtype=torch.uint8, device="cuda")
+
+
+def _fault_rows(fault_bits, shots, nfaults):
+    """(fault_bits, its row stride): the caller's rows checked -- cuda int32 [shots, >= ceil(nfaults / 32)], unit stride inside a row -- or new
+    rows of exactly that many words."""
+    torch = _torch()
+    words = (nfaults + 31) // 32
+    if fault_bits is None:
+        fault_bits = torch.empty((shots, words), dtype=torch.int32, device="cuda")
+    assert fault_bits.is_cuda and fault_bits.dtype == torch.int32 and fault_bits.dim() == 2 and fault_bits.shape[0] == shots
+    assert fault_bits.shape[1] >= words and (fault_bits.shape[1] <= 1 or fault_bits.stride(1) == 1)
+    return fault_bits, fault_bits.stride(0) if shots > 1 else max(fault_bits.stride(0), fault_bits.shape[1])
+
+
+def _check_mask(fail_mask, B):
+    """The pointer of a fail mask over B shots: a contiguous cuda int64 tensor of at least ceil(B / 64) words."""
+    torch = _torch()
+    assert fail_mask.is_cuda and fail_mask.dtype == torch.int64 and fail_mask.dim() == 1 and fail_mask.is_contiguous()
+    assert fail_mask.shape[0] >= (B + 63) // 64
+    return _ptr(fail_mask)
+
+
+class WindowGraph(_Handle):
     """Device copy of one window check matrix + priors (qd_graph).  Stands in for the sparse-matrix half of
     `BpOsdDecoder(pcm, channel_probs=...)` (reference sliding_window.py:149)."""
+    _destroy = "qd_graph_destroy"
 
     def __init__(self, pcm, priors, device: Optional[int] = None):
         L = _lib.require_gpu()
@@ -51,17 +97,10 @@ class WindowGraph:
                 "osd_lds_bytes", "rank", "scatter_walk_cycles", "scatter_walk_ideal", "scatter_threads", "scatter_checks_per_lane")
         return dict(zip(keys, [int(x) for x in arr]))
 
-    def __del__(self):
-        if getattr(self, "_h", None):
-            try:
-                self._L.qd_graph_destroy(self._h)
-            except Exception:
-                pass
-            self._h = None
 
-
-class BatchDecoder:
+class BatchDecoder(_Handle):
     """qd_decoder: BP(+OSD-0) over a batch of shots for one window."""
+    _destroy = "qd_decoder_destroy"
 
     def __init__(self, graph: WindowGraph, bp_method="minimum_sum", schedule="parallel", max_iter=0,
                  osd_method="osd_0", osd_order=0, ms_scaling_factor=1.0, edge_messages=False, raw_llr=False, off_chip=False):
@@ -169,14 +208,6 @@ class BatchDecoder:
         _lib.check(self._L.qd_decoder_profile(self._h, arr, 1 if reset else 0))
         return {"bp_ms": arr[0], "osd_ms": arr[1], "bp_launches": int(arr[2]), "osd_launches": int(arr[3])}
 
-    def __del__(self):
-        if getattr(self, "_h", None):
-            try:
-                self._L.qd_decoder_destroy(self._h)
-            except Exception:
-                pass
-            self._h = None
-
 
 class RelayBatchDecoder(BatchDecoder):
     """qd_decoder_create_relay: Relay-BP over a batch of shots for one window (csrc/bp_relay.hip; the definition is quits_amd/relay.py), then
@@ -235,8 +266,9 @@ class RelayBatchDecoder(BatchDecoder):
                     relay_lds_bytes=lds)
 
 
-class GF2Matrix:
+class GF2Matrix(_Handle):
     """Sparse GF(2) matrix on the device (qd_spmat), CSR."""
+    _destroy = "qd_spmat_destroy"
 
     def __init__(self, mat, device: Optional[int] = None):
         L = _lib.require_gpu()
@@ -256,14 +288,6 @@ class GF2Matrix:
         _lib.check(self._L.qd_gf2_spmv_batch(self._h, _ptr(err_bits), err_bits.stride(0), err_bits.shape[0], _ptr(out),
                                              out.stride(0), 1 if accumulate else 0, sp))
         return out
-
-    def __del__(self):
-        if getattr(self, "_h", None):
-            try:
-                self._L.qd_spmat_destroy(self._h)
-            except Exception:
-                pass
-            self._h = None
 
 
 def unpack_bits(bits, nbits: int):
@@ -323,9 +347,7 @@ class Tally:
             assert flags.is_cuda and flags.dtype == torch.uint8 and flags.shape == (B,) and flags.is_contiguous()
             fp = _ptr(flags)
         if fail_mask is not None:
-            assert fail_mask.is_cuda and fail_mask.dtype == torch.int64 and fail_mask.dim() == 1 and fail_mask.is_contiguous()
-            assert fail_mask.shape[0] >= (B + 63) // 64
-            mp = _ptr(fail_mask)
+            mp = _check_mask(fail_mask, B)
         _lib.check(self._L.qd_tally_batch(_ptr(pred), pred.stride(0), _ptr(obs), obs.stride(0), self.k, B, fp, _ptr(self.data), mp, _stream_ptr()))
 
     def counts(self):
@@ -379,11 +401,10 @@ class FaultStats:
         assert B == 1 or corr.stride(0) == stride, "faults and corrections must share a row stride"
         assert 32 * min(faults.shape[1], corr.shape[1]) >= nbits
         assert residual.is_cuda and residual.dtype == torch.uint8 and residual.dim() == 2 and (residual.shape[1] <= 1 or residual.stride(1) == 1)
-        assert fail_mask.is_cuda and fail_mask.dtype == torch.int64 and fail_mask.dim() == 1 and fail_mask.is_contiguous()
-        assert fail_mask.shape[0] >= (B + 63) // 64
+        mp = _check_mask(fail_mask, B)
         m = residual.shape[1]
         rs = residual.stride(0) if B > 1 else max(residual.stride(0), m)
-        _lib.check(self._L.qd_fault_stats_batch(_ptr(faults), _ptr(corr), stride, int(nbits), _ptr(residual), rs, m, _ptr(fail_mask), B, int(shot0),
+        _lib.check(self._L.qd_fault_stats_batch(_ptr(faults), _ptr(corr), stride, int(nbits), _ptr(residual), rs, m, mp, B, int(shot0),
                                                 _ptr(self.hist), _ptr(self.counts), _ptr(self.best), _stream_ptr()))
 
     def result(self):
@@ -450,9 +471,7 @@ def soft_tally(soft, shifts, fail_mask, hist, stream=None):
     assert hist.is_cuda and hist.dtype == torch.int64 and hist.shape == (_lib.SOFT_FIELDS, 2, _lib.SOFT_BINS) and hist.is_contiguous()
     mp = C.c_void_p(0)
     if fail_mask is not None:
-        assert fail_mask.is_cuda and fail_mask.dtype == torch.int64 and fail_mask.dim() == 1 and fail_mask.is_contiguous()
-        assert fail_mask.shape[0] >= (B + 63) // 64
-        mp = _ptr(fail_mask)
+        mp = _check_mask(fail_mask, B)
     sp = _stream_ptr() if stream is None else C.c_void_p(stream.cuda_stream)
     _lib.check(L.qd_soft_tally(_ptr(soft), ss, B, sh.ctypes.data_as(C.c_void_p), mp, _ptr(hist), sp))
     return hist
@@ -567,9 +586,8 @@ class FaultShrinker:
             pad = np.zeros(((A + 63) // 64) * 64, np.uint8)
             pad[:A] = v
             fail_mask = torch.from_numpy(np.packbits(pad, bitorder="little").view("<i8").copy()).to("cuda")
-        assert fail_mask.is_cuda and fail_mask.dim() == 1 and fail_mask.is_contiguous() and fail_mask.shape[0] >= (A + 63) // 64
         _lib.check(self._L.qd_shrink_step(self.Ht._h, self.Lt._h, _ptr(self.sets), self.words, self.P, _ptr(self.state), _ptr(self._live[0]), A,
-                                          _ptr(fail_mask), _ptr(self._live[1]), _ptr(self._count), _ptr(self.kept_det), self.kept_det.stride(0),
+                                          _check_mask(fail_mask, A), _ptr(self._live[1]), _ptr(self._count), _ptr(self.kept_det), self.kept_det.stride(0),
                                           _ptr(self.kept_obs), self.kept_obs.stride(0), _ptr(self._det), self._det.stride(0), _ptr(self._obs),
                                           self._obs.stride(0), _ptr(self._fault), _ptr(self._parent), _stream_ptr()))
         self._live.reverse()
@@ -618,12 +636,9 @@ class DemSampler:
         assert self.priors.shape[0] == self.Ht.shape[0]
 
     def sample(self, shots: int, seed: int, shot0: int = 0):
-        torch = _torch()
-        det = torch.empty((shots, self.m), dtype=torch.uint8, device="cuda")
-        obs = torch.empty((shots, self.nobs), dtype=torch.uint8, device="cuda")
+        det, obs = _sample_rows(shots, self.m, self.nobs)
         L = self.Ht._L
-        _lib.check(L.qd_sample_dem(self.Ht._h, self.Lt._h, self.priors.ctypes.data_as(C.c_void_p),
-                                   C.c_uint64(int(seed) & (2 ** 64 - 1)), int(shot0), int(shots), _ptr(det),
+        _lib.check(L.qd_sample_dem(self.Ht._h, self.Lt._h, self.priors.ctypes.data_as(C.c_void_p), _seed64(seed), int(shot0), int(shots), _ptr(det),
                                    det.stride(0), _ptr(obs), obs.stride(0), _stream_ptr()))
         return det, obs
 
@@ -637,13 +652,11 @@ class DemSampler:
     def sample_shots(self, indices, seed: int):
         """Row b = shot indices[b] of this seed's stream (qd_sample_dem_shots): what `sample(1, seed, shot0=indices[b])` returns.  `indices`: an
         int64 cuda tensor or any integer sequence; any order, repeats allowed."""
-        torch = _torch()
         idx = _shot_indices(indices)
         n = idx.shape[0]
-        det = torch.empty((n, self.m), dtype=torch.uint8, device="cuda")
-        obs = torch.empty((n, self.nobs), dtype=torch.uint8, device="cuda")
+        det, obs = _sample_rows(n, self.m, self.nobs)
         L = _lib.require_experiment(self.Ht._L)
-        _lib.check(L.qd_sample_dem_shots(self.Ht._h, self.Lt._h, self.priors.ctypes.data_as(C.c_void_p), C.c_uint64(int(seed) & (2 ** 64 - 1)),
+        _lib.check(L.qd_sample_dem_shots(self.Ht._h, self.Lt._h, self.priors.ctypes.data_as(C.c_void_p), _seed64(seed),
                                          _ptr(idx), n, _ptr(det), det.stride(0), _ptr(obs), obs.stride(0), _stream_ptr()))
         return det, obs
 
@@ -653,17 +666,10 @@ class DemSampler:
         return self.Ht.shape[0]
 
     def _sample_with_faults(self, idx, shots, seed, shot0, fault_bits):
-        torch = _torch()
         L = _lib.require_faults(self.Ht._L)
-        words = (self.nfaults + 31) // 32
-        det = torch.empty((shots, self.m), dtype=torch.uint8, device="cuda")
-        obs = torch.empty((shots, self.nobs), dtype=torch.uint8, device="cuda")
-        if fault_bits is None:
-            fault_bits = torch.empty((shots, words), dtype=torch.int32, device="cuda")
-        assert fault_bits.is_cuda and fault_bits.dtype == torch.int32 and fault_bits.dim() == 2 and fault_bits.shape[0] == shots
-        assert fault_bits.shape[1] >= words and (fault_bits.shape[1] <= 1 or fault_bits.stride(1) == 1)
-        fs = fault_bits.stride(0) if shots > 1 else max(fault_bits.stride(0), fault_bits.shape[1])
-        _lib.check(L.qd_sample_dem_faults(self.Ht._h, self.Lt._h, self.priors.ctypes.data_as(C.c_void_p), C.c_uint64(int(seed) & (2 ** 64 - 1)),
+        det, obs = _sample_rows(shots, self.m, self.nobs)
+        fault_bits, fs = _fault_rows(fault_bits, shots, self.nfaults)
+        _lib.check(L.qd_sample_dem_faults(self.Ht._h, self.Lt._h, self.priors.ctypes.data_as(C.c_void_p), _seed64(seed),
                                           int(shot0), C.c_void_p(0) if idx is None else _ptr(idx), shots, _ptr(det), det.stride(0), _ptr(obs),
                                           obs.stride(0), _ptr(fault_bits), fs, _stream_ptr()))
         return det, obs, fault_bits
@@ -680,11 +686,12 @@ class DemSampler:
         return self._sample_with_faults(idx, int(idx.shape[0]), seed, 0, fault_bits)
 
 
-class StratifiedDemSampler:
+class StratifiedDemSampler(_Handle):
     """Device-side sampler of the detector error model conditioned on the number of faults (qd_sample_dem_strata): row b holds exactly ks[b]
     faults, drawn from the model's exact conditional law.  quits_amd/strata.py states the law, the random stream and the threshold table
     (computed here once, for 0 .. kmax faults, and kept in device memory); `pmf[k]` = P(|E| = k) and `tail` = P(|E| > kmax) weigh the strata.
     Returns what DemSampler.sample_faults returns."""
+    _destroy = "qd_strata_destroy"
 
     def __init__(self, check_matrix, observable_matrix, priors, kmax: int, device: Optional[int] = None):
         from scipy.sparse import csr_matrix
@@ -720,15 +727,9 @@ class StratifiedDemSampler:
         if isinstance(ks, torch.Tensor):
             ks = ks.cpu().numpy()
         k = torch.from_numpy(strata.check_ks(ks, shots, self.priors, self.kmax)).to("cuda")
-        words = (self.nfaults + 31) // 32
-        det = torch.empty((shots, self.m), dtype=torch.uint8, device="cuda")
-        obs = torch.empty((shots, self.nobs), dtype=torch.uint8, device="cuda")
-        if fault_bits is None:
-            fault_bits = torch.empty((shots, words), dtype=torch.int32, device="cuda")
-        assert fault_bits.is_cuda and fault_bits.dtype == torch.int32 and fault_bits.dim() == 2 and fault_bits.shape[0] == shots
-        assert fault_bits.shape[1] >= words and (fault_bits.shape[1] <= 1 or fault_bits.stride(1) == 1)
-        fs = fault_bits.stride(0) if shots > 1 else max(fault_bits.stride(0), fault_bits.shape[1])
-        _lib.check(self._L.qd_sample_dem_strata(self._h, self.Ht._h, self.Lt._h, C.c_uint64(int(seed) & (2 ** 64 - 1)), int(shot0),
+        det, obs = _sample_rows(shots, self.m, self.nobs)
+        fault_bits, fs = _fault_rows(fault_bits, shots, self.nfaults)
+        _lib.check(self._L.qd_sample_dem_strata(self._h, self.Ht._h, self.Lt._h, _seed64(seed), int(shot0),
                                                 C.c_void_p(0) if idx is None else _ptr(idx), _ptr(k), shots, _ptr(det), det.stride(0), _ptr(obs),
                                                 obs.stride(0), _ptr(fault_bits), fs, _stream_ptr()))
         return det, obs, fault_bits
@@ -749,21 +750,14 @@ class StratifiedDemSampler:
         idx = _shot_indices(indices)
         return self._sample(idx, int(idx.shape[0]), ks, seed, 0, fault_bits)
 
-    def __del__(self):
-        if getattr(self, "_h", None):
-            try:
-                self._L.qd_strata_destroy(self._h)
-            except Exception:
-                pass
-            self._h = None
 
-
-class CircuitSampler:
+class CircuitSampler(_Handle):
     """Device-side circuit-level sampler (qd_sample_circuit): a Pauli-frame simulation of the circuit, what the reference gets from
     `circuit.compile_detector_sampler().sample(shots, separate_observables=True)` (simulation.py:8-28).  Same surface as DemSampler.
     `circuit`: circuit text, quits_amd.dem.Circuit, stim.Circuit, or a quits_amd.frame.CompiledCircuit.  The semantics, the random
     stream and its assumption (deterministic detectors) are in quits_amd/frame.py.  Biased noise (Y_ERROR, PAULI_CHANNEL_1,
     PAULI_CHANNEL_2) is sampled exactly and needs no `approximate_disjoint_errors`: that setting concerns detector error models only."""
+    _destroy = "qd_circuit_destroy"
 
     def __init__(self, circuit, device: Optional[int] = None):
         from ..frame import CompiledCircuit, compile_circuit
@@ -793,10 +787,8 @@ class CircuitSampler:
 
     def sample(self, shots: int, seed: int, shot0: int = 0):
         """(det uint8 [shots, m], obs uint8 [shots, nobs]) on the current device, shots shot0 .. shot0 + shots - 1."""
-        torch = _torch()
-        det = torch.empty((shots, self.m), dtype=torch.uint8, device="cuda")
-        obs = torch.empty((shots, self.nobs), dtype=torch.uint8, device="cuda")
-        _lib.check(self._L.qd_sample_circuit(self._h, C.c_uint64(int(seed) & (2 ** 64 - 1)), int(shot0), int(shots), _ptr(det),
+        det, obs = _sample_rows(shots, self.m, self.nobs)
+        _lib.check(self._L.qd_sample_circuit(self._h, _seed64(seed), int(shot0), int(shots), _ptr(det),
                                              det.stride(0), _ptr(obs), obs.stride(0), _stream_ptr()))
         return det, obs
 
@@ -810,22 +802,12 @@ class CircuitSampler:
     def sample_shots(self, indices, seed: int):
         """Row b = shot indices[b] of this seed's stream (qd_sample_circuit_shots): what `sample(1, seed, shot0=indices[b])` returns.
         `indices`: an int64 cuda tensor or any integer sequence; any order, repeats allowed."""
-        torch = _torch()
         idx = _shot_indices(indices)
         n = idx.shape[0]
-        det = torch.empty((n, self.m), dtype=torch.uint8, device="cuda")
-        obs = torch.empty((n, self.nobs), dtype=torch.uint8, device="cuda")
-        _lib.check(_lib.require_experiment(self._L).qd_sample_circuit_shots(self._h, C.c_uint64(int(seed) & (2 ** 64 - 1)), _ptr(idx), n, _ptr(det),
+        det, obs = _sample_rows(n, self.m, self.nobs)
+        _lib.check(_lib.require_experiment(self._L).qd_sample_circuit_shots(self._h, _seed64(seed), _ptr(idx), n, _ptr(det),
                                                                             det.stride(0), _ptr(obs), obs.stride(0), _stream_ptr()))
         return det, obs
-
-    def __del__(self):
-        if getattr(self, "_h", None):
-            try:
-                self._L.qd_circuit_destroy(self._h)
-            except Exception:
-                pass
-            self._h = None
 
 
 def _norm(x):

@@ -120,6 +120,28 @@ def get_codecap_pL(code, p, num_trials, decoder, dict, basis='Z', seed=-1, tqdm_
 
 
 # ---- a memory experiment on the device ------------------------------------------------------------------------------------------
+def _rate(shots, errors):
+    """(pL, sigma): `errors` / `shots` and its binomial standard deviation; NaN without shots."""
+    if not shots:
+        return float("nan"), float("nan")
+    pL = errors / shots
+    return pL, math.sqrt(pL * (1.0 - pL) / shots)
+
+
+class _ByFaults:
+    """The method the results with shots_by_faults / errors_by_faults share."""
+
+    def failure_fraction(self):
+        """f(w) = errors_by_faults[w] / shots_by_faults[w], float64 [256]; NaN where no shot had w faults (stratum w has no shots)."""
+        s = self.shots_by_faults.astype(np.float64)
+        return np.divide(self.errors_by_faults.astype(np.float64), s, out=np.full(s.shape, np.nan), where=s > 0)
+
+
+def _fault_rows(bits, nfaults):
+    """numpy bool [rows, nfaults] of packed fault words (a cuda int32 tensor: bit j & 31 of word j >> 5 = fault j)."""
+    return np.unpackbits(np.ascontiguousarray(bits.cpu().numpy()).view(np.uint8), axis=1, bitorder="little")[:, :nfaults].astype(bool)
+
+
 def _batch_step(batch):
     """`batch` rounded up to a multiple of 64, a word of the fail mask."""
     return (int(batch) + 63) // 64 * 64
@@ -178,8 +200,7 @@ class MemExperimentResult:
         from ._lib import SHOT_FLAG_NAMES, TALLY_HEAD
         c = np.asarray(counts, dtype=np.int64)
         shots, errors = int(c[0]), int(c[1])
-        pL = errors / shots if shots else float("nan")
-        sigma = math.sqrt(pL * (1.0 - pL) / shots) if shots else float("nan")
+        pL, sigma = _rate(shots, errors)
         flagged = {name: (int(c[2 + 2 * j]), int(c[3 + 2 * j])) for j, name in enumerate(SHOT_FLAG_NAMES)}
         return cls(shots, errors, pL, sigma, c[TALLY_HEAD:].copy(), flagged, np.asarray(failing_shots, dtype=np.int64), bool(failures_truncated),
                    int(seed), str(sampler), int(batch), float(seconds), shots / seconds if seconds > 0 else 0.0)
@@ -190,15 +211,19 @@ def _as_circuit(circuit):
     return circuit if isinstance(circuit, Circuit) else Circuit(str(circuit))
 
 
+def _check_sampler(sampler):
+    if sampler not in ("circuit", "dem"):
+        raise ValueError("sampler must be 'circuit' or 'dem'")
+
+
 def _make_sampler(circ, sampler):
     from .decoder.device import CircuitSampler, DemSampler
+    _check_sampler(sampler)
     if sampler == "circuit":
         return CircuitSampler(circ)
-    if sampler == "dem":
-        from .decoder.base import detector_error_model_to_matrix
-        H, L, priors = detector_error_model_to_matrix(circ.detector_error_model())
-        return DemSampler(H, L, priors)
-    raise ValueError("sampler must be 'circuit' or 'dem'")
+    from .decoder.base import detector_error_model_to_matrix
+    H, L, priors = detector_error_model_to_matrix(circ.detector_error_model())
+    return DemSampler(H, L, priors)
 
 
 def _mask_to_indices(words, shot0, limit):
@@ -208,6 +233,104 @@ def _mask_to_indices(words, shot0, limit):
     bits = np.unpackbits(words[nz].astype("<u8").view(np.uint8).reshape(-1, 8), axis=1, bitorder="little").astype(bool)
     idx = (np.int64(shot0) + nz.astype(np.int64)[:, None] * 64 + np.arange(64, dtype=np.int64)[None, :])[bits]
     return idx[:limit], idx.shape[0] > limit
+
+
+def _default_batch(plan):
+    """As many of the plan's chunks as the two-stream driver has lanes (at least two, so that it runs)."""
+    return max(2, int(plan.lanes) if plan.pipeline else 2) * int(plan.chunk)
+
+
+@dataclasses.dataclass
+class _Setup:
+    """What `_experiment_setup` hands a driver: the Circuit, the sampler (None where the driver asked for none), the model H, L, priors of the
+    DEM-column drivers (else None), the strata [(k, N_k), ...] (else None), the cached plan, `batch` (the caller's, or the default), `step`
+    (`batch` rounded up to a word of the fail mask, the result's `batch` field) and `words` = ceil(plan.nfaults / 32) of a correction row."""
+    circ: object
+    sampler: object
+    H: object
+    L: object
+    priors: object
+    strata: object
+    plan: object
+    batch: int
+    step: int
+    words: int
+
+    def decode_tally(self, tally, det, obs, soft_fields=0):
+        """One batch decoded with its correction in view and tallied: allocates the correction rows, the soft records where `soft_fields` says
+        how many, and the fail mask (written by the tally, so not zeroed).  Returns (correction, fail mask, soft records or None)."""
+        import torch
+        n = det.shape[0]
+        corr = torch.empty((n, self.words), dtype=torch.int32, device="cuda")
+        rec = torch.empty((n, soft_fields), dtype=torch.int64, device="cuda") if soft_fields else None
+        pred = self.plan.decode(det, None, corr, rec)
+        mask = torch.empty(((n + 63) // 64,), dtype=torch.int64, device="cuda")
+        tally.add(pred, obs, None, mask)
+        return corr, mask, rec
+
+    def decode_stats(self, Hdev, tally, fstats, det, obs, faults, shot0):
+        """`decode_tally`, then `det` -- the batch's own rows -- becomes the residual H C xor det in place and `fstats` bins the batch by its
+        faults, its correction and that residual.  Hdev: the model's H as a decoder.device.GF2Matrix.  Nothing is read back."""
+        corr, mask, _ = self.decode_tally(tally, det, obs)
+        Hdev.xor_apply(corr, det, accumulate=True)
+        fstats.add(faults, corr, self.plan.nfaults, det, mask, shot0)
+
+
+def _experiment_setup(circuit, hz, lz, W, F, decoder, opts, needs, *, sampler=None, columns=False, strata=None, batch=None, on_device=None):
+    """What every driver below does before its loop, in this order -- a new driver is this call and a loop body:
+
+      arguments  F != 0, `sampler` 'circuit', 'dem' or, with `columns` only, None (no sampler), `strata` a good k -> N_k mapping (_strata_plan): ValueError,
+                 whether or not there is a device.  A driver's further checks of its own arguments go in front of this call.
+      device     _lib.require_gpu and the entry-point groups named by `needs` (_lib.require_<name>, in that order; 'strata' is added where
+                 `strata` is given): RuntimeError, there is no CPU fallback.  Then `on_device()`, if given, before anything is put on the device.
+      model      the Circuit; with `columns` (the drivers that work on DEM columns) H, L, priors of its detector error model and from them the
+                 sampler -- StratifiedDemSampler up to the largest k where `strata` is given, else DemSampler for 'dem', none for None; without `columns`
+                 _make_sampler(circ, sampler), and the detector and observable counts are the sampler's (nothing extracts the model here).
+      plan       the number of rounds from the detector count and hz, the whole-history warning, the cached plan of (`decoder`, `opts`), its
+                 observable count against the circuit's and lz's, with `columns` its committed faults against the model's columns.
+
+    Returns a _Setup."""
+    import warnings
+    from . import _lib
+    if F == 0:
+        raise ValueError("Input parameter F cannot be zero.")
+    if sampler is not None:
+        _check_sampler(sampler)
+    todo = None if strata is None else _strata_plan(strata)
+    lib = _lib.require_gpu()                                # no GPU or no library: RuntimeError, there is no CPU fallback
+    for name in tuple(needs) + (("strata",) if todo is not None else ()):
+        getattr(_lib, "require_" + name)(lib)
+    if on_device is not None:
+        on_device()
+    from .decoder.base import detector_error_model_to_matrix, window_count
+    from .decoder.plan import cached_circuit_plan
+    circ = _as_circuit(circuit)
+    H = L = priors = None
+    if columns:
+        from . import strata as st
+        from .decoder.device import DemSampler, StratifiedDemSampler
+        H, L, priors = detector_error_model_to_matrix(circ.detector_error_model())
+        if todo is not None:
+            smp = StratifiedDemSampler(H, L, priors, max([k for k, _ in todo], default=0))
+            if todo:
+                st.check_ks(np.array([k for k, _ in todo]), len(todo), priors, smp.kmax)
+        else:
+            smp = DemSampler(H, L, priors) if sampler == "dem" else None
+        ndet, nobs = H.shape[0], L.shape[0]
+    else:
+        smp = _make_sampler(circ, sampler)
+        ndet, nobs = smp.m, smp.nobs
+    num_rounds = ndet // hz.shape[0] - 2
+    if window_count(num_rounds, W, F)[2]:
+        warnings.warn("Window size larger than the syndrome extraction rounds: Doing whole history correction")
+    plan = cached_circuit_plan(circ, hz, W, F, num_rounds, decoder, decoder, opts, opts)
+    if nobs != plan.nobs or np.asarray(lz.shape)[0] != plan.nobs:
+        raise ValueError("the circuit has %d observables, lz %d rows, the window plan commits %d" % (nobs, lz.shape[0], plan.nobs))
+    if columns and plan.nfaults != H.shape[1]:
+        raise ValueError("the windows commit %d faults, the detector error model has %d" % (plan.nfaults, H.shape[1]))
+    if batch is None:
+        batch = _default_batch(plan)
+    return _Setup(circ, smp, H, L, priors, todo, plan, batch, _batch_step(batch), (plan.nfaults + 31) // 32)
 
 
 def get_circuit_mem_pL(circuit, hz, lz, W, F, num_trials, max_iter=2, osd_order=0, bp_method='product_sum', schedule='serial',
@@ -256,41 +379,24 @@ def _mem_experiment(circuit, hz, lz, W, F, num_trials, decoder, opts, *, seed, s
     """The experiment loop of get_circuit_mem_pL and get_relay_mem_pL: `decoder` is the plug-in class of both window kinds, `opts` its
     keyword dict (the cached plan's key)."""
     import time
-    import warnings
-    from . import _lib
-    from .decoder.base import window_count
-    from .decoder.plan import cached_circuit_plan
-    if F == 0:
-        raise ValueError("Input parameter F cannot be zero.")
-    if sampler not in ("circuit", "dem"):
-        raise ValueError("sampler must be 'circuit' or 'dem'")
-    _lib.require_experiment(_lib.require_gpu())           # no GPU or no library: RuntimeError, there is no CPU fallback
     import torch
     from .decoder.device import Tally, shot_flags_fold
     from .parallel import env_rank_world, init_distributed, reduce_vector
     dist = None
     rank, world = (0, 1) if shard is None else (int(shard[0]), int(shard[1]))
-    if distributed:
+
+    def join_ranks():
+        nonlocal dist, rank, world
         env_rank, env_world, local = env_rank_world()
         if env_world > 1:
             torch.cuda.set_device(local % torch.cuda.device_count())    # one process per GPU; the plan, the samplers and RCCL follow the current device
         dist = init_distributed()
         if shard is None:
             rank, world = env_rank, env_world
-    circ = _as_circuit(circuit)
-    smp = _make_sampler(circ, sampler)
-    nz = hz.shape[0]
-    num_rounds = smp.m // nz - 2
-    if window_count(num_rounds, W, F)[2]:
-        warnings.warn("Window size larger than the syndrome extraction rounds: Doing whole history correction")
-    plan = cached_circuit_plan(circ, hz, W, F, num_rounds, decoder, decoder, opts, opts)
-    k = plan.nobs
-    if smp.nobs != k or np.asarray(lz.shape)[0] != k:
-        raise ValueError("the circuit has %d observables, lz %d rows, the window plan commits %d" % (smp.nobs, lz.shape[0], k))
-    if batch is None:
-        batch = max(2, int(plan.lanes) if plan.pipeline else 2) * int(plan.chunk)
-    batches = experiment_batches(num_trials, batch, rank, world)
-    step = _batch_step(batch)
+    su = _experiment_setup(circuit, hz, lz, W, F, decoder, opts, ("experiment",), sampler=sampler, batch=batch,
+                           on_device=join_ranks if distributed else None)
+    smp, plan, k, step = su.sampler, su.plan, su.plan.nobs, su.step
+    batches = experiment_batches(num_trials, su.batch, rank, world)
     limit = None if max_errors is None else -(-int(max_errors) // world)
     first = batches[0][0] if batches else 0
     nwin = len(plan.windows)
@@ -353,6 +459,7 @@ def replay_shots(circuit, shot_indices, seed, sampler='circuit'):
     row i being shot shot_indices[i] -- e.g. `result.failing_shots` of `get_circuit_mem_pL`, to decode them with other settings.  Both
     samplers draw shot s from (seed, s, site) alone, so nothing but the index is needed."""
     from . import _lib
+    _check_sampler(sampler)
     _lib.require_experiment(_lib.require_gpu())
     det, obs = _make_sampler(_as_circuit(circuit), sampler).sample_shots(shot_indices, int(seed))
     return det.cpu().numpy().astype(bool), obs.cpu().numpy().astype(bool)
@@ -388,8 +495,7 @@ class PostSelectionResult:
         if not (np.all(h[:, 0].sum(axis=1) == shots) and np.all(h[:, 1].sum(axis=1) == errors)):
             raise ValueError("soft histograms and counters disagree: %s / %s shots in the planes, counters %d / %d"
                              % (h[:, 0].sum(axis=1).tolist(), h[:, 1].sum(axis=1).tolist(), shots, errors))
-        pL = errors / shots if shots else float("nan")
-        sigma = math.sqrt(pL * (1.0 - pL) / shots) if shots else float("nan")
+        pL, sigma = _rate(shots, errors)
         return cls(shots, errors, pL, sigma, np.asarray(shifts, dtype=np.int32).copy(), h.copy(), int(seed), str(sampler), int(batch), float(seconds))
 
     def _field(self, field):
@@ -439,57 +545,33 @@ def get_postselected_pL(circuit, hz, lz, W, F, num_trials, max_iter=2, osd_order
 
     Returns a PostSelectionResult: `result.curve('weight')`, `result.at_rejection('iters', 0.05)`."""
     import time
-    import warnings
-    from . import _lib
-    from . import soft as _soft
-    from .decoder.base import window_count
-    from .decoder.plan import cached_circuit_plan
-    if F == 0:
-        raise ValueError("Input parameter F cannot be zero.")
-    if sampler not in ("circuit", "dem"):
-        raise ValueError("sampler must be 'circuit' or 'dem'")
-    _lib.require_soft(_lib.require_faults(_lib.require_experiment(_lib.require_gpu())))
     import torch
+    from . import soft as _soft
     from .decoder.device import SoftTally, Tally
     decoder, opts = _decoder_choice(relay, max_iter, osd_order, bp_method, schedule, osd_method)
-    circ = _as_circuit(circuit)
-    smp = _make_sampler(circ, sampler)
-    nz = hz.shape[0]
-    num_rounds = smp.m // nz - 2
-    if window_count(num_rounds, W, F)[2]:
-        warnings.warn("Window size larger than the syndrome extraction rounds: Doing whole history correction")
-    plan = cached_circuit_plan(circ, hz, W, F, num_rounds, decoder, decoder, opts, opts)
-    k = plan.nobs
-    if smp.nobs != k or np.asarray(lz.shape)[0] != k:
-        raise ValueError("the circuit has %d observables, lz %d rows, the window plan commits %d" % (smp.nobs, lz.shape[0], k))
-    if batch is None:
-        batch = max(2, int(plan.lanes) if plan.pipeline else 2) * int(plan.chunk)
-    batches = experiment_batches(num_trials, batch)
+    su = _experiment_setup(circuit, hz, lz, W, F, decoder, opts, ("experiment", "faults", "soft"), sampler=sampler, batch=batch)
+    smp, plan = su.sampler, su.plan
+    batches = experiment_batches(num_trials, su.batch)
     if shifts is None:
         iters = relay.total_iter if relay is not None else (int(max_iter) if int(max_iter) > 0 else max(w["graph"].n for w in plan.windows))
         shifts = _soft.default_shifts(plan.commit_weights().cpu().numpy(), plan.commit_priors(), smp.m, len(plan.windows), iters)
-    words = (plan.nfaults + 31) // 32
     with plan.in_use():
-        tally, stally = Tally(k), SoftTally(shifts)
+        tally, stally = Tally(plan.nobs), SoftTally(shifts)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for shot0, n in batches:
             det, obs = smp.sample(n, seed, shot0)
-            corr = torch.empty((n, words), dtype=torch.int32, device="cuda")
-            rec = torch.empty((n, len(_soft.FIELDS)), dtype=torch.int64, device="cuda")
-            pred = plan.decode(det, None, corr, rec)
-            mask = torch.empty(((n + 63) // 64,), dtype=torch.int64, device="cuda")
-            tally.add(pred, obs, None, mask)
+            _, mask, rec = su.decode_tally(tally, det, obs, len(_soft.FIELDS))
             stally.add(rec, mask)
         torch.cuda.synchronize()
         seconds = time.perf_counter() - t0
         counts, hist = tally.counts(), stally.result()
-    return PostSelectionResult.from_counts(counts, stally.shifts, hist, seed, sampler, _batch_step(batch), seconds)
+    return PostSelectionResult.from_counts(counts, stally.shifts, hist, seed, sampler, su.step, seconds)
 
 
 # ---- the same experiment with the faults in view --------------------------------------------------------------------------------------
 @dataclasses.dataclass
-class FaultSpectrumResult:
+class FaultSpectrumResult(_ByFaults):
     """What `get_fault_spectrum` returns.  shots, errors, pL as in MemExperimentResult.  shots_by_faults[w], errors_by_faults[w]: shots /
     failing shots in which w faults of the detector error model fired (bin 255 collects w >= 255).  residual_shots: shots whose correction C
     does not reproduce the syndrome (H C != det; some window reported an inconsistent syndrome), failing_residual_shots: the failing ones
@@ -509,11 +591,6 @@ class FaultSpectrumResult:
     batch: int = 0
     seconds: float = 0.0
 
-    def failure_fraction(self):
-        """f(w) = errors_by_faults[w] / shots_by_faults[w], float64 [256]; NaN where no shot had w faults."""
-        s = self.shots_by_faults.astype(np.float64)
-        return np.divide(self.errors_by_faults.astype(np.float64), s, out=np.full(s.shape, np.nan), where=s > 0)
-
     @classmethod
     def from_counts(cls, hist, counts, lightest, seed=0, batch=0, seconds=0.0):
         """From decoder.device.FaultStats.result(): hist int64 [3, 256], counts = (shots, failing, shots with H C != det, failing ones of those)."""
@@ -523,7 +600,7 @@ class FaultSpectrumResult:
         if int(h[0].sum()) != shots or int(h[1].sum()) != errors or int(h[2].sum()) != errors - int(c[3]):
             raise ValueError("fault histograms and counters disagree: %d / %d / %d shots in the histograms, counters %s"
                              % (h[0].sum(), h[1].sum(), h[2].sum(), c.tolist()))
-        return cls(shots, errors, errors / shots if shots else float("nan"), h[0].copy(), h[1].copy(), h[2].copy(), int(c[2]), int(c[3]),
+        return cls(shots, errors, _rate(shots, errors)[0], h[0].copy(), h[1].copy(), h[2].copy(), int(c[2]), int(c[3]),
                    None if lightest is None else (int(lightest[0]), int(lightest[1])), int(seed), int(batch), float(seconds))
 
 
@@ -540,57 +617,30 @@ def get_fault_spectrum(circuit, hz, lz, W, F, num_trials, max_iter=2, osd_order=
 
     Returns a FaultSpectrumResult; `replay_faults(circuit, [result.lightest[1]], seed)` regenerates the lightest residual's fault set."""
     import time
-    import warnings
-    from . import _lib
-    from .decoder.base import detector_error_model_to_matrix, window_count
-    from .decoder.bposd import BpOsdDecoder
-    from .decoder.plan import cached_circuit_plan
-    if F == 0:
-        raise ValueError("Input parameter F cannot be zero.")
-    _lib.require_faults(_lib.require_experiment(_lib.require_gpu()))
     import torch
-    from .decoder.device import DemSampler, FaultStats, GF2Matrix, Tally
+    from .decoder.device import FaultStats, GF2Matrix, Tally
+    decoder, opts = _decoder_choice(None, max_iter, osd_order, bp_method, schedule, osd_method)
     rank, world = (0, 1) if shard is None else (int(shard[0]), int(shard[1]))
-    circ = _as_circuit(circuit)
-    H, L, priors = detector_error_model_to_matrix(circ.detector_error_model())
-    smp = DemSampler(H, L, priors)
-    nz = hz.shape[0]
-    num_rounds = smp.m // nz - 2
-    if window_count(num_rounds, W, F)[2]:
-        warnings.warn("Window size larger than the syndrome extraction rounds: Doing whole history correction")
-    opts = {'bp_method': bp_method, 'max_iter': max_iter, 'schedule': schedule, 'osd_method': osd_method, 'osd_order': osd_order}
-    plan = cached_circuit_plan(circ, hz, W, F, num_rounds, BpOsdDecoder, BpOsdDecoder, opts, opts)
-    k = plan.nobs
-    if smp.nobs != k or np.asarray(lz.shape)[0] != k:
-        raise ValueError("the circuit has %d observables, lz %d rows, the window plan commits %d" % (smp.nobs, lz.shape[0], k))
-    if plan.nfaults != smp.nfaults:
-        raise ValueError("the windows commit %d faults, the detector error model has %d" % (plan.nfaults, smp.nfaults))
-    if batch is None:
-        batch = max(2, int(plan.lanes) if plan.pipeline else 2) * int(plan.chunk)
-    batches = experiment_batches(num_trials, batch, rank, world)
+    su = _experiment_setup(circuit, hz, lz, W, F, decoder, opts, ("experiment", "faults"), sampler="dem", columns=True, batch=batch)
+    smp, plan = su.sampler, su.plan
+    batches = experiment_batches(num_trials, su.batch, rank, world)
     if batches and batches[-1][0] + batches[-1][1] > 1 << 40:
         raise ValueError("shot indices must stay below 2^40")
-    Hdev = GF2Matrix(H)
-    words = (plan.nfaults + 31) // 32
+    Hdev = GF2Matrix(su.H)
     with plan.in_use():
-        tally, fstats = Tally(k), FaultStats()
+        tally, fstats = Tally(plan.nobs), FaultStats()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for shot0, n in batches:
             det, obs, faults = smp.sample_faults(n, seed, shot0)
-            corr = torch.empty((n, words), dtype=torch.int32, device="cuda")
-            pred = plan.decode(det, None, corr)
-            mask = torch.empty(((n + 63) // 64,), dtype=torch.int64, device="cuda")
-            tally.add(pred, obs, None, mask)
-            Hdev.xor_apply(corr, det, accumulate=True)         # det is this batch's own: it becomes the residual H C xor det in place
-            fstats.add(faults, corr, plan.nfaults, det, mask, shot0)
+            su.decode_stats(Hdev, tally, fstats, det, obs, faults, shot0)
         torch.cuda.synchronize()
         seconds = time.perf_counter() - t0
         hist, counts, lightest = fstats.result()
         tc = tally.counts()
     if int(tc[0]) != int(counts[0]) or int(tc[1]) != int(counts[1]):
         raise RuntimeError("the tally counted %d shots and %d failures, the fault statistics %d and %d" % (tc[0], tc[1], counts[0], counts[1]))
-    return FaultSpectrumResult.from_counts(hist, counts, lightest, seed, _batch_step(batch), seconds)
+    return FaultSpectrumResult.from_counts(hist, counts, lightest, seed, su.step, seconds)
 
 
 def replay_faults(circuit, shot_indices, seed):
@@ -600,13 +650,12 @@ def replay_faults(circuit, shot_indices, seed):
     from . import _lib
     _lib.require_faults(_lib.require_experiment(_lib.require_gpu()))
     smp = _make_sampler(_as_circuit(circuit), "dem")
-    bits = smp.sample_shots_faults(shot_indices, int(seed))[2].cpu().numpy()
-    return np.unpackbits(np.ascontiguousarray(bits).view(np.uint8), axis=1, bitorder="little")[:, :smp.nfaults].astype(bool)
+    return _fault_rows(smp.sample_shots_faults(shot_indices, int(seed))[2], smp.nfaults)
 
 
 # ---- the same experiment, stratified by the number of faults -----------------------------------------------------------------------------
 @dataclasses.dataclass
-class StratifiedResult:
+class StratifiedResult(_ByFaults):
     """What `get_stratified_pL` returns.  shots_by_faults[k], errors_by_faults[k] (int64 [256]): shots drawn with exactly k faults and the
     failing ones among them; pmf[k] = P(|E| = k) under the detector error model (float64 [256]), tail = P(|E| > 255).
     pL = sum over the sampled k of pmf_k f_k, f_k = errors_k / shots_k; sigma = sqrt(sum pmf_k^2 f_k (1 - f_k) / shots_k);
@@ -632,11 +681,6 @@ class StratifiedResult:
     batch: int = 0
     seconds: float = 0.0
     sigma_max: float = 0.0
-
-    def failure_fraction(self):
-        """f(k) = errors_by_faults[k] / shots_by_faults[k], float64 [256]; NaN where stratum k has no shots."""
-        s = self.shots_by_faults.astype(np.float64)
-        return np.divide(self.errors_by_faults.astype(np.float64), s, out=np.full(s.shape, np.nan), where=s > 0)
 
     @classmethod
     def from_counts(cls, shots_by_faults, errors_by_faults, pmf, tail, residual_weight_hist=None, residual_shots=0, failing_residual_shots=0,
@@ -681,39 +725,15 @@ def get_stratified_pL(circuit, hz, lz, W, F, shots_per_weight, max_iter=2, osd_o
 
     Returns a StratifiedResult."""
     import time
-    import warnings
+    import torch
     from . import _lib
     from . import strata as st
-    from .decoder.base import detector_error_model_to_matrix, window_count
-    from .decoder.bposd import BpOsdDecoder
-    from .decoder.plan import cached_circuit_plan
-    if F == 0:
-        raise ValueError("Input parameter F cannot be zero.")
-    todo = _strata_plan(shots_per_weight)
-    _lib.require_strata(_lib.require_faults(_lib.require_experiment(_lib.require_gpu())))
-    import torch
-    from .decoder.device import FaultStats, GF2Matrix, StratifiedDemSampler, Tally
-    circ = _as_circuit(circuit)
-    H, L, priors = detector_error_model_to_matrix(circ.detector_error_model())
-    pmf, tail = st.fault_count_pmf(priors, st.KMAX_LIMIT)
-    smp = StratifiedDemSampler(H, L, priors, max([k for k, _ in todo], default=0))
-    if todo:
-        st.check_ks(np.array([k for k, _ in todo]), len(todo), priors, smp.kmax)
-    nz = hz.shape[0]
-    num_rounds = smp.m // nz - 2
-    if window_count(num_rounds, W, F)[2]:
-        warnings.warn("Window size larger than the syndrome extraction rounds: Doing whole history correction")
-    opts = {'bp_method': bp_method, 'max_iter': max_iter, 'schedule': schedule, 'osd_method': osd_method, 'osd_order': osd_order}
-    plan = cached_circuit_plan(circ, hz, W, F, num_rounds, BpOsdDecoder, BpOsdDecoder, opts, opts)
-    nobs = plan.nobs
-    if smp.nobs != nobs or np.asarray(lz.shape)[0] != nobs:
-        raise ValueError("the circuit has %d observables, lz %d rows, the window plan commits %d" % (smp.nobs, lz.shape[0], nobs))
-    if plan.nfaults != smp.nfaults:
-        raise ValueError("the windows commit %d faults, the detector error model has %d" % (plan.nfaults, smp.nfaults))
-    if batch is None:
-        batch = max(2, int(plan.lanes) if plan.pipeline else 2) * int(plan.chunk)
-    Hdev = GF2Matrix(H)
-    words = (plan.nfaults + 31) // 32
+    from .decoder.device import FaultStats, GF2Matrix, Tally
+    decoder, opts = _decoder_choice(None, max_iter, osd_order, bp_method, schedule, osd_method)
+    su = _experiment_setup(circuit, hz, lz, W, F, decoder, opts, ("experiment", "faults"), columns=True, strata=shots_per_weight, batch=batch)
+    smp, plan, todo = su.sampler, su.plan, su.strata
+    pmf, tail = st.fault_count_pmf(su.priors, st.KMAX_LIMIT)
+    Hdev = GF2Matrix(su.H)
     shots_by = np.zeros(_lib.FAULT_HIST, np.int64)
     errors_by = np.zeros(_lib.FAULT_HIST, np.int64)
     rw = np.zeros(_lib.FAULT_HIST, np.int64)
@@ -724,15 +744,10 @@ def get_stratified_pL(circuit, hz, lz, W, F, shots_per_weight, max_iter=2, osd_o
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for k, nk in todo:
-            tally, fstats = Tally(nobs), FaultStats()                  # per stratum: the lightest residual is then known with its k
-            for shot0, n in experiment_batches(nk, batch):
+            tally, fstats = Tally(plan.nobs), FaultStats()             # per stratum: the lightest residual is then known with its k
+            for shot0, n in experiment_batches(nk, su.batch):
                 det, obs, faults = smp.sample_faults(k, seed, shot0, shots=n)
-                corr = torch.empty((n, words), dtype=torch.int32, device="cuda")
-                pred = plan.decode(det, None, corr)
-                mask = torch.empty(((n + 63) // 64,), dtype=torch.int64, device="cuda")
-                tally.add(pred, obs, None, mask)
-                Hdev.xor_apply(corr, det, accumulate=True)             # det becomes the residual H C xor det in place
-                fstats.add(faults, corr, plan.nfaults, det, mask, shot0)
+                su.decode_stats(Hdev, tally, fstats, det, obs, faults, shot0)
             strata_stats.append((k, nk, tally, fstats))
         torch.cuda.synchronize()
         seconds = time.perf_counter() - t0
@@ -750,7 +765,7 @@ def get_stratified_pL(circuit, hz, lz, W, F, shots_per_weight, max_iter=2, osd_o
             fail_res_shots += int(counts[3])
             if best is not None and (lightest is None or best[0] < lightest[0]):
                 lightest = (int(best[0]), k, int(best[1]))
-    return StratifiedResult.from_counts(shots_by, errors_by, pmf, tail, rw, res_shots, fail_res_shots, lightest, seed, _batch_step(batch), seconds)
+    return StratifiedResult.from_counts(shots_by, errors_by, pmf, tail, rw, res_shots, fail_res_shots, lightest, seed, su.step, seconds)
 
 
 def replay_strata_faults(circuit, k, shot_indices, seed):
@@ -762,8 +777,7 @@ def replay_strata_faults(circuit, k, shot_indices, seed):
     _lib.require_strata(_lib.require_faults(_lib.require_gpu()))
     H, L, priors = detector_error_model_to_matrix(_as_circuit(circuit).detector_error_model())
     smp = StratifiedDemSampler(H, L, priors, int(k))
-    bits = smp.sample_shots_faults(shot_indices, int(k), int(seed))[2].cpu().numpy()
-    return np.unpackbits(np.ascontiguousarray(bits).view(np.uint8), axis=1, bitorder="little")[:, :smp.nfaults].astype(bool)
+    return _fault_rows(smp.sample_shots_faults(shot_indices, int(k), int(seed))[2], smp.nfaults)
 
 
 # ---- failing fault sets shrunk to 1-minimal ones ------------------------------------------------------------------------------------------
@@ -820,27 +834,6 @@ def _decoder_choice(relay, max_iter, osd_order, bp_method, schedule, osd_method)
     return RelayBpDecoder, relay_options(relay, 'osd_off' if osd_method is None else osd_method, osd_order)
 
 
-def _fault_model_plan(circuit, hz, lz, W, F, decoder, opts):
-    """(Circuit, H, L, priors, cached plan) of a circuit's detector error model, checked as get_fault_spectrum checks them."""
-    import warnings
-    from .decoder.base import detector_error_model_to_matrix, window_count
-    from .decoder.plan import cached_circuit_plan
-    if F == 0:
-        raise ValueError("Input parameter F cannot be zero.")
-    circ = _as_circuit(circuit)
-    H, L, priors = detector_error_model_to_matrix(circ.detector_error_model())
-    nz = hz.shape[0]
-    num_rounds = H.shape[0] // nz - 2
-    if window_count(num_rounds, W, F)[2]:
-        warnings.warn("Window size larger than the syndrome extraction rounds: Doing whole history correction")
-    plan = cached_circuit_plan(circ, hz, W, F, num_rounds, decoder, decoder, opts, opts)
-    if L.shape[0] != plan.nobs or np.asarray(lz.shape)[0] != plan.nobs:
-        raise ValueError("the circuit has %d observables, lz %d rows, the window plan commits %d" % (L.shape[0], lz.shape[0], plan.nobs))
-    if plan.nfaults != H.shape[1]:
-        raise ValueError("the windows commit %d faults, the detector error model has %d" % (plan.nfaults, H.shape[1]))
-    return circ, H, L, priors, plan
-
-
 def _shrink_on_plan(plan, shr, sets, batch, timing=None):
     """The one loop of shrink_fault_sets and get_minimal_failures (inside plan.in_use()): `shr`, a decoder.device.FaultShrinker, walks the packed
     `sets`; every round's trial rows are decoded by `plan` in pieces of `batch` rows and tallied, and the fail mask goes back to the shrinker.
@@ -888,10 +881,6 @@ def _shrink_on_plan(plan, shr, sets, batch, timing=None):
     return decodes
 
 
-def _default_batch(plan):
-    return max(2, int(plan.lanes) if plan.pipeline else 2) * int(plan.chunk)
-
-
 def shrink_fault_sets(circuit, hz, lz, W, F, fault_sets, max_iter=2, osd_order=0, bp_method='product_sum', schedule='serial', osd_method=None,
                       *, relay=None, batch=None):
     """Shrink fault sets of the circuit's detector error model to 1-minimal failing ones (quits_amd/shrink.py states the walk): a set S fails
@@ -905,14 +894,12 @@ def shrink_fault_sets(circuit, hz, lz, W, F, fault_sets, max_iter=2, osd_order=0
 
     Returns a quits_amd.shrink.ShrinkResult: sets in the form they came in (packed ones as numpy), fails, minimal, start_weight, weight,
     trials per parent.  A parent that does not fail comes back unchanged with fails = False."""
-    from . import _lib
-    from . import shrink as sk
-    decoder, opts = _decoder_choice(relay, max_iter, osd_order, bp_method, schedule, osd_method)
-    _lib.require_shrink(_lib.require_faults(_lib.require_experiment(_lib.require_gpu())))
     import torch
+    from . import shrink as sk
     from .decoder.device import FaultShrinker
-    circ, H, L, priors, plan = _fault_model_plan(circuit, hz, lz, W, F, decoder, opts)
-    n, words = plan.nfaults, (plan.nfaults + 31) // 32
+    decoder, opts = _decoder_choice(relay, max_iter, osd_order, bp_method, schedule, osd_method)
+    su = _experiment_setup(circuit, hz, lz, W, F, decoder, opts, ("experiment", "faults", "shrink"), columns=True, batch=batch)
+    plan, n, words = su.plan, su.plan.nfaults, su.words
     packed_in = isinstance(fault_sets, torch.Tensor) or (np.asarray(fault_sets).dtype != np.bool_ and np.asarray(fault_sets).ndim == 2
                                                          and np.asarray(fault_sets).shape[1] != n)
     if packed_in:
@@ -924,9 +911,9 @@ def shrink_fault_sets(circuit, hz, lz, W, F, fault_sets, max_iter=2, osd_order=0
         if bits.ndim != 2 or bits.shape[1] != n:
             raise ValueError("fault_sets must be a [parents, %d] array, one column per fault of the detector error model" % n)
         sets = sk.pack_sets(bits != 0)
-    shr = FaultShrinker(H, L)
+    shr = FaultShrinker(su.H, su.L)
     with plan.in_use():
-        _shrink_on_plan(plan, shr, sets, _default_batch(plan) if batch is None else batch)
+        _shrink_on_plan(plan, shr, sets, su.batch)
         res = shr.result()
     if not packed_in:
         res.sets = sk.unpack_sets(res.sets, n)
@@ -973,33 +960,23 @@ def _minimal_failures(circuit, hz, lz, W, F, num_trials, decoder, opts, *, seed,
     """The loop of get_minimal_failures and get_relay_minimal_failures: `decoder` is the plug-in class of both window kinds, `opts` its keyword
     dict (the cached plan's key)."""
     import time
+    import torch
     from . import _lib
-    from . import strata as st
+    from .decoder.device import FaultShrinker, FaultStats, Tally
     t_start = time.perf_counter()
-    todo = None if shots_per_weight is None else _strata_plan(shots_per_weight)
     if int(max_parents) < 0 or int(keep_sets) < 0:
         raise ValueError("max_parents and keep_sets must not be negative")
-    _lib.require_shrink(_lib.require_faults(_lib.require_experiment(_lib.require_gpu())))
-    if todo is not None:
-        _lib.require_strata(_lib.load())
-    import torch
-    from .decoder.device import DemSampler, FaultShrinker, FaultStats, StratifiedDemSampler, Tally
-    circ, H, L, priors, plan = _fault_model_plan(circuit, hz, lz, W, F, decoder, opts)
-    nobs, nfaults, words = plan.nobs, plan.nfaults, (plan.nfaults + 31) // 32
-    if batch is None:
-        batch = _default_batch(plan)
-    step = _batch_step(batch)
+    su = _experiment_setup(circuit, hz, lz, W, F, decoder, opts, ("experiment", "faults", "shrink"), sampler="dem", columns=True,
+                           strata=shots_per_weight, batch=batch)
+    smp, plan, todo, batch, step, words = su.sampler, su.plan, su.strata, su.batch, su.step, su.words
+    nobs = plan.nobs
     if todo is None:
-        smp = DemSampler(H, L, priors)
         work = [(None, shot0, n) for shot0, n in experiment_batches(num_trials, batch)]
     else:
-        smp = StratifiedDemSampler(H, L, priors, max([k for k, _ in todo], default=0))
-        if todo:
-            st.check_ks(np.array([k for k, _ in todo]), len(todo), priors, smp.kmax)
         work = [(k, shot0, n) for k, nk in todo for shot0, n in experiment_batches(nk, batch)]
     if work and max(shot0 + n for _, shot0, n in work) > 1 << 40:
         raise ValueError("shot indices must stay below 2^40")
-    shr = FaultShrinker(H, L)
+    shr = FaultShrinker(su.H, su.L)
     timing = {}
     with plan.in_use():
         tally = Tally(nobs)
@@ -1029,13 +1006,8 @@ def _minimal_failures(circuit, hz, lz, W, F, num_trials, decoder, opts, *, seed,
         fstats, final = FaultStats(), Tally(nobs)
         for c0 in range(0, P, step):
             n = min(step, P - c0)
-            det = shr.kept_det[c0:c0 + n].clone()
-            corr = torch.empty((n, words), dtype=torch.int32, device="cuda")
-            pred = plan.decode(det, None, corr)
-            mask = torch.empty(((n + 63) // 64,), dtype=torch.int64, device="cuda")
-            final.add(pred, shr.kept_obs[c0:c0 + n], None, mask)
-            shr.H.xor_apply(corr, det, accumulate=True)            # det becomes the residual H C xor H S in place
-            fstats.add(shr.sets[c0:c0 + n], corr, nfaults, det, mask, c0)
+            det = shr.kept_det[c0:c0 + n].clone()                  # a copy: the step turns it into the residual H C xor H S
+            su.decode_stats(shr.H, final, fstats, det, shr.kept_obs[c0:c0 + n], shr.sets[c0:c0 + n], c0)
         torch.cuda.synchronize()
         t3 = time.perf_counter()
         tc = tally.counts()
