@@ -1,7 +1,7 @@
 // bp_scatter_edge.h -- the per-edge steps of the scatter form of flooding min-sum (gather pass: QS_EDGE_M / QS_EDGE_K, scatter pass: QS_SCAT) of
 // qd_bp_scatter_wide_kernel and qd_bp_first_pass_kernel (bp_scatter_wide.hip, bp_scatter_wide_walk.inc).
 // The macros work on the enclosing scope's names: s1, s2 (what the check sent last), a1, a2, ltw, neww, hp (what this pass
-// collects), dc (the check's degree), pdif, pxq, own, xw (scatter pass).
+// collects), dc (the check's degree), n1, nx, own (scatter pass).  qs_reset_to_priors: the one copy of "accumulators := priors".
 #pragma once
 #include "qd_internal.h"
 #include <float.h>
@@ -116,16 +116,32 @@ __device__ __forceinline__ float qs_min_f32(float a, float b)       // no canoni
 
 // the scatter pass's one LDS operation per edge (a plain read, a plain store, an add of a constant or nothing in its place: profiles/r05_k1sw_ablation_bounds.txt)
 #define QS_ADD(off, v_) (void)__hip_atomic_fetch_add(QS_LDS(off), v_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-// Scatter pass, one edge: (new message) - (message sent in the last iteration) = sn a - so b with a, b = min1 of the two passes
-// (the argmin edges are corrected after the loop) and sn, so = +-1 the outgoing signs: sn (a - b) where the signs agree, sn (a + b)
-// where they differ.  `own` holds the new signs, `xw` = new ^ sent, edge i of the group at bit 31 - i; pdif = a - b, pxq = (a - b) ^ (a + b).
+// Scatter pass, one edge.  The accumulators stand at the priors when the pass begins (qs_reset_to_priors below), so an edge adds its new message
+// and nothing else: +-min1 (the argmin edge is corrected after the loop).  `own` holds the new outgoing signs, edge k of the word at bit_;
+// n1 = min1, nx = n1 ^ -n1 (once per check): n1 ^ (nx & sign mask) is n1 or -n1.  Two vector instructions and the LDS add.
 #define QS_SCAT(off, k_, bit_, TAILFIX)                                                                      \
     {                                                                                                        \
-        const int dm_ = __builtin_amdgcn_sbfe((int)xw, bit_, 1), sm_ = __builtin_amdgcn_sbfe((int)own, bit_, 1); \
-        const int mg_ = (int)__builtin_amdgcn_bitop3_b32((uint32_t)pdif, (uint32_t)pxq, (uint32_t)dm_, 0x78);   /* pdif ^ (pxq & dm) */ \
-        int v_ = (mg_ ^ sm_) - sm_;                                                                          \
+        const int sm_ = __builtin_amdgcn_sbfe((int)own, bit_, 1);                                            \
+        int v_ = (int)__builtin_amdgcn_bitop3_b32((uint32_t)n1, (uint32_t)nx, (uint32_t)sm_, 0x78);          /* n1 ^ (nx & sm) */ \
         TAILFIX(v_, k_)                                                                                      \
         QS_ADD(off, v_)                                                                                      \
     }
 #define QS_TAILZERO(v_, k_) v_ = ((int)(k_) < dc) ? v_ : 0;
+
+// Accumulators := priors (minus one), trash slots := 0: the image ScatArgs::prior_g, a constant of the decoder, copied into the accumulator region
+// without passing through registers -- global_load_lds_dwordx4, 1 KB per wavefront instruction (the LDS destination is a wave-uniform base + 16 bytes
+// per lane), the pieces dealt over the workgroup's NW wavefronts.  `nslots` is a multiple of 32 (graph_layout.hip: 32 banks), so the region is whole
+// 16-byte units; in the last, partial piece the lanes beyond the region are switched off, so nothing is read behind prior_g and nothing is written
+// behind the region (the output words follow it).  The copies are in flight when this returns: they count on vmcnt, and the caller's __syncthreads()
+// waits for them (the compiler puts vmcnt(0) in front of a barrier while a load into LDS is pending) before any wavefront touches the region.
+template <int NW>
+__device__ __forceinline__ void qs_reset_to_priors(const int32_t *prior_g, uint32_t offA, int nslots, int tid)
+{
+    const int nbytes = nslots * 4;
+    const int lane16 = (tid & 63) * 16;
+    for (int p = __builtin_amdgcn_readfirstlane(tid >> 6) * 1024; p < nbytes; p += NW * 1024)
+        if (p + lane16 < nbytes)
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(reinterpret_cast<const char *>(prior_g) + p + lane16),
+                                             (__attribute__((address_space(3))) void *)(uintptr_t)(offA + (uint32_t)p), 16, 0, 0);
+}
 

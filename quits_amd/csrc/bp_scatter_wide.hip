@@ -11,7 +11,7 @@
 // rebuilding every check's message from the check's packed state).  On the grid every message is an integer multiple of 2^-k, so a
 // posterior is an INTEGER sum -- and integer LDS atomics run at the rate of a 4-byte gather (ds_add_u32: 2.2 ns per wavefront
 // instruction per CU, scattered addresses; ds_add_f32: 80 ns, profiles/r03z_lds_atomic_rates.txt).  So the check that has just
-// computed (min1, min2, argmin, signs) adds +-min1 to each of its faults' accumulators itself (one sign mask, one xor, one subtract,
+// computed (min1, min2, argmin, signs) adds +-min1 to each of its faults' accumulators itself (one sign mask, one v_bitop3,
 // one ds_add_u32 per edge), corrects the argmin fault by +-(min2 - min1), and the bit pass is gone.  The check state never leaves the
 // lane, so the LDS holds one int32 accumulator per fault and nothing per check: 38 KB + 2 KB at the headline window, 76 KB for a QLP
 // window of BASELINE configs[4] where qd_bp_minsum_kernel needs 112 KB (ONE workgroup of 1024 threads per CU; here two: BP 36.8 ->
@@ -32,9 +32,15 @@
 // two barriers.
 //
 // One iteration = [gather pass of check 0 .. CPL-1 over L(t): new minima and signs, and the syndrome of L(t)'s hard decision] barrier
-// [converged? | scatter pass of check 0 .. CPL-1] barrier.  The scatter pass works in place: every gather of the iteration precedes
-// every add, and each edge's accumulator moves by (new message) - (message sent last time), so L(t+1) = prior + sum of the new messages
-// without a second buffer and without a reset.  An accumulator holds L - 1, so that (L <= 0) is its sign bit: a check gets the parity
+// [converged? | accumulators := priors] barrier [scatter pass of check 0 .. CPL-1] barrier.  Every gather of the iteration precedes
+// the vote's barrier, so behind it the one buffer can go back to the priors (qs_reset_to_priors, bp_scatter_edge.h: the decoder's
+// constant image ScatArgs::prior_g, L2-resident and shared by every shot, copied by global_load_lds_dwordx4 without passing through
+// registers; the prologue's fill is the same routine), and behind the second barrier an edge adds its new message and nothing else:
+// L(t+1) = prior + sum of the new messages, the integer the in-place form (each accumulator moved by new message - message sent
+// last time: five vector instructions per edge, a second atomic per check for the old argmin edge) arrived at.  Two vector
+// instructions per edge; the price is 4 bytes of L2 traffic per slot and iteration and the third barrier
+// (profiles/bp_scatter_reset_ab.txt).  The reset waits for the vote: a shot that has converged, or has run its last iteration, keeps
+// L(t) in the buffer for the epilogue.  An accumulator holds L - 1, so that (L <= 0) is its sign bit: a check gets the parity
 // of its faults' hard decisions with one XOR per edge, and (bit->check message <= 0) is the sign bit of the difference it computes anyway.
 //
 // Exactness.  Integer accumulation cannot round; what must not round are the float operations of the gather
@@ -95,10 +101,15 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
             dcs[j] = sg.chk_deg[c];
         }
     }
-    {
-        int32_t *bA = reinterpret_cast<int32_t *>(smem + sg.offA);
-        for (int b = tid; b < sg.nslots; b += T) bA[b] = x.prior_g[b];                 // (unused slots and the trash slots of the short rows hold 0 and stay 0)
+    // per wavefront and round: trip count | largest degree << 8 | smallest << 16 (scalar); a round whose 64 slots lie beyond the window has 0
+    // (read in front of the fill: behind a load that writes LDS the compiler no longer takes a global load for a scalar one)
+    int dws[CPL];
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) {
+        const int wslot = __builtin_amdgcn_readfirstlane(cs[j] >> 6);
+        dws[j] = wslot >= 0 ? (int)sg.deg_w[wslot] : 0;
     }
+    qs_reset_to_priors<NW>(x.prior_g, (uint32_t)sg.offA, sg.nslots, tid);               // (unused slots and the trash slots of the short rows hold 0 there)
     for (int w = tid; w < g.out_words; w += T) outw[w] = 0u;
     __syncthreads();
     any = qd_block_or(any, misc, NW, 0);
@@ -107,24 +118,13 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
         if (tid == 0) a.status[shot] = QD_STATUS_CONVERGED | QD_STATUS_ZERO | a.status_or;
         return;
     }
-
-    // per wavefront and round: trip count | largest degree << 8 | smallest << 16 (scalar); a round whose 64 slots lie beyond the window has 0
-    int dws[CPL];
-#pragma unroll
-    for (int j = 0; j < CPL; ++j) {
-        const int wslot = __builtin_amdgcn_readfirstlane(cs[j] >> 6);
-        dws[j] = wslot >= 0 ? (int)sg.deg_w[wslot] : 0;
-    }
     // check state, in registers: what each check SENT in the last scatter pass (the two minima, the position of the argmin edge, the
     // outgoing signs: edge k of a word of kend edges at bit kend - 1 - k) and what the gather pass of this iteration found
     float S1[CPL], S2[CPL], A1[CPL], A2[CPL], mx2 = 0.f;
     uint32_t KOLD[CPL], KST[CPL], O[CPL][NSW], Q[CPL][NSW];
     [[maybe_unused]] uint32_t cmpf = 0u;                // bit j: round j of this wavefront walks in the compare form from now on (two-word shapes; see the gather pass)
-    uint32_t FOFF[CPL];                                 // where and what the last scatter pass added for its argmin edge (min2 - min1, signed): given back by the next
-    int FVAL[CPL];
 #pragma unroll
     for (int j = 0; j < CPL; ++j) {
-        FOFF[j] = (uint32_t)sg.offA + (uint32_t)(sg.nslots - 32 + (tid & 31)) * 4u; FVAL[j] = 0;      // (a trash slot)
         S1[j] = 0.f; S2[j] = 0.f; A1[j] = FLT_MAX; A2[j] = FLT_MAX; KOLD[j] = 0xFFFFFFFFu; KST[j] = 0u;
 #pragma unroll
         for (int w = 0; w < NSW; ++w) { O[j][w] = 0u; Q[j][w] = 0u; }
@@ -233,9 +233,14 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
         QSW_VOTE(us, anyun)
         if (t >= 1 && !anyun) { converged = 1; break; }
         if (t == a.max_iter) break;
+        // ---- reset: every read of the pass lies before the vote's barrier, and the accumulators are not the result (both tests above say so), so
+        // they go back to the priors; no add may be issued before every wavefront's copies have landed: a second barrier.  (Where `have` skips the
+        // gather pass -- the fast start -- the prologue's fill is still there.)
+        qs_reset_to_priors<NW>(x.prior_g, cur, sg.nslots, tid);
+        __syncthreads();
       }
         have = false;
-        // ---- scatter pass, in place: each edge's accumulator moves by (new message) - (message sent last time)
+        // ---- scatter pass over the priors: each edge adds its new message
         __builtin_amdgcn_s_setprio(QS_PRIO);
 #pragma unroll
         for (int j = 0; j < CPL; ++j) {
@@ -259,8 +264,7 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
                 const int trip = dwj & 0xFF, wmax = (dwj >> 8) & 0xFF, wmin = (dwj >> 16) & 0xFF, wmin4 = wmin & ~3;
                 const int adj_voff = cs[j] * 16;
                 const int dc = dcs[j];
-                const int n1i = (int)A1[j], s1i = (int)S1[j];
-                const int pdif = n1i - s1i, pxq = pdif ^ (n1i + s1i);
+                const int n1 = (int)A1[j], nx = n1 ^ -n1;
                 const uint32_t kst = KST[j];
                 const uint32_t fixn_off = __builtin_amdgcn_raw_buffer_load_b32(adj_rsrc, (int)((kst >> 2) * (uint32_t)adj_row + (kst & 3u) * 4u) + adj_voff, 0, 0);
                 const int ng = trip >> 2;
@@ -288,7 +292,7 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
                 for (int w = 0; w < NSW; ++w) {
                     if (32 * w < trip) {
                         const int kendw = min(trip - 32 * w, 32);
-                        const uint32_t own = Q[j][w], xw = Q[j][w] ^ O[j][w];
+                        const uint32_t own = Q[j][w];
                         const int g1 = min(ng, 8 * w + 8);                    // groups of this word: [8 w, g1)
                         const int gp = min(g1, max(wmin4 >> 2, 8 * w));       // ... of which [8 w, gp) are plain (as in the gather pass: three loops, no test per group)
                         uint4 ea = (j == 0 && w == 0) ? pf : QS_ADJ(8 * w), eb;
@@ -319,19 +323,16 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
 #undef QS_GROUP_TAIL
 #undef QS_SCAT_TAIL
 #undef QS_GROUP_POS
-                // the argmin edges carry min2, not min1: the new one gains +-(min2 - min1), the old one gives its own back
+                // the argmin edge carries min2, not min1: it gains +-(min2 - min1)
                 {
                     const int kw = (int)(kst >> 5), kendw = min(trip - 32 * kw, 32);
                     uint32_t wd = Q[j][0];
 #pragma unroll
                     for (int w = 1; w < NSW; ++w) wd = (kw == w) ? Q[j][w] : wd;
                     const uint32_t sg_ = (wd >> (kendw - 1 - (int)(kst & 31u))) & 1u;
-                    const int dlt = (int)A2[j] - n1i;
+                    const int dlt = (int)A2[j] - n1;
                     const int vn = sg_ ? -dlt : dlt;
                     (void)__hip_atomic_fetch_add(QS_LDS(fixn_off), vn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    // ... which is exactly what the last pass added for ITS argmin edge, kept from then (0 at the trash slot before any message was sent)
-                    (void)__hip_atomic_fetch_add(QS_LDS(FOFF[j]), -FVAL[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    FOFF[j] = fixn_off; FVAL[j] = vn;
                 }
             }
             S1[j] = A1[j]; S2[j] = A2[j]; KOLD[j] = KST[j];

@@ -123,16 +123,17 @@ def main():
         print("\n# gather pass, innermost loop (%d edges per trip; counts per 4 edges): " % ne + ", ".join("%s %.1f" % (k, v) for k, v in c.items() if v))
         print("#   per edge: %.2f fast + %.2f slow VALU = %.1f issue clk at 2 / 4 clk" % (c["valu_fast"] / 4, c["valu_slow"] / 4,
               (2 * c["valu_fast"] + 4 * c["valu_slow"]) / 4))
-        # the scatter pass's plain path: the block that builds three of a group's four values back to back (v_bitop3 0x78 =
-        # pdif ^ (pxq & differ-mask), no tail predicate); the fourth is computed in the loop header, the same five instructions
-        sl = [(b, cnt) for b, cnt in rows if sum("bitop3:0x78" in i for i in b["ins"]) == 3 and not any(i.startswith("v_cndmask") for i in b["ins"])]
+        # the scatter pass's plain loop: the innermost loop with the most ds_add_u32 per trip (two groups of four edges; per edge one
+        # v_bfe_i32 for the sign mask and one v_bitop3 0x78 = n1 ^ (nx & mask): the accumulators stand at the priors, an edge adds +-min1)
+        sl = [(sum(i.startswith("ds_add_u32") for i in b["ins"]), cnt) for b, cnt in rows if b["inner"]
+              and any(i.startswith("ds_add_u32") for i in b["ins"]) and not any(i.startswith("v_cndmask") for i in b["ins"])]
         if sl:
-            b, cnt = sl[0]
+            na, cnt = max(sl, key=lambda t: t[0])
             summary["scatter_pass_plain_block"] = cnt
-            summary["scatter_pass_edges_in_block"] = 3
-            print("# scatter pass, plain block (3 of a group's 4 edges): " + ", ".join("%s %d" % (k, v) for k, v in cnt.items() if v))
-            print("#   per edge: %.2f fast + %.2f slow VALU = %.1f issue clk at 2 / 4 clk" % (cnt["valu_fast"] / 3, cnt["valu_slow"] / 3,
-                  (2 * cnt["valu_fast"] + 4 * cnt["valu_slow"]) / 3))
+            summary["scatter_pass_edges_in_block"] = na
+            print("# scatter pass, plain loop (%d edges per trip): " % na + ", ".join("%s %d" % (k, v) for k, v in cnt.items() if v))
+            print("#   per edge: %.2f fast + %.2f slow VALU = %.1f issue clk at 2 / 4 clk" % (cnt["valu_fast"] / na, cnt["valu_slow"] / na,
+                  (2 * cnt["valu_fast"] + 4 * cnt["valu_slow"]) / na))
     mn = {}
     for b, cnt in rows:
         for ins in b["ins"]:
