@@ -70,6 +70,12 @@ __device__ __forceinline__ float qs_min_f32(float a, float b)       // no canoni
     asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
+__device__ __forceinline__ float qs_max_f32(float a, float b)       // likewise for the certificate's running maximum of the second minima
+{
+    float r;
+    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
 #define QS_KEY_POS0 0x3F800000u           // 1.0f
 #define QS_KEY_LIMIT 262144.0f            // 2^18
 #define QS_EDGE_K(off, k_, SGN_, TAILFIX, HP, MAG_)                                                          \

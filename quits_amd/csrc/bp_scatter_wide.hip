@@ -26,8 +26,9 @@
 //   * more checks than a workgroup has lanes, or rows of 65..96 faults (three sign words): 512 lanes x 3 checks (or 704 / 1024 x 2) --
 //     the windows of BASELINE configs[4] (QLP [[1020,136]], W = 3: 1350 checks of up to 78 faults, 18 900 faults).
 //
-// A lane's checks keep their state in registers (two minima, argmin position, the sign words, twice: what was sent and what the gather
-// pass just found).  Check slots are sorted by degree; a wavefront's 64 checks of one round are 64 consecutive slots (sg.wave_map), so
+// A lane's checks keep their state in registers (two minima, argmin position, the sign words), ONE set per check: what was sent last
+// until the gather walk commits what it found, which the scatter pass then sends.
+// Check slots are sorted by degree; a wavefront's 64 checks of one round are 64 consecutive slots (sg.wave_map), so
 // the trip count stays wave-uniform, and the rounds are dealt out so that the wavefronts of a workgroup walk equally many edges between
 // two barriers.
 //
@@ -69,7 +70,7 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
     const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)smem;
     if (lds_base != 0u) __builtin_trap();   // no static LDS in this kernel: byte offsets into smem are LDS addresses
     uint32_t *outw = reinterpret_cast<uint32_t *>(smem + sg.off_out);
-    int *misc = reinterpret_cast<int *>(smem + sg.off_misc);             // [0..31] qd_block_or, [32..47] convergence flags, [48] fail slot
+    int *misc = reinterpret_cast<int *>(smem + sg.off_misc);             // [0..31] qd_block_or, [32..35] convergence flags (one BYTE per wavefront), [48] fail slot
     constexpr int NW = T / 64;
     static_assert(T % 64 == 0 && NW <= 16, "workgroup shape");
 
@@ -81,7 +82,7 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
 
     // ---- the window syndrome (sliding_window.py:168-169), the accumulators at the priors (minus one)
     int any = 0;
-    uint32_t synd[CPL];
+    uint32_t synd[CPL];                                // the check's syndrome bit, at bit 31: where the accumulators keep the hard decision (the vote XORs the two)
     int dcs[CPL];
     bool act[CPL];
     if (tid < 64) misc[tid] = 0;
@@ -97,6 +98,7 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
             const uint32_t o = g.chk_orig[c];
             synd[j] = det[o] & 1u;
             if (upd && (int)o < a.upd_rows) synd[j] ^= upd[o] & 1u;
+            synd[j] <<= 31;
             any |= (int)synd[j];
             dcs[j] = sg.chk_deg[c];
         }
@@ -118,16 +120,28 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
         if (tid == 0) a.status[shot] = QD_STATUS_CONVERGED | QD_STATUS_ZERO | a.status_or;
         return;
     }
-    // check state, in registers: what each check SENT in the last scatter pass (the two minima, the position of the argmin edge, the
-    // outgoing signs: edge k of a word of kend edges at bit kend - 1 - k) and what the gather pass of this iteration found
-    float S1[CPL], S2[CPL], A1[CPL], A2[CPL], mx2 = 0.f;
-    uint32_t KOLD[CPL], KST[CPL], O[CPL][NSW], Q[CPL][NSW];
+    // check state, in registers, one set per check: the two minima, the position of the argmin edge, the outgoing signs (edge k of a word of
+    // kend edges at bit kend - 1 - k).  A gather walk reads what the check SENT in the last scatter pass, works on locals and commits what it
+    // found at its end (QSW_WALKED); the scatter pass sends what it finds there and nothing reads the set between the two, so the live ranges of
+    // "sent" and "found" are disjoint and there is nothing to copy back (two sets cost ten moves per wavefront-iteration, profiles/bp_per_check_ab.txt).
+    float S1[CPL], S2[CPL], mx2 = 0.f;
+    uint32_t KOLD[CPL], O[CPL][NSW];
+    uint32_t FX[CPL];                                   // LDS offset of the argmin edge's accumulator (QS_FIX_ADDR), asked for in front of the barriers the scatter pass starts behind
+#ifdef QSW_STATS
+    float P1[CPL], P2[CPL];                             // what was sent before the last commit: the statistics compare the two
+    uint32_t PK[CPL], PO[CPL][NSW];
+#endif
     [[maybe_unused]] uint32_t cmpf = 0u;                // bit j: round j of this wavefront walks in the compare form from now on (two-word shapes; see the gather pass)
 #pragma unroll
     for (int j = 0; j < CPL; ++j) {
-        S1[j] = 0.f; S2[j] = 0.f; A1[j] = FLT_MAX; A2[j] = FLT_MAX; KOLD[j] = 0xFFFFFFFFu; KST[j] = 0u;
+        S1[j] = 0.f; S2[j] = 0.f; KOLD[j] = 0xFFFFFFFFu; FX[j] = 0u;
 #pragma unroll
-        for (int w = 0; w < NSW; ++w) { O[j][w] = 0u; Q[j][w] = 0u; }
+        for (int w = 0; w < NSW; ++w) O[j][w] = 0u;
+#ifdef QSW_STATS
+        P1[j] = 0.f; P2[j] = 0.f; PK[j] = 0xFFFFFFFFu;
+#pragma unroll
+        for (int w = 0; w < NSW; ++w) PO[j][w] = 0u;
+#endif
     }
     const uint32_t cur = (uint32_t)sg.offA;
     const __amdgpu_buffer_rsrc_t adj_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)sg.adjA, 0, (g.max_rdeg_pad / 4 + 2) * m_pad * 16, 0x00020000);
@@ -136,6 +150,12 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
     // The first group of offsets of a pass (round 0, word 0) is requested BEFORE the barrier the pass starts behind: every wavefront of the workgroup
     // would otherwise begin the pass by waiting for the same L2 round trip at the same time.
 #define QS_ADJ_FIRST qs_as_uint4(__builtin_amdgcn_raw_buffer_load_b128(adj_rsrc, cs[0] * 16, 0, 0))
+    // The argmin edge's entry of the adjacency table, one dword per check and pass.  Asked for at the head of the scatter round it would be the OLDEST load
+    // in flight there, and the round's first add -- which needs only the prefetched group -- would wait for its round trip (vmcnt counts in order).  Asked
+    // for behind the gather pass, with `pf`, it lands while the workgroup stands at the vote's and the reset's barriers.
+    // (A 24-bit multiply-add: the group index is below 64 and adj_row = 16 m_pad far below 2^24 for any window whose checks fit a workgroup -- the plain
+    //  product compiles to the 64-bit v_mad_u64_u32.)
+#define QS_FIX_ADDR(j_) __builtin_amdgcn_raw_buffer_load_b32(adj_rsrc, (int)(__umul24(KOLD[j_] >> 2, (uint32_t)adj_row) + (KOLD[j_] & 3u) * 4u) + cs[j_] * 16, 0, 0)
     uint4 pf = QS_ADJ_FIRST;
     // ---- fast start.  Gather pass 0 reads the priors alone (nothing has been sent: S1 = S2 = 0, O = 0, KOLD none), so the minima, the argmin and
     // the incoming signs it finds are constants of the decoder: they come from the table qd_bp_first_pass_kernel made with the same walk.  Only `flip`
@@ -143,7 +163,7 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
     // the loop at scatter pass 0, behind the barriers of the set-up above.
     // (The table and the thin last pass behind the loop, each measured alone against the generic loop: profiles/bp_fast_start_ab.txt.)
     const bool fast = x.first_pass != nullptr && a.max_iter >= 1;
-    bool have = false;                                  // A1 / A2 / KST / Q already hold what the gather pass of this iteration would find
+    bool have = false;                                  // the state set already holds what the gather pass of this iteration would commit
     if (fast) {
 #pragma unroll
         for (int j = 0; j < CPL; ++j)
@@ -151,49 +171,52 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
                 const uint4 *rp = reinterpret_cast<const uint4 *>(x.first_pass) + 2 * cs[j];
                 const uint4 r0 = rp[0], r1 = rp[1];
                 const uint32_t negw[3] = {r0.w, r1.x, r1.y};
-                const uint32_t flip = 0u - ((synd[j] ^ r1.z) & 1u);
-                A1[j] = __uint_as_float(r0.x); A2[j] = __uint_as_float(r0.y); KST[j] = r0.z;
+                const uint32_t flip = 0u - (((synd[j] >> 31) ^ r1.z) & 1u);
+                S1[j] = __uint_as_float(r0.x); S2[j] = __uint_as_float(r0.y); KOLD[j] = r0.z; FX[j] = r1.w;     // (the record holds the entry itself)
 #pragma unroll
-                for (int w = 0; w < NSW; ++w) Q[j][w] = negw[w] ^ flip;
-                mx2 = fmaxf(mx2, A2[j]);
+                for (int w = 0; w < NSW; ++w) O[j][w] = negw[w] ^ flip;
+                mx2 = qs_max_f32(mx2, S2[j]);
             }
         have = true;
     }
-    // the convergence vote of a gather pass: one flag per wavefront, read by everybody behind the barrier the pass ends at
-#define QSW_VOTE(us_, anyun_)                                                                          \
+    // The convergence vote of a gather pass.  A lane collects syndrome ^ hard-decision parity of its rounds in the sign bit of one word `uw_` (one
+    // v_bitop3 per round, the other bits are noise); one ballot on the sign, one flag BYTE per wavefront (the bytes of the wavefronts a shape does
+    // not have stay 0 from the set-up), read by everybody behind the barrier the pass ends at: 8 or 16 bytes, one read, one or three ORs.
+#define QSW_VOTE_ROUND(uw_, synd_, hp_) uw_ = __builtin_amdgcn_bitop3_b32(uw_, synd_, hp_, 0xF6);     /* uw | (synd ^ hp) */
+#define QSW_VOTE(uw_, anyun_)                                                                          \
         {                                                                                              \
-            const unsigned long long bal = __ballot(us_);                                              \
-            if ((tid & 63) == 0) misc[32 + (tid >> 6)] = (bal != 0ull);                                \
+            const unsigned long long bal = __ballot((int)(uw_) < 0);                                   \
+            if ((tid & 63) == 0) reinterpret_cast<unsigned char *>(misc + 32)[tid >> 6] = (unsigned char)(bal != 0ull); \
         }                                                                                              \
         __syncthreads();                                                                               \
-        anyun_ = 0;                                                                                    \
-        {                                                                                              \
-            const int4 *f4 = reinterpret_cast<const int4 *>(misc + 32);                                \
-            for (int w = 0; w < (NW + 3) / 4; ++w) {                                                   \
-                const int4 v = f4[w];                                                                  \
-                anyun_ |= v.x | v.y | v.z | v.w;                                                       \
-            }                                                                                          \
+        if constexpr (NW <= 8) {                                                                       \
+            const int2 v = *reinterpret_cast<const int2 *>(misc + 32);                                 \
+            anyun_ = v.x | v.y;                                                                        \
+        } else {                                                                                       \
+            const int4 v = *reinterpret_cast<const int4 *>(misc + 32);                                 \
+            anyun_ = (v.x | v.y) | (v.z | v.w);                                                        \
         }
     int t = 0, converged = 0;
     for (;;) {
       if (!have) {
         // ---- gather pass t+1 over L(t); the parity of the hard decisions it meets is the convergence test of iteration t
-        bool us = false;
+        uint32_t us = 0u;
         if (fast && t == a.max_iter) break;      // the last pass runs behind the loop, in its thin form
 #pragma unroll
         for (int j = 0; j < CPL; ++j) {
             float a1 = FLT_MAX, a2 = FLT_MAX;
             uint32_t kst = 0u;
             QSW_GATHER_PRIO(j)          // the later gather rounds of a wavefront run at a higher priority
-            // what a walk leaves behind (hp, par, neg[]) becomes the check's new state
+            // what a walk leaves behind (a1, a2, kst, hp, par, neg[]) becomes the check's new state: the one commit, of the key walk that holds, of
+            // the compare walk, and of the compare walk behind a key walk that did not hold (which has written locals only)
             // outgoing sign on edge k = syndrome ^ (parity of all incoming signs) ^ incoming sign k
 #define QSW_WALKED                                                                                     \
                 {                                                                                      \
-                    const uint32_t flip = 0u - ((synd[j] ^ (uint32_t)__popc(par)) & 1u);               \
+                    const uint32_t flip = 0u - ((uint32_t)__popc(par ^ synd[j]) & 1u);                 \
                     _Pragma("unroll")                                                                  \
-                    for (int w = 0; w < NSW; ++w) Q[j][w] = neg[w] ^ flip;                             \
-                    mx2 = fmaxf(mx2, a2);                                                              \
-                    us = us || (((synd[j] ^ (hp >> 31)) & 1u) != 0u);                                  \
+                    for (int w = 0; w < NSW; ++w) O[j][w] = neg[w] ^ flip;                             \
+                    mx2 = qs_max_f32(mx2, a2);                                                         \
+                    QSW_VOTE_ROUND(us, synd[j], hp)                                                    \
                 }
             // Rows of at most 64 faults walk in the key form (bp_scatter_edge.h: QS_EDGE_K), which is exact where every check's second key stays below
             // 2^18, i.e. min2 < 2^18 - 1.  Where a round's walk ends at or above that (late iterations of shots that do not converge: 2.1 % of the headline's
@@ -203,6 +226,9 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
             if constexpr (NSW == 2) cmpw = __builtin_amdgcn_ballot_w64((cmpf >> j) & 1u) != 0ull;       // (wave-uniform: set for all of a round's lanes or none)
 #ifdef QSW_STATS
             if ((tid & 63) == 0 && __ballot(act[j])) atomicAdd(&a.dbg[14], 1ull);
+            P1[j] = S1[j]; P2[j] = S2[j]; PK[j] = KOLD[j];
+#pragma unroll
+            for (int w = 0; w < NSW; ++w) PO[j][w] = O[j][w];
 #endif
             if (act[j]) {
                 if constexpr (NSW == 2) {
@@ -225,10 +251,13 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
                 }
             }
 #undef QSW_WALKED
-            A1[j] = a1; A2[j] = a2; KST[j] = kst;
+            S1[j] = a1; S2[j] = a2; KOLD[j] = kst;           // (outside the test: a lane without a check keeps nothing worth a register of its own)
         }
         __builtin_amdgcn_s_setprio(0);
         pf = QS_ADJ_FIRST;              // for the scatter pass behind the barrier
+#pragma unroll
+        for (int j = 0; j < CPL; ++j)
+            if (act[j]) FX[j] = QS_FIX_ADDR(j);
         int anyun;
         QSW_VOTE(us, anyun)
         if (t >= 1 && !anyun) { converged = 1; break; }
@@ -246,9 +275,9 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
         for (int j = 0; j < CPL; ++j) {
 #ifdef QSW_STATS
             {
-                bool same = A1[j] == S1[j] && A2[j] == S2[j] && (KST[j] == KOLD[j] || A1[j] == A2[j]);
+                bool same = S1[j] == P1[j] && S2[j] == P2[j] && (KOLD[j] == PK[j] || S1[j] == S2[j]);
 #pragma unroll
-                for (int w = 0; w < NSW; ++w) same = same && Q[j][w] == O[j][w];
+                for (int w = 0; w < NSW; ++w) same = same && O[j][w] == PO[j][w];
                 const unsigned long long ba = __ballot(act[j]), bs = __ballot(act[j] && same);
                 if ((tid & 63) == 0 && ba) {
                     const int bk = min(t / 10, 4);
@@ -264,9 +293,9 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
                 const int trip = dwj & 0xFF, wmax = (dwj >> 8) & 0xFF, wmin = (dwj >> 16) & 0xFF, wmin4 = wmin & ~3;
                 const int adj_voff = cs[j] * 16;
                 const int dc = dcs[j];
-                const int n1 = (int)A1[j], nx = n1 ^ -n1;
-                const uint32_t kst = KST[j];
-                const uint32_t fixn_off = __builtin_amdgcn_raw_buffer_load_b32(adj_rsrc, (int)((kst >> 2) * (uint32_t)adj_row + (kst & 3u) * 4u) + adj_voff, 0, 0);
+                const int n1 = (int)S1[j], nx = n1 ^ -n1;
+                const uint32_t kst = KOLD[j];
+                const uint32_t fixn_off = FX[j];
                 const int ng = trip >> 2;
                 // The sign / difference bit of an edge is picked with a scalar bit position (v_bfe_i32 with an SGPR offset) instead of shifting the two
                 // words by 4 per group: half a vector instruction per edge moves to the scalar unit.  BP stage 42.35 -> 42.24 ms per 65 536 headline
@@ -292,7 +321,7 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
                 for (int w = 0; w < NSW; ++w) {
                     if (32 * w < trip) {
                         const int kendw = min(trip - 32 * w, 32);
-                        const uint32_t own = Q[j][w];
+                        const uint32_t own = O[j][w];
                         const int g1 = min(ng, 8 * w + 8);                    // groups of this word: [8 w, g1)
                         const int gp = min(g1, max(wmin4 >> 2, 8 * w));       // ... of which [8 w, gp) are plain (as in the gather pass: three loops, no test per group)
                         uint4 ea = (j == 0 && w == 0) ? pf : QS_ADJ(8 * w), eb;
@@ -323,21 +352,24 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
 #undef QS_GROUP_TAIL
 #undef QS_SCAT_TAIL
 #undef QS_GROUP_POS
-                // the argmin edge carries min2, not min1: it gains +-(min2 - min1)
+                // the argmin edge carries min2, not min1: it gains +-(min2 - min1).  Its sign is bit kend_w - 1 - (kst - 32 w) of its word w (kend_w is
+                // wave-uniform: one subtraction from a scalar per word, the word and the bit picked by the same compare), taken as a mask m = 0 / -1 by one
+                // v_bfe_i32 and applied as (dlt ^ m) - m; kst < the lane's degree <= trip, so the bit position is within 0..31.
                 {
-                    const int kw = (int)(kst >> 5), kendw = min(trip - 32 * kw, 32);
-                    uint32_t wd = Q[j][0];
+                    uint32_t wd = O[j][0];
+                    int bpos = min(trip, 32) - 1 - (int)kst;
 #pragma unroll
-                    for (int w = 1; w < NSW; ++w) wd = (kw == w) ? Q[j][w] : wd;
-                    const uint32_t sg_ = (wd >> (kendw - 1 - (int)(kst & 31u))) & 1u;
-                    const int dlt = (int)A2[j] - n1;
-                    const int vn = sg_ ? -dlt : dlt;
+                    for (int w = 1; w < NSW; ++w) {
+                        const bool inw = kst >= 32u * (uint32_t)w;
+                        wd = inw ? O[j][w] : wd;
+                        bpos = inw ? min(trip - 32 * w, 32) - 1 + 32 * w - (int)kst : bpos;
+                    }
+                    const int m_ = __builtin_amdgcn_sbfe((int)wd, bpos, 1);
+                    const int dlt = (int)S2[j] - n1;
+                    const int vn = (dlt ^ m_) - m_;
                     (void)__hip_atomic_fetch_add(QS_LDS(fixn_off), vn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 }
             }
-            S1[j] = A1[j]; S2[j] = A2[j]; KOLD[j] = KST[j];
-#pragma unroll
-            for (int w = 0; w < NSW; ++w) O[j][w] = Q[j][w];
         }
         __builtin_amdgcn_s_setprio(0);
         pf = QS_ADJ_FIRST;              // for the next gather pass
@@ -349,7 +381,7 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
         // away; what is left is the parity of the hard decisions, the convergence test of the last iteration.  Steps beyond a check's degree read a
         // trash slot, which holds 0: they cannot set bit 31.  The pass's second minima do not enter mx2 either: they are magnitudes of messages of
         // iteration max_iter + 1, which nobody sends -- every sum that was computed is covered by the minima of the passes before.
-        bool us = false;
+        uint32_t us = 0u;
 #pragma unroll
         for (int j = 0; j < CPL; ++j) {
             QSW_GATHER_PRIO(j)
@@ -371,7 +403,7 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
                 }
                 if (gi < ng) QS_HP_GROUP(nx)
 #undef QS_HP_GROUP
-                us = us || (((synd[j] ^ (hp >> 31)) & 1u) != 0u);
+                QSW_VOTE_ROUND(us, synd[j], hp)
             }
         }
         __builtin_amdgcn_s_setprio(0);
@@ -380,8 +412,10 @@ __global__ void __launch_bounds__(T, MW) qd_bp_scatter_wide_kernel(BpGraphDev g,
         if (!anyun) converged = 1;                  // (t = max_iter >= 1)
     }
 #undef QSW_VOTE
+#undef QSW_VOTE_ROUND
 #undef QS_ADJ
 #undef QS_ADJ_FIRST
+#undef QS_FIX_ADDR
 #undef QSW_GATHER_PRIO
     // L(t) - 1 is in the buffer: the scatter pass of the last iteration did not run
 
